@@ -3,7 +3,7 @@
 (BASELINE.json `metric`; workload = configs[1]: batch 256 per GPU, N = 32,
 bf16 autocast, random-init weights, synthetic PCQM-schema graphs).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = preprocess (edge mask, coordinate noise, distances) + forward + loss +
@@ -13,11 +13,15 @@ resident in HBM before the timed region.  One process per GPU; graphs are
 independent, so each rank steps its own 256 graphs (weak scaling) and the only
 exchange is the gradient all-reduce.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and
+prints it (contract fields, per-step durations, memory counters).  With --full
+the line also carries
   roofline     : the dominant hand-written kernel (triplet attention backward or
                  forward), algorithmic HBM bytes / HIP-event time inside the timed steps
+                 and over extra single-stream steps after them
   cpu_baseline : the oracle (CPU restatement of the reference) timed on this
                  host on a bounded sample of the same workload (N=1 only).
+--dump-outputs DIR writes what the last timed step computed on rank 0 as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -201,6 +205,23 @@ def launcher_selftest(rank, world):
     dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 1 << 22                       # elements kept of a larger array (16 MB as float32)
+
+
+def dump_outputs(path, arrays):
+    """name -> tensor as path/<name>.npy (float64 stays float64, every other dtype becomes float32).  An array of more than
+    DUMP_SAMPLE elements is written as `<name>_sample`: the same DUMP_SAMPLE flat indices (seeded by the array's size) every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(t.numel()))
+            t, name = t.reshape(-1)[idx.to(t.device)], name + '_sample'
+        t = t.cpu().double() if t.dtype == torch.float64 else t.cpu().float()
+        np.save(os.path.join(path, name + '.npy'), t.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -241,7 +262,15 @@ def main():
                          'two ranks on one device).  Walks the exact multi-rank branch of this file -- rendezvous, rank-0 broadcast, '
                          'bucketed gradient exchange from the hooks, settle-step count, all_gather of the timings, per-rank NUMA binding, '
                          'per-rank TunableOp files -- on a 1-GPU box; the number it prints is NOT a scaling figure (config says so)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the roofline leg (HIP events around its kernels inside the timed '
+                         'steps, then --roofline-steps single-stream steps) and the CPU baseline; implied by --profile-all and '
+                         '--cpu-baseline-full')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what the last one computed on rank 0 as DIR/<name>.npy: the model outputs (gap, '
+                         'distance-bin logits), the loss and the float32 parameters after its Adam update (a fixed sample of the large ones)')
     args = ap.parse_args()
+    args.full = args.full or args.profile_all or args.cpu_baseline_full
     if args.cpu_baseline_worker:
         cpu_baseline_worker(args.cpu_baseline_worker, full=args.cpu_baseline_full)
         return
@@ -339,6 +368,10 @@ def main():
     # start-up transient (synchronous hipMalloc calls during the first ~50 steps of any run) out of the timed region.
     settled = 0
     if args.settle_steps > 0:
+        # How many settle steps run depends on the allocator, and each one trains the model and draws from the random streams.  The
+        # warm-up and timed steps start from the state before them instead (initial parameters, zero Adam moments, step counts,
+        # control block, seeds), so that what the timed steps compute -- what --dump-outputs writes -- is the same from run to run.
+        start = (trainer.flat.param.cpu(), trainer.ctl.clone(), trainer.state_dict())
         quiet, last = 0, torch.cuda.memory_stats(dev).get('num_device_alloc', 0)
         # (every step runs the ranks' gradient exchange: with more than one rank the COUNT must not depend on a rank's own allocator)
         while settled < args.settle_steps and (quiet < 16 or world > 1):
@@ -347,6 +380,13 @@ def main():
             now = torch.cuda.memory_stats(dev).get('num_device_alloc', 0)
             quiet = quiet + 1 if now == last else 0
             last = now
+        trainer.flat.param.copy_(start[0])
+        trainer.ctl.copy_(start[1])
+        trainer.load_state_dict(start[2])            # (zeroes the moments and step counts, refreshes the 16-bit shadow)
+        torch.manual_seed(4321 + rank)
+        gen.manual_seed(1234 + rank)
+        ops.reset_random_pools()
+        del start
     for i in range(args.warmup):
         step(i)
     # The host queues a step ~20 ms ahead of the GPU.  A generation-2 collection of Python's garbage collector walks every tracked
@@ -362,7 +402,7 @@ def main():
                         'tgt_node_attention_fwd', 'tgt_node_attention_bwd')
     if args.profile_all:          # (A/B: events around every launch, as rounds 1-4 did)
         ROOFLINE_KERNELS = None
-    prof = ops.profile_kernels(True, only=ROOFLINE_KERNELS, stride=1 if ROOFLINE_KERNELS is None else 5)
+    prof = ops.profile_kernels(True, only=ROOFLINE_KERNELS, stride=1 if ROOFLINE_KERNELS is None else 5) if args.full else None
     fence()
     ms0 = torch.cuda.memory_stats(dev)
     # one event per step on the step's stream (GPU-side step boundaries: the spread of the steps, e.g. one stalled by a
@@ -375,7 +415,7 @@ def main():
     marks[0].record()
     for i in range(args.steps):
         h0 = time.perf_counter()
-        _, loss = step(args.warmup + i)
+        outputs, loss = step(args.warmup + i)
         marks[i + 1].record()
         host_ms.append((time.perf_counter() - h0) * 1e3)
         # (a non-blocking query: True = the GPU had already finished the previous step when the host finished queueing this one,
@@ -392,12 +432,15 @@ def main():
     n_comm_timed = len(trainer._comm_events) - n_comm_before
     ms1 = torch.cuda.memory_stats(dev)
     ops.profile_kernels(False)
+    if args.dump_outputs and rank == 0:
+        # (before the roofline steps below, which step the parameters again)
+        dump_outputs(args.dump_outputs, dict(gap=outputs[0], dist_logits=outputs[1], loss=loss, params=trainer.flat.param))
     # Kernel durations for `roofline`: inside the timed region the node channel runs on a second HIP stream and its kernels share
     # the CUs with the edge kernels, so an event pair around an edge launch also sees the other stream's work (and the wait for
     # CUs it holds).  A few more steps of the same loop, NOT timed, with everything on one stream give the kernel's own duration
     # -- the number `TGT_NODE_STREAM=0 rocprofv3 --kernel-trace --stats` of this command shows (profiles/).  Both are reported.
     prof_iso = None
-    if ops.side_stream.enabled and args.roofline_steps > 0:
+    if args.full and ops.side_stream.enabled and args.roofline_steps > 0:
         ops.side_stream.enabled = False
         forked, ops._WGRAD_STREAM = ops._WGRAD_STREAM, False      # (the forked parameter-gradient stream as well: one stream, kernels alone)
         step(args.warmup + args.steps)                    # (one step for the allocator to settle on the new stream pattern)
@@ -423,7 +466,7 @@ def main():
     loss_val = float(loss.detach())
 
     if rank == 0:
-        times_region = ops.kernel_times_ms(prof)
+        times_region = ops.kernel_times_ms(prof) if prof is not None else {}      # (no roofline without --full)
         times = ops.kernel_times_ms(prof_iso) if prof_iso is not None else times_region
         C, Ht = mcfg['edge_width'], mcfg['triplet_heads']
         esz = 4 if args.precision == 'fp32' else 2
@@ -450,7 +493,7 @@ def main():
         # tools/pmc_summary.py) at this shape; anything else is reported as stale, not as a measurement.
         traffic, pmc, pmc_note = {}, {}, None
         n48 = args.batch == 128 and args.nodes == 48 and args.precision == 'bf16'          # BASELINE config 4's shape has its own counter pass (profiles/*_n48_pmc_summary.json)
-        if ((args.batch == 256 and args.nodes == 32) or n48) and args.precision == 'bf16':
+        if args.full and ((args.batch == 256 and args.nodes == 32) or n48) and args.precision == 'bf16':
             sys.path.insert(0, os.path.join(ROOT, 'tools'))
             from pmc_summary import kernel_source_sha
             sha = kernel_source_sha(ROOT)
@@ -570,8 +613,10 @@ def main():
                                               per_step=ahead[:64],
                                               note='step-end marks (of the last 6) the GPU had not reached when the host finished queueing a step: 0 = the stream ran dry')),
             # conditions of the timed region a plain Trainer loop does not get by itself: stated, not hidden
-            timed_region_policy=dict(gc_frozen=True, allocator_settle='up to --settle-steps untimed steps until 16 in a row make no device allocation',
-                                     numa_bound=bool(host_affinity.get('bound')), per_kernel_events='roofline kernels only, one launch in five'),
+            timed_region_policy=dict(gc_frozen=True, allocator_settle='up to --settle-steps untimed steps until 16 in a row make no device allocation, '
+                                                                      'then the state before them restored',
+                                     numa_bound=bool(host_affinity.get('bound')),
+                                     per_kernel_events='roofline kernels only, one launch in five' if args.full else 'none'),
             roofline=roofline,
             # the caching allocator inside the timed region: device allocations / frees there are synchronous driver calls
             allocator_settle_steps=settled,
@@ -581,7 +626,7 @@ def main():
                         device_frees_in_timed_region=ms1.get('num_device_free', 0) - ms0.get('num_device_free', 0),
                         alloc_retries=ms1.get('num_alloc_retries', 0)),
         )
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if host_mask is not None:
                 from tgt_amd.training.affinity import restore_affinity
                 restore_affinity(host_mask)                 # the oracle's step runs on all of the host's cores again (every thread)

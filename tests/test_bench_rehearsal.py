@@ -28,7 +28,7 @@ def _bench(args, timeout=900):
 @pytest.mark.parametrize('launcher', ['self', 'torchrun', 'self_sharded'])
 def test_bench_two_ranks_share_one_gpu(launcher):
     common = ['--gpus', '2', '--share-device', '--batch', '16', '--steps', '3', '--warmup', '1', '--settle-steps', '3',
-              '--roofline-steps', '1', '--no-cpu-baseline']
+              '--full', '--roofline-steps', '1', '--no-cpu-baseline']
     if launcher == 'self_sharded':                          # the sharded-optimizer exchange (StepConfig.shard_optimizer) through the same branch
         out = _bench(common + ['--grad-exchange', 'reduce_scatter_sharded'])
         assert out['grad_exchange']['optimizer_sharded'] is True and out['grad_exchange']['mode'] == 'reduce_scatter'
@@ -58,3 +58,32 @@ def test_bench_two_ranks_share_one_gpu(launcher):
     assert out['allocator_settle_steps'] == 3              # every rank ran the same count (it drives collectives)
     assert out['value'] > 0 and abs(out['value'] - 32 * 3 / (out['ms_per_step'] * 3e-3)) < 1e-3 * out['value'] + 1
     assert out['roofline'] is not None and out['final_loss'] == out['final_loss']        # a number, not NaN
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_its_last_step(tmp_path):
+    """`bench.py --gpus 1` without --full: --steps timed steps, ms_per_step, no roofline / CPU baseline; --dump-outputs writes the
+    last timed step's arrays as float32 / float64 .npy files (64 MB at most), and they do not depend on how many allocator settle
+    steps ran before the warm-up (the state before them is restored)"""
+    import numpy as np
+    common = ['--gpus', '1', '--batch', '16', '--steps', '3', '--warmup', '1', '--no-gemm-tuning']     # (16 x 32 x 32 x 512 logits: sampled)
+    dumps = []
+    for k, settle in enumerate(('4', '2')):
+        d = tmp_path / str(k)
+        out = _bench(common + ['--settle-steps', settle, '--dump-outputs', str(d)], timeout=600)
+        assert out['steps'] == 3 and out['allocator_settle_steps'] == int(settle)
+        assert out['ms_per_step'] > 0 and abs(out['value'] - 16 * 3 / (out['ms_per_step'] * 3e-3)) < 1e-3 * out['value'] + 1
+        assert out['roofline'] is None and 'cpu_baseline' not in out
+        files = sorted(os.listdir(d))
+        assert files == ['dist_logits_sample.npy', 'gap.npy', 'loss.npy', 'params_sample.npy'], files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f: np.load(d / f) for f in files})
+    assert dumps[0]['gap.npy'].shape == (16,) and dumps[0]['loss.npy'].shape == ()
+    for f, a in dumps[0].items():
+        b = dumps[1][f]
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.isfinite(a).all(), f
+        # the step is not bitwise reproducible (bf16 outputs move by a few units in the last place between runs); another
+        # dropout / DropPath stream or another parameter state moves most elements by far more than this
+        diff = np.abs(b.astype(np.float64) - a)
+        assert diff.max() <= 0.1 * np.abs(a).max() + 1e-6 and diff.mean() <= 2e-2 * np.abs(a).mean() + 1e-6, \
+            (f, float(diff.max()), float(diff.mean()))

@@ -15,7 +15,7 @@ for ((i = 0; i < rounds; ++i)); do
   for arm in "$@"; do
     envs=(); flags=()
     for w in $arm; do case $w in -*) flags+=($w);; *=*) if [ ${#flags[@]} -eq 0 ]; then envs+=($w); else flags+=($w); fi;; *) flags+=($w);; esac; done
-    env "${envs[@]}" timeout 900 python bench.py --no-cpu-baseline --steps $STEPS --warmup $WARMUP "${flags[@]}" 2>/dev/null | tail -1 > $O/${n}_$i.json
+    env "${envs[@]}" timeout 900 python bench.py --full --no-cpu-baseline --steps $STEPS --warmup $WARMUP "${flags[@]}" 2>/dev/null | tail -1 > $O/${n}_$i.json
     python - "$arm" $O/${n}_$i.json <<'PY'
 import json, sys
 arm, f = sys.argv[1], sys.argv[2]
