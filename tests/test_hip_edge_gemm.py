@@ -370,7 +370,7 @@ def test_ffn_block_with_fused_activation_both_ways(dtype, p, prescaled, monkeypa
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
-@pytest.mark.parametrize('rows,cols', [(4100, 256), (333, 64), (9000, 512), (77, 128)])
+@pytest.mark.parametrize('rows,cols', [(4100, 256), (333, 64), (9000, 512), (77, 128), (262144, 256)])
 @pytest.mark.parametrize('p', [0.0, 0.2])
 def test_gelu_backward_with_bias_gradient_column_sums(dtype, rows, cols, p):
     """tgt_gelu_dropout_bwd_colsum: dx bit-equal to tgt_gelu_dropout_scaled_bwd, colsum = float64 column sums of the STORED dx"""
@@ -532,6 +532,153 @@ def test_grid_cap_hook_walks_many_tiles_per_workgroup(case, dtype, cap):
     z = a.double() @ w.double().t()
     if epi == 'bias':
         assert rel(got[0], z + b.double()) < TOL[dtype]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The two BACKWARD epilogues at BASELINE size, against float64: lin_W2's data gradient + GELU / dropout backward + lin_W1's
+# bias-gradient column sums (EPI_GELU_BWD), and the consumer's data gradient + LayerNorm backward + stream gradient + row scale
+# + three column-sum planes (EPI_LN_BWD).  At 262144 rows each persistent workgroup walks 32 tiles and writes ONE colsum_partial
+# row, so the cross-tile accumulators are what the column sums test; under grid caps 1 and 3 a ~1600-row problem is 17..50
+# tiles per workgroup.  (Above, these epilogues run one tile per workgroup, and at size they are only held to each other.)
+# ---------------------------------------------------------------------------------------------------------------
+_CHUNK = 32768          # float64 references over all rows go in chunks of this many rows (one 262144-row piece is 0.5 GB)
+
+
+def _colsum_close(got, want):
+    """the bar of test_gelu_backward_with_bias_gradient_column_sums: max |got - want| <= 1e-5 max |want| + 1e-6 (error on record
+    relative to max |want|)"""
+    top = float(want.abs().max())
+    err = parity_log.record(float((got - want).abs().max()) / (top + 1e-30))
+    return err * top <= 1e-5 * top + 1e-6, err
+
+
+def _gelu_bwd_check(M, rps, dtype, p, with_scale, blocks, slices=()):
+    TOL[dtype]                  # (files the comparisons below under this dtype in the parity log)
+    K = N = 256
+    a, w, _, g = _mk(M, K, N, dtype, 43, bias=False)
+    pre = torch.randn(M, N, device='cuda', generator=g).to(dtype)
+    sc = (torch.rand(-(-M // rps), device='cuda', generator=g) + 0.5) if with_scale else None
+    seed = 0x9e1b5eed if p else 0
+    L = _lib.lib()
+
+    def run(s, e):
+        cs = torch.empty(L.tgt_edge_linear_parts(e - s, N), N, device='cuda')
+        out = ops.edge_linear_raw(a[s:e], w, None, _lib.EPI_GELU_BWD, res=pre[s:e], out_scale=None if sc is None else sc[s // rps:],
+                                  rows_per_sample=rps if with_scale else 0, dropout=(p, seed), colsum_partial=cs)
+        return out, cs
+
+    out, cs = run(0, M)
+    keep = None
+    if p:                   # the keep pattern of the standalone kernel (same generator, indexed by the absolute element)
+        one, kd = torch.ones_like(pre), torch.empty_like(pre)
+        _lib.check(L.tgt_gelu_dropout_bwd(pre.data_ptr(), one.data_ptr(), kd.data_ptr(), pre.numel(), ops._DT[dtype], p, seed, None), 'gd')
+        keep = kd != 0
+        del one, kd
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(cs).all())
+    f = sc.double().repeat_interleave(rps)[:M, None] if with_scale else None
+    for s, e in blocks:
+        dy = (a[s:e].double() @ w.double().t()).to(dtype).double()          # the GEMM result is rounded to the 16-bit type first,
+        if with_scale:
+            dy = (dy * f[s:e]).to(dtype).double()                             # and again after the per-graph factor
+        x = pre[s:e].double()
+        ref = dy * (0.5 * (1 + torch.erf(x / math.sqrt(2.0))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2 * math.pi)) / (1 - p)
+        if keep is not None:
+            ref = ref * keep[s:e]
+        assert rel(out[s:e], ref) < TOL[dtype], (s, rel(out[s:e], ref))
+    # the column sums (lin_W1's bias gradient) are those of the d_pre AS STORED
+    want = torch.zeros(N, dtype=torch.float64, device='cuda')
+    for i in range(0, M, _CHUNK):
+        want += out[i:i + _CHUNK].double().sum(0)
+    ok, err = _colsum_close(cs.double().sum(0), want)
+    assert ok, ('colsum', err)
+    for s, e in slices:     # a row's result does not depend on the workgroup / stage that computed it
+        assert torch.equal(out[s:e], run(s, e)[0]), s
+
+
+def _ln_bwd_check(M, K, rps, dtype, blocks, slices=()):
+    TOL[dtype]                  # (files the comparisons below under this dtype in the parity log)
+    N = 256
+    a, w, _, g = _mk(M, K, N, dtype, 47, bias=False)
+    s_ = (torch.randn(M, N, device='cuda', generator=g) * 1.3 + 0.2).to(dtype)
+    gamma = torch.rand(N, device='cuda', generator=g) + 0.5
+    ds = torch.randn(M, N, device='cuda', generator=g).to(dtype)
+    sc = (torch.rand(-(-M // rps), device='cuda', generator=g) > 0.2).float() / 0.8          # DropPath factors, zeros included
+    zero = torch.zeros_like(gamma)
+    mean, rstd = torch.empty(M, device='cuda'), torch.empty(M, device='cuda')
+    for i in range(0, M, _CHUNK):
+        _, mu, rs = _ln64(s_[i:i + _CHUNK], gamma, zero, 1e-5)
+        mean[i:i + _CHUNK], rstd[i:i + _CHUNK] = mu.float(), rs.float()
+    L = _lib.lib()
+
+    def run(s, e):
+        partial = torch.empty(L.tgt_edge_linear_parts(e - s, N), 3 * N, device='cuda')
+        dres = torch.empty(e - s, N, dtype=dtype, device='cuda')
+        dx = torch.empty(e - s, N, dtype=dtype, device='cuda')
+        ops.edge_linear_raw(a[s:e], w, None, _lib.EPI_LN_BWD, ln=(gamma, None, 1e-5), stats=(mean[s:e], rstd[s:e]), res=s_[s:e],
+                            ds_in=ds[s:e], out=dres, out2=dx, row_scale=sc[s // rps:], rows_per_sample=rps, colsum_partial=partial)
+        return dres, dx, partial
+
+    dres, dx, partial = run(0, M)
+    torch.cuda.synchronize()
+    for t in (dres, dx, partial):
+        assert bool(torch.isfinite(t).all())
+    f = sc.double().repeat_interleave(rps)[:M, None]
+
+    def ref64(s, e):
+        dy = (a[s:e].double() @ w.double().t()).to(dtype).double()          # the unfused chain stores dy in the 16-bit type
+        _, mu, rs = _ln64(s_[s:e], gamma, zero, 1e-5)
+        xh = (s_[s:e].double() - mu[:, None]) * rs[:, None]
+        gg = dy * gamma.double()
+        d = rs[:, None] * (gg - gg.mean(-1, keepdim=True) - xh * (gg * xh).mean(-1, keepdim=True)) + ds[s:e].double()
+        return dy, xh, d
+
+    for s, e in blocks:
+        _, _, d = ref64(s, e)
+        assert rel(dres[s:e], d) < TOL[dtype], ('d_res', s)
+        assert rel(dx[s:e], dres[s:e].double() * f[s:e]) < TOL[dtype], ('dx', s)        # of the d_res AS STORED
+    # the three planes: dgamma = sum dy xhat, dbeta = sum dy, the consumer's bias gradient = sum of dx AS STORED
+    want = torch.zeros(3, N, dtype=torch.float64, device='cuda')
+    for i in range(0, M, _CHUNK):
+        dy, xh, _ = ref64(i, min(M, i + _CHUNK))
+        want[0] += (dy * xh).sum(0)
+        want[1] += dy.sum(0)
+        want[2] += dx[i:i + _CHUNK].double().sum(0)
+    tot = partial.double().sum(0).view(3, N)
+    for j, name in enumerate(('dgamma', 'dbeta', 'dx colsum')):
+        assert rel(tot[j], want[j]) < 1e-4, (name, rel(tot[j], want[j]))
+    for s, e in slices:
+        part = run(s, e)
+        assert torch.equal(dres[s:e], part[0]) and torch.equal(dx[s:e], part[1]), s
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('p', [0.0, 0.1])
+@pytest.mark.parametrize('with_scale', [True, False])
+def test_gelu_backward_epilogue_at_baseline_size(dtype, p, with_scale):
+    _gelu_bwd_check(SIZE_M, 1024, dtype, p, with_scale, SIZE_BLOCKS, SIZE_SLICES if p == 0 else ())
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('K', [256, 128])        # the consumer: lin_W1 (256 -> 256), lin_EG (256 -> 128)
+def test_layernorm_backward_epilogue_at_baseline_size(dtype, K):
+    _ln_bwd_check(SIZE_M, K, 1024, dtype, SIZE_BLOCKS, SIZE_SLICES)
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('case', ['gelu_bwd', 'gelu_bwd scaled p=0.1', 'ln_bwd K=256', 'ln_bwd K=128'])
+@pytest.mark.parametrize('cap', [1, 3])
+def test_grid_cap_hook_walks_many_tiles_in_the_backward_epilogues(case, dtype, cap):
+    """the backward epilogues with 17..50 tiles per workgroup (1591 rows on `cap` workgroups), every row against float64"""
+    M, rps = 1600 - 9, 100
+    _lib.lib().tgt_edge_linear_set_grid_cap(cap)
+    try:
+        if case.startswith('gelu_bwd'):
+            _gelu_bwd_check(M, rps, dtype, 0.1 if 'p=0.1' in case else 0.0, 'scaled' in case, [(0, M)])
+        else:
+            _ln_bwd_check(M, int(case.split('K=')[1]), rps, dtype, [(0, M)])
+    finally:
+        _lib.lib().tgt_edge_linear_set_grid_cap(0)
 
 
 # ---------------------------------------------------------------------------------------------------------------

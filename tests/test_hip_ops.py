@@ -774,6 +774,85 @@ def test_add_layer_norm(dtype, with_scale):
     assert rel(wg.grad, w64.grad) < 2 * tol and rel(bg.grad, b64.grad) < 2 * tol
 
 
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('rows,C', [(262144, 256), (8192, 768)])
+def test_layer_norm_backward_reductions_at_size(rows, C, dtype):
+    """ops.layer_norm and ops.add_layer_norm (per-graph scale, stream gradient ds) backward at the benchmark's edge size (262144 x 256:
+    1280 partial rows, the in-LDS accumulators of the one-vector-per-lane form) and at node width (8192 x 768: two vectors per lane,
+    1024 partial rows): dgamma, dbeta and the column sums of the x-branch gradient (the bias gradient handed to the Linear that
+    produced x) against chunked float64 sums, which see the same stored operands -- hence the 1e-4 bar of the fp32 accumulation,
+    not the storage tolerance; the row gradients on sampled blocks at 2x the forward tolerance."""
+    from tgt_amd import ops
+    rps = 1024
+    B = rows // rps
+    g = torch.Generator(device='cuda').manual_seed(rows + C)
+    x = (torch.randn(B, rps, C, device='cuda', generator=g) * 1.5 + 0.3).to(dtype)
+    res = torch.randn(B, rps, C, device='cuda', generator=g).to(dtype)
+    w = torch.rand(C, device='cuda', generator=g) + 0.5
+    b = torch.randn(C, device='cuda', generator=g) * 0.1
+    dy = torch.randn(B, rps, C, device='cuda', generator=g).to(dtype)
+    ds = torch.randn(B, rps, C, device='cuda', generator=g).to(dtype)
+    scale = (torch.rand(B, device='cuda', generator=g) > 0.25).float() / 0.75          # DropPath factors, zeros included
+    f = scale.double().repeat_interleave(rps)[:, None]
+    blocks = [(0, 96), (10240 - 48, 10240 + 48), (rows // 2 - 40, rows // 2 + 60), (rows - 128, rows)]
+    chunk = 32768
+    tol = TOL[dtype]
+
+    def ln_bwd64(xs, dys, s, e):
+        """float64 LayerNorm backward of rows [s:e) of the stored input: (xhat, dy, d_input)"""
+        xv, dv = xs.reshape(rows, C)[s:e].double(), dys.reshape(rows, C)[s:e].double()
+        mu = xv.mean(-1, keepdim=True)
+        rs = 1 / torch.sqrt(((xv - mu) ** 2).mean(-1, keepdim=True) + 1e-5)
+        xh = (xv - mu) * rs
+        gg = dv * w.double()
+        return xh, dv, rs * (gg - gg.mean(-1, keepdim=True) - xh * (gg * xh).mean(-1, keepdim=True))
+
+    def sums64(xs, dys, extra=None):
+        out = torch.zeros(3, C, dtype=torch.float64, device='cuda')
+        for i in range(0, rows, chunk):
+            e = min(rows, i + chunk)
+            xh, dv, d = ln_bwd64(xs, dys, i, e)
+            out[0] += (dv * xh).sum(0)
+            out[1] += dv.sum(0)
+            if extra is not None:
+                out[2] += extra(d, i, e).sum(0)
+        return out
+
+    # plain LayerNorm
+    xg, wg, bg = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    y = ops.layer_norm(xg, wg, bg, 1e-5, out_dtype=dtype)
+    y.backward(dy)
+    torch.cuda.synchronize()
+    want = sums64(x, dy)
+    assert rel(wg.grad, want[0]) < 1e-4 and rel(bg.grad, want[1]) < 1e-4, (rel(wg.grad, want[0]), rel(bg.grad, want[1]))
+    for s, e in blocks:
+        assert rel(xg.grad.view(rows, C)[s:e], ln_bwd64(x, dy, s, e)[2]) < 2 * tol, ('dx', s)
+    del xg, wg, bg, y
+
+    # residual add + LayerNorm: s = res + scale * x, y = LN(s); the loss sees both s (ds) and y (dy)
+    xg, rg = x.clone().requires_grad_(True), res.clone().requires_grad_(True)
+    wg, bg = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    handed = []
+
+    def take(grad):
+        handed.append(ops._take_colsum(grad, C))
+
+    xg.register_hook(take)
+    s_, y = ops.add_layer_norm(xg, rg, scale, wg, bg, 1e-5, out_dtype=dtype)
+    torch.autograd.backward([s_, y], [ds, dy])
+    torch.cuda.synchronize()
+    assert len(handed) == 1 and handed[0] is not None, 'the x-branch column sums were not handed over'
+    s_ = s_.detach()
+    dsf = ds.reshape(rows, C)
+    want = sums64(s_, dy, lambda d, i, e: (d + dsf[i:e].double()) * f[i:e])
+    for j, (name, got) in enumerate((('dgamma', wg.grad), ('dbeta', bg.grad), ('x colsum', handed[0]))):
+        assert rel(got, want[j]) < 1e-4, (name, rel(got, want[j]))
+    for s, e in blocks:
+        d_res = ln_bwd64(s_, dy, s, e)[2] + dsf[s:e].double()
+        assert rel(rg.grad.view(rows, C)[s:e], d_res) < 2 * tol, ('d_res', s)
+        assert rel(xg.grad.view(rows, C)[s:e], d_res * f[s:e]) < 2 * tol, ('d_x', s)
+
+
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize('with_scale', [False, True])
 @pytest.mark.parametrize('permuted', [False, True])
