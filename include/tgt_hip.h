@@ -292,17 +292,25 @@ int tgt_loss_accumulate(const void* loss, int32_t loss_is_f64, float samples, fl
  *                    that produced the branch, to be summed over the rows (tgt_sum_planes).  No bias (a data-gradient GEMM).
  *   TGT_EPI_RESID with gamma / beta / y: additionally y = LayerNorm(out as stored; gamma, beta, eps), mean / rstd (M)
  *                    float32 written when given (N <= 256): the fused entry of the next pre-norm sub-block.
+ *   TGT_EPI_GLU      (ABI 31; K = 256, N = 512) out2 (M, 512) = z = [g | e], the pre-activation as stored (bit-identical to a
+ *                    TGT_EPI_BIAS launch of the same operands); out (M, 256) = dropout(e * act(g), dropout_p, dropout_seed)
+ *                    * row_scale[m / rows_per_sample] (row_scale may be NULL): tgt_glu_dropout_fwd on out2, bit for bit, in the
+ *                    store phase of the GEMM.  The kind (TGT_GLU_*) travels in flags: kind << TGT_EDGE_GLU_KIND_SHIFT.
  * Element type 16-bit (TGT_BF16 / TGT_F16; bias in the same type); N % 8 == 0; K in {64, 128, 256}.
  * tgt_edge_linear_supported() tells; anything else is the caller's library GEMM + tgt_layer_norm_* path.
  * tgt_edge_linear_set_grid_cap(cap): TEST HOOK -- at most `cap` persistent workgroups per launch (0 = no cap), so that small
  * problems walk several row tiles per workgroup the way the BASELINE-size launches do.
  * ---------------------------------------------------------------------- */
-enum { TGT_EPI_BIAS = 0, TGT_EPI_GELU = 1, TGT_EPI_RESID = 2, TGT_EPI_GELU_BWD = 3, TGT_EPI_LN_BWD = 4 };
+enum { TGT_EPI_BIAS = 0, TGT_EPI_GELU = 1, TGT_EPI_RESID = 2, TGT_EPI_GELU_BWD = 3, TGT_EPI_LN_BWD = 4, TGT_EPI_GLU = 5 };
+/* the gated activations y = e * act(g) of x = [g | e] (gate half first; reference lib/tgt/layers/activations.py:4-17):
+ * geglu act = gelu (erf form), glu act = sigmoid, swiglu act = g * sigmoid(g) */
+enum { TGT_GLU_GEGLU = 0, TGT_GLU_GLU = 1, TGT_GLU_SWIGLU = 2 };
 /* flags.  TGT_EDGE_BIAS_SCALED (TGT_EPI_RESID, N = 256, K in {64,128,256}): a arrives PRE-SCALED by row_scale (its producer
  * folded the DropPath factor in: tgt_gelu_dropout_scaled_fwd, tgt_node_attention_args.hhat_scale), so
  *     out = res + a W^T + row_scale[row / rows_per_sample] * bias
  * and the backward of the block needs no scaled copy of the stream gradient (tgt_add_layer_norm_bwd with scale and d_x = NULL). */
-enum { TGT_EDGE_BIAS_SCALED = 1 };
+/* bits 1-2 (ABI 31, TGT_EPI_GLU only): the activation, TGT_GLU_* << TGT_EDGE_GLU_KIND_SHIFT */
+enum { TGT_EDGE_BIAS_SCALED = 1, TGT_EDGE_GLU_KIND_SHIFT = 1, TGT_EDGE_GLU_KIND_MASK = 6 };
 typedef struct tgt_edge_linear_args {
     int64_t M;
     int32_t K, N, dtype, epilogue;
@@ -392,6 +400,19 @@ int tgt_gelu_colsum_parts(void);
 int tgt_gelu_dropout_bwd_colsum(const void* x, const void* dy, void* dx, int64_t n, int32_t dtype, float p, uint64_t seed,
                                 const float* sample_scale, int64_t elems_per_sample, int32_t cols, float* partial, float* colsum,
                                 void* stream);
+
+/* (ABI 31) Fused gated activation + dropout: the middle of an FFN block whose activation is geglu / glu / swiglu (reference
+ * lib/tgt/layers/activations.py:4-17, then the nn.Dropout of lib/tgt/layers/layers.py:158).  x (rows, 2 cols) = [g | e],
+ *   y (rows, cols) = keep(i) ? e * act(g) / (1-p) * sample_scale[i / elems_per_sample] : 0        i over the (rows, cols) output
+ *   dx (rows, 2 cols) = [d_g | d_e]:  d_e = dy * act(g) * k,  d_g = dy * e * act'(g) * k,  k = keep(i) / (1-p) * sample_scale[..]
+ * with the generator of tgt_gelu_dropout_fwd on the OUTPUT index space (the seed counter mixed in): no mask is stored, the
+ * backward recomputes it.  kind: TGT_GLU_*.  cols: a multiple of 16 / sizeof(element); tensors contiguous and 16-byte aligned;
+ * fewer than 2^32 output vectors.  sample_scale (optional, float32 per sample): elems_per_sample counts OUTPUT elements and
+ * is a whole number of rows. */
+int tgt_glu_dropout_fwd(const void* x, void* y, int64_t rows, int32_t cols, int32_t kind, int32_t dtype, float p, uint64_t seed,
+                        const float* sample_scale, int64_t elems_per_sample, void* stream);
+int tgt_glu_dropout_bwd(const void* x, const void* dy, void* dx, int64_t rows, int32_t cols, int32_t kind, int32_t dtype, float p,
+                        uint64_t seed, const float* sample_scale, int64_t elems_per_sample, void* stream);
 
 /* Column sums of a (rows, C) tensor into float32 (C): the bias gradient of a Linear layer
  * (the `grad_output.sum(0)` ATen reduction behind nn.Linear, e.g. reference

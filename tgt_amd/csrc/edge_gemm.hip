@@ -14,6 +14,7 @@
 //   EPI_GELU_BWD   (.) * gelu'(pre) * keep / (1-p)    (data gradient through lin_W2 and the activation)
 //   EPI_LN_BWD     LayerNorm backward of the result + the gradient arriving on the residual stream,
 //                  dgamma / dbeta / bias-gradient column sums as per-workgroup partials
+//   EPI_GLU   pre-activation [g | e] + dropout(e * act(g))   (lin_W1 of an FFN with geglu / glu / swiglu, 256 -> 512: edge_glu.hip)
 // so that the standalone LayerNorm / residual / GELU sweeps over the edge tensor disappear.
 //
 // Two kernels: the weight-resident SLICE kernel (narrow outputs, EPI_BIAS) and the ROW-PHASE kernel (N = 256, whole-row
@@ -981,6 +982,8 @@ __global__ void __launch_bounds__(1024, 4) edge_wide512_kernel(const tgt_edge_li
 
 bool edge_wgrad_eligible(const tgt_edge_linear_args& a);                       // edge_wgrad.hip
 int edge_wgrad_run(const tgt_edge_linear_args& a, int grid, hipStream_t st);
+bool edge_glu_eligible(const tgt_edge_linear_args& a);                         // edge_glu.hip (TGT_EPI_GLU: 256 -> 512 + gated activation)
+int edge_glu_run(const tgt_edge_linear_args& a, int grid, hipStream_t st);
 
 // test hook (tgt_edge_linear_set_grid_cap): at most this many persistent workgroups / row groups per launch, so that a small
 // problem walks several tiles per workgroup -- the stage hand-over the BASELINE-size launches (32 tiles each) depend on
@@ -1143,6 +1146,7 @@ int edge_linear_supported(const tgt_edge_linear_args* a) {
     if (!a) return 0;
     if (a->dtype != TGT_BF16 && a->dtype != TGT_F16) return 0;
     const int K = a->K, N = a->N;
+    if (a->epilogue == EPI_GLU) return edge_glu_eligible(*a) ? 1 : 0;              // lin_W1 + geglu / glu / swiglu (K = 256, N = 512)
     if (K == 512) return (N == 256 && a->epilogue == EPI_RESID && (!a->gamma || (a->beta && a->y))) ? 1 : 0;      // lin_O + residual [+ LayerNorm]
     if ((K != 64 && K != 128 && K != 256) || N < 8 || N % 8) return 0;
     if (a->gamma && a->epilogue != EPI_RESID && a->epilogue != EPI_LN_BWD) return 0;          // (no LayerNorm prologue)
@@ -1160,7 +1164,7 @@ int edge_linear_run(const tgt_edge_linear_args* a, hipStream_t st) {
     if (a->M < 0 || a->K <= 0 || a->N <= 0) return set_error(TGT_ERR_INVALID, "edge linear: bad sizes");
     if (!edge_linear_supported(a))
         return set_error(TGT_ERR_UNSUPPORTED, "edge linear: unsupported shape/dtype (K=%d N=%d dtype=%d epilogue=%d): needs a 16-bit "
-                         "dtype, N %% 8 == 0, K in {64,128,256} (K = 512: residual epilogue, N = 256); row-wise epilogues N <= 256",
+                         "dtype, N %% 8 == 0, K in {64,128,256} (K = 512: residual epilogue, N = 256); row-wise epilogues N <= 256; TGT_EPI_GLU K = 256, N = 512",
                          a->K, a->N, a->dtype, a->epilogue);
     if (a->M == 0) return TGT_OK;
     const uintptr_t al = (uintptr_t)a->a | (uintptr_t)a->w | (uintptr_t)a->out | (uintptr_t)a->out2 | (uintptr_t)a->res |
@@ -1168,7 +1172,7 @@ int edge_linear_run(const tgt_edge_linear_args* a, hipStream_t st) {
     if (al % 16 || (a->lda * 2) % 16 || (a->ldw * 2) % 16 || (a->ldo * 2) % 16 || (a->ldo2 * 2) % 16 || (a->ldr * 2) % 16 ||
         (a->ldy * 2) % 16 || (a->ld_ds * 2) % 16)
         return set_error(TGT_ERR_INVALID, "edge linear: tensors and row strides must be 16-byte aligned");
-    if ((a->epilogue == EPI_GELU && !a->out2) || ((a->epilogue == EPI_RESID || a->epilogue == EPI_GELU_BWD) && !a->res))
+    if (((a->epilogue == EPI_GELU || a->epilogue == EPI_GLU) && !a->out2) || ((a->epilogue == EPI_RESID || a->epilogue == EPI_GELU_BWD) && !a->res))
         return set_error(TGT_ERR_INVALID, "edge linear: epilogue operand missing");
     if ((a->epilogue == EPI_GELU_BWD || a->epilogue == EPI_LN_BWD) && a->bias)
         return set_error(TGT_ERR_INVALID, "edge linear: the backward epilogues are data-gradient GEMMs, they take no bias");
@@ -1186,6 +1190,7 @@ int edge_linear_run(const tgt_edge_linear_args* a, hipStream_t st) {
         if (((uintptr_t)a->dw_partial) % 16) return set_error(TGT_ERR_INVALID, "edge linear: dw_partial must be 16-byte aligned");
         return edge_wgrad_run(*a, er_grid(*a), st);
     }
+    if (a->epilogue == EPI_GLU) return edge_glu_run(*a, er_grid(*a), st);
     if (a->K == 512) return a->dtype == TGT_BF16 ? er512_launch<bf16_t>(*a, st) : er512_launch<f16_t>(*a, st);
     if (ew512_eligible(*a)) return a->dtype == TGT_BF16 ? ew512_launch<bf16_t>(*a, st) : ew512_launch<f16_t>(*a, st);
     if (er_eligible(*a)) return a->dtype == TGT_BF16 ? er_run<bf16_t>(*a, st) : er_run<f16_t>(*a, st);

@@ -1145,6 +1145,77 @@ def gelu_dropout(x, p, training, sample_scale=None):
     return _GeluDropout.apply(x, p, seed, sample_scale)
 
 
+GLU_KINDS = _lib.GLU_KINDS        # 'geglu' / 'glu' / 'swiglu' -> TGT_GLU_*
+
+
+def _glu_kind(kind):
+    if isinstance(kind, str):
+        if kind not in GLU_KINDS:
+            raise RuntimeError(f'glu_dropout: unknown gated activation {kind!r} (one of {sorted(GLU_KINDS)})')
+        return GLU_KINDS[kind]
+    return int(kind)
+
+
+def _glu_backward(pre, d_act, kind, p, seed, sample_scale, eps_):
+    """[d_g | d_e] of y = dropout(e * act(g), p) * sample_scale for pre = [g | e]: one streaming pass, the drop pattern recomputed"""
+    cols = pre.shape[-1] // 2
+    d_act = d_act.contiguous()
+    if d_act.dtype != pre.dtype:
+        d_act = d_act.to(pre.dtype)
+    d_pre = torch.empty_like(pre)
+    s, e = _prof_begin('tgt_glu_dropout_bwd')
+    _lib.check(_lib.lib().tgt_glu_dropout_bwd(_ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel() // (2 * cols), cols, kind, _DT[pre.dtype],
+                                              p, seed, _ptr(sample_scale), eps_, _stream()), 'tgt_glu_dropout_bwd')
+    _prof_end('tgt_glu_dropout_bwd', s, e)
+    return d_pre
+
+
+class _GluDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kind, p, seed, sample_scale):
+        _dev(x, sample_scale)
+        x = x.contiguous()
+        cols = x.shape[-1] // 2
+        y = torch.empty(*x.shape[:-1], cols, dtype=x.dtype, device=x.device)
+        eps_ = y.numel() // sample_scale.numel() if sample_scale is not None else 0
+        s, e = _prof_begin('tgt_glu_dropout_fwd')
+        _lib.check(_lib.lib().tgt_glu_dropout_fwd(_ptr(x), _ptr(y), y.numel() // cols, cols, kind, _DT[x.dtype], float(p), seed,
+                                                  _ptr(sample_scale), eps_, _stream()), 'tgt_glu_dropout_fwd')
+        _prof_end('tgt_glu_dropout_fwd', s, e)
+        ctx.save_for_backward(x, sample_scale)
+        ctx.meta = (kind, float(p), seed, eps_)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, sample_scale = ctx.saved_tensors
+        return _glu_backward(x, dy, *ctx.meta[:3], sample_scale, ctx.meta[3]), None, None, None, None
+
+
+def _glu_check(x_last, out_elems, dtype, sample_scale, what):
+    if dtype not in _DT:
+        raise RuntimeError(f'{what}: no kernel for dtype {dtype} (float32 / bfloat16 / float16)')
+    if x_last % 2:
+        raise RuntimeError(f'{what}: the last axis holds [gate | linear] halves, got {x_last} channels')
+    if sample_scale is not None:
+        cols = x_last // 2
+        if sample_scale.dtype != torch.float32 or out_elems % sample_scale.numel() or (out_elems // sample_scale.numel()) % cols:
+            raise RuntimeError(f'{what}: sample_scale must be float32 with a whole number of rows per sample')
+
+
+def glu_dropout(x, kind, p, training, sample_scale=None):
+    """dropout(e * act(g), p) for x = [g | e] along the last axis, in one pass each way: kind 'geglu' (act = gelu, erf form), 'glu'
+    (sigmoid) or 'swiglu' (g * sigmoid(g)) -- reference lib/tgt/layers/activations.py:4-17 and the nn.Dropout of
+    lib/tgt/layers/layers.py:158.  Only x is kept for the backward; the drop pattern comes from a per-call seed (no mask tensor).
+    sample_scale (B,) float32: the result is multiplied by sample_scale[b] (the branch's DropPath factor, see gelu_dropout)."""
+    kind = _glu_kind(kind)
+    p = float(p) if training else 0.0
+    seed = _host_seed() if p > 0 else 0
+    _dev(x, sample_scale)
+    _glu_check(x.shape[-1], x.numel() // 2, x.dtype, sample_scale, 'glu_dropout')
+    return _GluDropout.apply(x, kind, p, seed, sample_scale)
+
+
 class _MultiHotEmbed(torch.autograd.Function):
     """sum_f W[idx[..., f]]  as  counts(idx) @ W: both directions are small GEMMs
     instead of a gather and a sort-based scatter (the ATen embedding backward spends
@@ -2005,6 +2076,64 @@ def linear_gelu_dropout(x, weight, bias, p, training, sample_scale=None):
     # rides on the tensor object (as _tgt_colsum does): what a consumer needs to take over the activation's backward
     act._tgt_gelu = (pre, p, seed, sample_scale)
     return act
+
+
+class _LinearGluDropout(torch.autograd.Function):
+    """act = dropout(e * act(g), p) * sample_scale[b] with [g | e] = x W^T + b as ONE launch (tgt_edge_linear, TGT_EPI_GLU: the
+    256 -> 512 weight-resident kernel with the activation in its store phase; reference FFN, lib/tgt/layers/layers.py:155-158 with
+    a GLU activation).  The pre-activation is written once for the backward, which is tgt_glu_dropout_bwd on it followed by the
+    Linear's (bias gradient: the column sums of d_pre)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, cd, kind, p, seed, sample_scale):
+        _dev(x, weight, sample_scale)
+        xs = x.shape
+        x2 = x.reshape(-1, xs[-1])
+        if x2.dtype != cd:
+            x2 = x2.to(cd)
+        w = _as_dtype(weight, cd)
+        b = None if bias is None else _as_dtype(bias, cd)
+        N2 = weight.shape[0]
+        pre = torch.empty(*xs[:-1], N2, dtype=cd, device=x.device)
+        act = torch.empty(*xs[:-1], N2 // 2, dtype=cd, device=x.device)
+        rps = (x2.shape[0] // sample_scale.numel()) if sample_scale is not None else 0
+        edge_linear_raw(x2, w, b, _lib.EPI_GLU, out=act.view(-1, N2 // 2), out2=pre.view(-1, N2), dropout=(p, seed),
+                        row_scale=sample_scale, rows_per_sample=rps, flags=kind << _lib.EDGE_GLU_KIND_SHIFT)
+        ctx.save_for_backward(x2, w, pre, sample_scale)
+        ctx.meta = (xs, x.dtype, weight.dtype, None if bias is None else bias.dtype, kind, float(p), seed, rps * (N2 // 2))
+        ctx.wptr = weight.data_ptr()
+        return act
+
+    @staticmethod
+    def backward(ctx, d_act):
+        x2, w, pre, sample_scale = ctx.saved_tensors
+        xs, xdt, wdt, bdt, kind, p, seed, eps_ = ctx.meta
+        d_pre = _glu_backward(pre, d_act, kind, p, seed, sample_scale, eps_)
+        dx, dw, db = _linear_backward(x2, w, d_pre.view(-1, d_pre.shape[-1]), xs, xdt, wdt, bdt, ctx.needs_input_grad[0],
+                                      ctx.needs_input_grad[1], bdt is not None and ctx.needs_input_grad[2], dw_ptr=ctx.wptr)
+        return dx, dw, db, None, None, None, None, None
+
+
+def linear_glu_dropout_ok(x, weight, sample_scale=None):
+    """whether linear_glu_dropout takes this call: edge rows (many of them), a 16-bit compute dtype, a (512, 256) weight"""
+    if not x.is_cuda:
+        return False
+    cd = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else x.dtype
+    rows = x.numel() // x.shape[-1]
+    if sample_scale is not None and (rows % sample_scale.numel() or sample_scale.dtype != torch.float32):
+        return False
+    return tuple(weight.shape) == (512, 256) and _edge_kernel_ok(x.reshape(-1, x.shape[-1]), 512, cd, ks=(256,)) and \
+        edge_linear_supported(256, 512, cd, _lib.EPI_GLU, row_scale=sample_scale is not None)
+
+
+def linear_glu_dropout(x, weight, bias, kind, p, training, sample_scale=None):
+    """dropout(e * act(g), p) [* sample_scale per graph] with [g | e] = linear(x, weight, bias) in one launch; kind as in
+    glu_dropout; see linear_glu_dropout_ok"""
+    kind = _glu_kind(kind)
+    cd = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else x.dtype
+    p = float(p) if training else 0.0
+    seed = _host_seed() if p > 0 else 0
+    return _LinearGluDropout.apply(x, weight, bias, cd, kind, p, seed, sample_scale)
 
 
 # ---------------------------------------------------------------------------

@@ -193,6 +193,13 @@ class FFN(nn.Module):
         the next LayerNorm).  sample_scale (B,): the result times that per-graph factor (the branch's DropPath, folded in)"""
         if self.activation == 'gelu' and ops.linear_gelu_dropout_ok(x, self.lin_W1.weight, sample_scale):
             return ops.linear_gelu_dropout(x, self.lin_W1.weight, self.lin_W1.bias, self.act_dropout, self.training, sample_scale)
+        if self.activation in ops.GLU_KINDS:
+            # gated activations: lin_W1 + activation + dropout as one launch on the edge rows (256 -> 512, 16-bit); any other
+            # width, the node channel and fp32 take the library GEMM and one streaming pass each way
+            if ops.linear_glu_dropout_ok(x, self.lin_W1.weight, sample_scale):
+                return ops.linear_glu_dropout(x, self.lin_W1.weight, self.lin_W1.bias, self.activation, self.act_dropout,
+                                              self.training, sample_scale)
+            return ops.glu_dropout(self.lin_W1(x), self.activation, self.act_dropout, self.training, sample_scale)
         x = self.lin_W1(x)
         if self.activation == 'gelu' and x.dtype in (torch.float32, torch.bfloat16, torch.float16):
             return ops.gelu_dropout(x, self.act_dropout, self.training, sample_scale)      # one pass each way, no mask tensor
@@ -200,7 +207,7 @@ class FFN(nn.Module):
         return x if sample_scale is None else x * sample_scale.view([-1] + [1] * (x.ndim - 1)).to(x.dtype)
 
     def can_fold_scale(self):
-        return self.activation == 'gelu'
+        return self.activation == 'gelu' or self.activation in ops.GLU_KINDS
 
 
 class DropPath(nn.Module):
