@@ -67,7 +67,9 @@ int tgt_abi_version(void);
  * Backward adds: d_out (same layout as out), and writes d_qkv[dir]
  * (same layout as qkv[dir]: every Q,K,V element is written), d_eg[dir]
  * (E and G columns written; same layout as eg[dir]).
- * Supported: N <= 64, D in {8,16,32}, any H.
+ * Supported: N <= 64 with D in {8,16,32}, and 65 <= N <= 128 with D = 16 (key-blocked kernels with an online softmax,
+ * csrc/triplet_attention_kb.hip; the backward needs the caller's `workspace`, and d_qkv_colsum / d_eg_colsum are not
+ * produced there: TGT_ERR_UNSUPPORTED when set); any H.
  * ---------------------------------------------------------------------- */
 typedef struct tgt_triplet_attention_args {
     int32_t B, N, H, D;
@@ -91,7 +93,8 @@ typedef struct tgt_triplet_attention_args {
     float*  d_eg_colsum[2];
     /* attention dropout on the gated weights (reference triplet.py:223-225, :242-244); 0 = off.
      * Counter-based: the backward must be called with the forward's (p, seed).  Generator:
-     * csrc/triplet_common.hpp (tri_drop_bits), unit = ((b*2 + dir)*H + h)*N + j. */
+     * csrc/triplet_common.hpp (tri_drop_bits), unit = ((b*2 + dir)*H + h)*N + j; the hash word of element (i, k) inside a
+     * unit is (i*64 + k) >> 1 for N <= 64 and (i*128 + k) >> 1 for N > 64 (no two pairs of a unit share a 16-bit field). */
     float    dropout_p;
     uint32_t _pad1;
     uint64_t dropout_seed;
@@ -108,8 +111,16 @@ typedef struct tgt_triplet_attention_args {
      * rows and column sums -- equal (up to the sign of a zero) to the full computation followed by the multiplication.  The factor itself
      * is NOT applied here.  NULL = every graph is computed. */
     const float* graph_scale;
+    /* ABI 32: scratch of the backward for N > 64 (softmax statistics between its two sweeps): DEVICE memory, 16-byte aligned, at
+     * least tgt_triplet_attention_workspace_bytes(a, 1) bytes, owned by the caller and free again when the call's work on
+     * `stream` is done.  Ignored (may be NULL / 0) where that function returns 0.  Too small: TGT_ERR_INVALID before any launch. */
+    void*   workspace;
+    int64_t workspace_bytes;
 } tgt_triplet_attention_args;
 
+/* Host only; reads B, N, H, D, dtype, flags.  Bytes of `workspace` the forward (bwd = 0) / backward (bwd != 0) of this shape
+ * needs: 0 for N <= 64 and for every forward, a multiple of 16 otherwise; negative for a shape the kernels do not take. */
+int64_t tgt_triplet_attention_workspace_bytes(const tgt_triplet_attention_args* a, int32_t bwd);
 int tgt_triplet_attention_fwd(const tgt_triplet_attention_args* a, void* stream);
 int tgt_triplet_attention_bwd(const tgt_triplet_attention_args* a, void* stream);
 

@@ -19,8 +19,10 @@ CSRC = os.path.join(_HERE, 'csrc')
 # (source, extra flags, object suffix): the triplet attention kernels compile one dtype per translation unit
 SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_wgrad.hip', 'params.hip', 'loss.hip', 'predict.hip', 'gaussian.hip', 'triplet_attention_proj.hip',
            ('triplet_attention.hip', ['-DTGT_TRI_INST=9'], '.f32'), ('triplet_attention.hip', ['-DTGT_TRI_INST=2'], '.bf16'),
-           ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip', 'triplet_attention_bwd2.hip', 'triplet_aggregate.hip', 'node_attention.hip', 'node_attention_mfma.hip', 'node_attention16.hip', 'node_attention_kb.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip']
-ABI_VERSION = 31
+           ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip', 'triplet_attention_bwd2.hip',
+           ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=9'], '.f32'), ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=2'], '.bf16'),
+           ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=4'], '.f16'), 'triplet_aggregate.hip', 'node_attention.hip', 'node_attention_mfma.hip', 'node_attention16.hip', 'node_attention_kb.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip']
+ABI_VERSION = 32
 
 TGT_F32, TGT_BF16, TGT_F16 = 0, 1, 2
 TRI_BIASED, TRI_GATED, TRI_MASK_OUT = 1, 2, 4
@@ -41,6 +43,7 @@ class TripletAttentionArgs(C.Structure):
         ('dropout_p', _f32), ('_pad1', C.c_uint32), ('dropout_seed', C.c_uint64),
         ('ld_dqkv', _i64 * 2), ('ld_deg', _i64 * 2),
         ('graph_scale', _vp),
+        ('workspace', _vp), ('workspace_bytes', _i64),
     ]
 
 
@@ -109,6 +112,7 @@ SYMBOLS = {
     'tgt_abi_version': (C.c_int, []),
     'tgt_triplet_attention_fwd': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp]),
     'tgt_triplet_attention_bwd': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp]),
+    'tgt_triplet_attention_workspace_bytes': (_i64, [C.POINTER(TripletAttentionArgs), _i32]),
     'tgt_triplet_attention_proj_supported': (C.c_int, [C.POINTER(TripletAttentionArgs), _i32]),
     'tgt_triplet_attention_proj_fwd': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _i32, _vp, _vp, _vp]),
     'tgt_triplet_aggregate_fwd': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp]),

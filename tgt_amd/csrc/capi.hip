@@ -23,6 +23,7 @@ int check_launch(const char* what) {
 }
 
 int triplet_attention_run(const tgt_triplet_attention_args* a, bool bwd, hipStream_t st);
+int64_t tri_att_kb_workspace_bytes(const tgt_triplet_attention_args* a, int bwd);
 int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, bool bwd, hipStream_t st);
 int node_attention_run(const tgt_node_attention_args* a, bool bwd, hipStream_t st);
 int layer_norm_parts();
@@ -90,7 +91,7 @@ using namespace tgt;
 extern "C" {
 
 const char* tgt_last_error(void) { return g_err; }
-int tgt_abi_version(void) { return 31; }
+int tgt_abi_version(void) { return 32; }
 int tgt_set_seed_counter(const void* device_counter) {
     g_seed_counter = reinterpret_cast<const uint64_t*>(device_counter);
     return TGT_OK;
@@ -102,6 +103,7 @@ int tgt_triplet_attention_fwd(const tgt_triplet_attention_args* a, void* stream)
 int tgt_triplet_attention_bwd(const tgt_triplet_attention_args* a, void* stream) {
     return triplet_attention_run(a, true, reinterpret_cast<hipStream_t>(stream));
 }
+int64_t tgt_triplet_attention_workspace_bytes(const tgt_triplet_attention_args* a, int32_t bwd) { return tri_att_kb_workspace_bytes(a, bwd); }
 int tgt_triplet_aggregate_fwd(const tgt_triplet_aggregate_args* a, void* stream) {
     return triplet_aggregate_run(a, false, reinterpret_cast<hipStream_t>(stream));
 }

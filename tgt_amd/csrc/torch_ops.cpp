@@ -148,6 +148,13 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> triplet_attention_bwd(const Tensor& q
     a.d_out = d_out.data_ptr();
     a.out = d_out.data_ptr();          // (checked non-null; the backward does not touch it)
     a.d_qkv[0] = dqi.data_ptr(); a.d_qkv[1] = dqo.data_ptr(); a.d_eg[0] = dei.data_ptr(); a.d_eg[1] = deo.data_ptr();
+    // N > 64: the backward's scratch comes from the caching allocator for this call (a negative size: the entry point says why)
+    const int64_t ws_bytes = tgt_triplet_attention_workspace_bytes(&a, 1);
+    Tensor ws;
+    if (ws_bytes > 0) {
+        ws = at::empty({ws_bytes}, qi.options().dtype(at::kByte));
+        a.workspace = ws.data_ptr(); a.workspace_bytes = ws_bytes;
+    }
     ok(tgt_triplet_attention_bwd(&a, stream_of(qi)), "tgt_triplet_attention_bwd");
     return {dqi, dei, dqo, deo};
 }

@@ -740,13 +740,14 @@ bool tri_att16_bwd_eligible(const tgt_triplet_attention_args& a);
 int tri_att16_bwd_run(const tgt_triplet_attention_args& a, hipStream_t st);
 bool tri_att_bwd2_eligible(const tgt_triplet_attention_args& a);       // triplet_attention_bwd2.hip: 16-bit, D = 16, N <= 32, H % 8 == 0
 int tri_att_bwd2_run(const tgt_triplet_attention_args& a, hipStream_t st);
+int tri_att_kb_run(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st);      // triplet_attention_kb.hip: 65 <= N <= 128, D = 16
 
 int triplet_attention_run(const tgt_triplet_attention_args* a, bool bwd, hipStream_t st) {
     if (!a) return set_error(TGT_ERR_INVALID, "triplet attention: null args");
 
     if (a->B < 0 || a->N < 0 || a->H <= 0) return set_error(TGT_ERR_INVALID, "triplet attention: bad sizes B=%d N=%d H=%d", a->B, a->N, a->H);
     if (a->B == 0 || a->N == 0) return TGT_OK;                 // empty batch: nothing to do
-    if (a->N > 64) return set_error(TGT_ERR_UNSUPPORTED, "triplet attention: N=%d > 64 not supported", a->N);
+    if (a->N > 128) return set_error(TGT_ERR_UNSUPPORTED, "triplet attention: N=%d > 128 not supported", a->N);
     if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return set_error(TGT_ERR_INVALID, "triplet attention: dropout_p=%f outside [0,1)", a->dropout_p);
     const int64_t esz = a->dtype == TGT_F32 ? 4 : 2;
     for (int dir = 0; dir < 2; ++dir) {
@@ -767,6 +768,7 @@ int triplet_attention_run(const tgt_triplet_attention_args* a, bool bwd, hipStre
             if ((a->flags & (TGT_TRI_BIASED | TGT_TRI_GATED)) && !a->d_eg[dir]) return set_error(TGT_ERR_INVALID, "triplet attention bwd: d_eg missing");
         }
     }
+    if (a->N > 64) return tri_att_kb_run(*a, bwd, st);                             // key-blocked kernels; checks D and the workspace before any launch
     if (!bwd && tri_att16_fwd_eligible(*a)) return tri_att16_fwd_run(*a, st);      // 33 <= N <= 64: 16-wide tiles (triplet_attention16.hip)
     if (bwd && tri_att16_bwd_eligible(*a)) return tri_att16_bwd_run(*a, st);
     if (bwd && tri_att_bwd2_eligible(*a)) return tri_att_bwd2_run(*a, st);

@@ -432,6 +432,8 @@ __device__ __forceinline__ float arm_stage_store_grad(const ThirdArm& ta, void* 
 //   word = mix32( mix32(seed_lo ^ mix32(unit)) + seed_hi + ((i*64 + k) >> 1) * 0x9e3779b9 )
 //   keep(k even) = (word & 0xffff) >= thresh16,  keep(k odd) = (word >> 16) >= thresh16,
 //   thresh16 = clamp(round(p * 65536), 1, 65535); kept weights are scaled by 1/(1-p).
+// Word stride of a row: 64 for N <= 64 (as above).  With k >= 64 that index would alias (i, k) with (i+1, k-64), so the
+// kernels for N > 64 (triplet_attention_kb.hip) use ((i*128 + k) >> 1): `stride` below.  Patterns for N <= 64 are unchanged.
 // (tests/golden_util.py::triplet_dropout_keep restates it in numpy for the parity tests.)
 // Returns the keep bits of the 16 accumulator elements of one lane: bit q <-> k = 32*kt + acc_row(q,hi).
 // ---------------------------------------------------------------------------
@@ -451,13 +453,13 @@ __device__ __forceinline__ TriDrop tri_drop(float p, uint64_t seed) {
     d.scale = d.on ? 1.f / (1.f - p) : 1.f;
     return d;
 }
-__device__ __forceinline__ uint32_t tri_drop_bits(const TriDrop& d, uint32_t unit, int i, int kt, int hi) {
+__device__ __forceinline__ uint32_t tri_drop_bits(const TriDrop& d, uint32_t unit, int i, int kt, int hi, int stride = 64) {
     const uint32_t base = mix32(d.seed_lo ^ mix32(unit)) + d.seed_hi;
     uint32_t bits = 0;
 #pragma unroll
     for (int w = 0; w < 8; ++w) {
         const int k = 32 * kt + acc_row(2 * w, hi);
-        const uint32_t r = mix32(base + (uint32_t)((i * 64 + k) >> 1) * 0x9e3779b9u);
+        const uint32_t r = mix32(base + (uint32_t)((i * stride + k) >> 1) * 0x9e3779b9u);
         bits |= ((r & 0xffffu) >= d.thresh16 ? 1u : 0u) << (2 * w);
         bits |= ((r >> 16) >= d.thresh16 ? 1u : 0u) << (2 * w + 1);
     }

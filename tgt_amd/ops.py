@@ -184,6 +184,13 @@ def _tri_args(fused, mask3, out, L, d_out=None, d_fused=None, colsum=None, dropo
             a.d_qkv_colsum = _pair(C.c_void_p, cp, cp)
             if L.biased:
                 a.d_eg_colsum = _pair(C.c_void_p, cp + eo * 4, cp + eo * 4)
+    # N > 64: the key-blocked backward keeps its softmax statistics in a caller-owned workspace.  A fresh block from the caching
+    # allocator per call, as _colsum_workspace: it is kept alive on the argument block until the launches are enqueued and reused
+    # in stream order afterwards.  (A negative size = a shape the kernels refuse: the entry point says why.)
+    need = _lib.lib().tgt_triplet_attention_workspace_bytes(C.byref(a), 0 if d_out is None else 1) if N > 64 else 0
+    if need > 0:
+        a._workspace = torch.empty(need, dtype=torch.uint8, device=fused.device)
+        a.workspace, a.workspace_bytes = a._workspace.data_ptr(), need
     return a
 
 
@@ -551,12 +558,17 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         eg = None
         proj_skip = None
         if x.numel() // L.C >= _SPLIT_MIN_ROWS and not (dropout[0] == 0 and _proj_fused_ok(x, N, L, cd)) and _TRI_PROJ:
-            why = ('N > 32' if N > 32 else 'attention dropout > 0' if dropout[0] else 'head dim != 16' if L.D != 16 else
+            why = ('N > 64' if N > 64 else 'N > 32' if N > 32 else 'attention dropout > 0' if dropout[0] else 'head dim != 16' if L.D != 16 else
                    'heads not a multiple of 8' if L.H % 8 else 'edge width != 256' if L.C != 256 else
                    'fp32' if cd not in (torch.bfloat16, torch.float16) else 'padded / unbiased layout')
-            _slow_path_notice(('tri_proj', why), f'triplet attention: the projection-fused forward / round-4 backward do not take this shape ({why}); '
-                              'running the projection as library GEMMs + the general attention kernels (N in 33..64: 16-wide tiles at 0.39-0.45 of '
-                              'HBM instead of 0.52; see DESIGN.md section 4)')
+            if N > 64:
+                _slow_path_notice(('tri_proj', why), 'triplet attention: the projection-fused forward / round-4 backward do not take this shape (N > 64); '
+                                  'running the projection as library GEMMs + the key-blocked attention kernels (65 <= N <= 128, D = 16: online softmax '
+                                  'forward, two-sweep backward, bias gradient by a separate column-sum pass; see DESIGN.md section 4)')
+            else:
+                _slow_path_notice(('tri_proj', why), f'triplet attention: the projection-fused forward / round-4 backward do not take this shape ({why}); '
+                                  'running the projection as library GEMMs + the general attention kernels (N in 33..64: 16-wide tiles at 0.39-0.45 of '
+                                  'HBM instead of 0.52; see DESIGN.md section 4)')
         if dropout[0] == 0 and _proj_fused_ok(x, N, L, cd):
             # Q/K/V projected inside the attention kernel (it still writes them once, for the
             # backward); only the narrow E/G third-arm projection stays a library GEMM, written
@@ -618,14 +630,18 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         d_fused = torch.empty(*fused.shape[:3], L.width, dtype=fused.dtype, device=fused.device)   # every used column is written
         if L.width > L.used:
             d_fused[..., L.used:] = 0
-        colsum = _colsum_workspace(fused.shape[0], L.width, L.used, fused.device)
+        # (N > 64: the key-blocked kernels produce no column sums; the bias gradient is a column-sum pass over d_fused)
+        kb = fused.shape[1] > 64
+        colsum = None if kb else _colsum_workspace(fused.shape[0], L.width, L.used, fused.device)
         a = _tri_args(fused, mask3, out, L, d_out, d_fused, colsum, dropout=ctx.dropout, eg=eg, graph_scale=ctx.graph_scale)
         _call('tgt_triplet_attention_bwd', _lib.lib().tgt_triplet_attention_bwd, a)
         if _GATE_NODE_BWD == 1:
             _gate_record(d_fused.device)
         need_p = any(ctx.needs_input_grad[7:])
         d2 = d_fused.view(-1, L.width)
-        if eg is not None and need_p:
+        if kb:
+            db = column_sum(d2) if need_p else None
+        elif eg is not None and need_p:
             ws0 = _terminal_fork(d2.shape[0], colsum)
             with _on_stream(ws0):
                 db = sum_rows(colsum)
