@@ -134,6 +134,9 @@ int tgt_triplet_attention_bwd(const tgt_triplet_attention_args* a, void* stream)
  *            O[i,j,h,:] = sum_k A[k,i,h] V_out[k,j,h,:]
  * v[dir] : (B,N,N,ld_v[dir]) rows, V of head h at v_off[dir] + h*D.
  * eg / mask / out as above.  No saved statistics (weights are recomputed).
+ * Supported: N <= 64 with D in {8,16,32}, and 65 <= N <= 128 with D = 16 (csrc/triplet_aggregate_kb.hip: no workspace; the
+ * backward is two launches, dE / dG then dV, every sum in a fixed order).  The entry points check, before any launch: sizes
+ * (TGT_ERR_INVALID), N > 128 and then D != 16 at N > 64 (TGT_ERR_UNSUPPORTED), then null / misaligned tensors (TGT_ERR_INVALID).
  * ---------------------------------------------------------------------- */
 typedef struct tgt_triplet_aggregate_args {
     int32_t B, N, H, D;
@@ -147,7 +150,7 @@ typedef struct tgt_triplet_aggregate_args {
     void*   d_v[2];
     void*   d_eg[2];
     /* attention dropout on the gated weights (reference triplet.py:59-60, :66-67); 0 = off;
-     * unit = (b*2 + dir)*H + h, otherwise as tgt_triplet_attention_args. */
+     * unit = (b*2 + dir)*H + h, otherwise as tgt_triplet_attention_args: word (i*128 + k) >> 1 for N > 64. */
     float    dropout_p;
     uint32_t _pad1;
     uint64_t dropout_seed;

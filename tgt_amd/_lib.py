@@ -21,7 +21,9 @@ SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_w
            ('triplet_attention.hip', ['-DTGT_TRI_INST=9'], '.f32'), ('triplet_attention.hip', ['-DTGT_TRI_INST=2'], '.bf16'),
            ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip', 'triplet_attention_bwd2.hip',
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=9'], '.f32'), ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=2'], '.bf16'),
-           ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=4'], '.f16'), 'triplet_aggregate.hip', 'node_attention.hip', 'node_attention_mfma.hip', 'node_attention16.hip', 'node_attention_kb.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip']
+           ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=4'], '.f16'), 'triplet_aggregate.hip',
+           ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=9'], '.f32'), ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=2'], '.bf16'),
+           ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=4'], '.f16'), 'node_attention.hip', 'node_attention_mfma.hip', 'node_attention16.hip', 'node_attention_kb.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip']
 ABI_VERSION = 32
 
 TGT_F32, TGT_BF16, TGT_F16 = 0, 1, 2

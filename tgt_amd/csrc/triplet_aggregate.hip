@@ -336,11 +336,15 @@ static int agg_dispatch_d(const tgt_triplet_aggregate_args& a, bool bwd, hipStre
     }
 }
 
+int tri_agg_kb_run(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st);      // triplet_aggregate_kb.hip: 65 <= N <= 128, D = 16
+
 int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, bool bwd, hipStream_t st) {
     if (!a) return set_error(TGT_ERR_INVALID, "triplet aggregate: null args");
     if (a->B < 0 || a->N < 0 || a->H <= 0) return set_error(TGT_ERR_INVALID, "triplet aggregate: bad sizes");
     if (a->B == 0 || a->N == 0) return TGT_OK;
-    if (a->N > 64) return set_error(TGT_ERR_UNSUPPORTED, "triplet aggregate: N=%d > 64 not supported", a->N);
+    if (a->N > 128) return set_error(TGT_ERR_UNSUPPORTED, "triplet aggregate: N=%d > 128 not supported", a->N);
+    if (a->N > 64 && a->D != 16)
+        return set_error(TGT_ERR_UNSUPPORTED, "triplet aggregate: N=%d > 64 is supported for D = 16 only (D=%d)", a->N, a->D);
     const int64_t esz = a->dtype == TGT_F32 ? 4 : 2;
     for (int dir = 0; dir < 2; ++dir) {
         if (!a->v[dir] || !a->eg[dir] || !a->out || !a->mask) return set_error(TGT_ERR_INVALID, "triplet aggregate: null tensor");
@@ -350,6 +354,7 @@ int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, bool bwd, hipStre
         if (bwd && (!a->d_out || !a->d_v[dir] || !a->d_eg[dir] || ((uintptr_t)a->d_v[dir] % 16) || ((uintptr_t)a->d_out % 16)))
             return set_error(TGT_ERR_INVALID, "triplet aggregate bwd: null/misaligned gradient tensor");
     }
+    if (a->N > 64) return tri_agg_kb_run(*a, bwd, st);                             // key-blocked kernels
     switch (a->dtype) {
         case TGT_F32: return agg_dispatch_d<float>(*a, bwd, st);
         case TGT_BF16: return agg_dispatch_d<bf16_t>(*a, bwd, st);
