@@ -256,16 +256,29 @@ template <> struct DType<f16_t>  { static constexpr int id = TGT_F16; };
 int set_error(int code, const char* fmt, ...);
 int check_launch(const char* what);
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: remember it per (kernel instantiation, device).
-// `done` is a function-local `static bool attr_set[16] = {}` of the launcher of ONE kernel instantiation.
-static inline bool dyn_lds_once(bool (&done)[16], const void* fn, int lds) {
+constexpr int cmax(int x, int y) { return x > y ? x : y; }
+
+// Kernels with dynamic LDS.  More than 64 KB needs hipFuncSetAttribute(MaxDynamicSharedMemorySize), which is per device: it
+// is remembered per (kernel instantiation, device) -- `done` is a static of the template, so there is one array per KERNEL.
+// reserve_lds alone is for a launcher of several kernels that wants every reservation made before its first launch.
+template <auto KERNEL>
+static int reserve_lds(const char* name, int lds) {
+    static bool done[16] = {};
+    if (lds <= 64 * 1024) return TGT_OK;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
     if (dev >= 16 || !done[dev]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return false;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+            return set_error(TGT_ERR_LAUNCH, "%s: cannot reserve %d bytes of LDS", name, lds);
         if (dev < 16) done[dev] = true;
     }
-    return true;
+    return TGT_OK;
+}
+template <auto KERNEL, typename... Args>
+static int launch_lds(const char* name, dim3 grid, dim3 block, int lds, hipStream_t st, const Args&... args) {
+    if (int rc = reserve_lds<KERNEL>(name, lds)) return rc;
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, st, args...);
+    return check_launch(name);
 }
 
 }  // namespace tgt

@@ -1010,31 +1010,19 @@ static int er_launch(const tgt_edge_linear_args& a, hipStream_t st) {
     constexpr int K = KS * 16;
     constexpr int lds0 = 2 * 32 * K * 2 + 2 * 32 * 256 * 2 + 2 * 256 * 4;
     constexpr int lds = lds0 < 49152 ? 49152 : lds0;                        // the final column-sum fold of LN_BWD needs 48 KB
-    static bool attr_set[16] = {};
-    if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&edge_rows_kernel<T, KS, EPI>), lds))
-        return set_error(TGT_ERR_LAUNCH, "edge_rows_kernel: cannot reserve %d bytes of LDS", lds);
-    hipLaunchKernelGGL((edge_rows_kernel<T, KS, EPI>), dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a, seed_counter());
-    return check_launch("edge_rows_kernel");
+    return launch_lds<edge_rows_kernel<T, KS, EPI>>("edge_rows_kernel", dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a, seed_counter());
 }
 
 template <typename T>
 static int er512_launch(const tgt_edge_linear_args& a, hipStream_t st) {
     constexpr int lds = 2 * 32 * 512 * 2 + 2 * 32 * 256 * 4 + 3 * 256 * 4;
-    static bool attr_set[16] = {};
-    if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&edge_rows512_kernel<T>), lds))
-        return set_error(TGT_ERR_LAUNCH, "edge_rows512_kernel: cannot reserve %d bytes of LDS", lds);
-    hipLaunchKernelGGL((edge_rows512_kernel<T>), dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a);
-    return check_launch("edge_rows512_kernel");
+    return launch_lds<edge_rows512_kernel<T>>("edge_rows512_kernel", dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a);
 }
 
 template <typename T>
 static int ew512_launch(const tgt_edge_linear_args& a, hipStream_t st) {
     constexpr int lds = 2 * 32 * 256 * 2 + 32 * 512 * 2 + 512 * 4;
-    static bool attr_set[16] = {};
-    if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&edge_wide512_kernel<T>), lds))
-        return set_error(TGT_ERR_LAUNCH, "edge_wide512_kernel: cannot reserve %d bytes of LDS", lds);
-    hipLaunchKernelGGL((edge_wide512_kernel<T>), dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a);
-    return check_launch("edge_wide512_kernel");
+    return launch_lds<edge_wide512_kernel<T>>("edge_wide512_kernel", dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a);
 }
 // K = 256 -> N = 512 with the plain epilogue and nothing else attached
 static bool ew512_eligible(const tgt_edge_linear_args& a) {
@@ -1073,9 +1061,6 @@ template <typename T, int KS, int WN, int EPI, int RB>
 static int es_launch(const tgt_edge_linear_args& a, hipStream_t st) {
     constexpr int kBM = 32 * RB;
     constexpr int lds = 2 * kBM * KS * 32 + WN * kBM * 2 * 4;
-    static bool attr_set[16] = {};
-    if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&edge_slice_kernel<T, KS, WN, EPI, RB>), lds))
-        return set_error(TGT_ERR_LAUNCH, "edge_slice_kernel: cannot reserve %d bytes of LDS", lds);
     const int n_slices = (a.N + 32 * WN - 1) / (32 * WN);
     const int64_t row_tiles = (a.M + kBM - 1) / kBM;
     // one workgroup per CU; per XCD (blocks b % 8) a whole number of row groups x all their slices
@@ -1085,8 +1070,7 @@ static int es_launch(const tgt_edge_linear_args& a, hipStream_t st) {
     if (groups > row_tiles) groups = row_tiles;
     if (g_grid_cap && groups > g_grid_cap) groups = g_grid_cap;
     const int64_t blocks = ((groups + 7) / 8) * n_slices * 8;
-    hipLaunchKernelGGL((edge_slice_kernel<T, KS, WN, EPI, RB>), dim3((unsigned)blocks), dim3(512), lds, st, a, (int)groups, seed_counter());
-    return check_launch("edge_slice_kernel");
+    return launch_lds<edge_slice_kernel<T, KS, WN, EPI, RB>>("edge_slice_kernel", dim3((unsigned)blocks), dim3(512), lds, st, a, (int)groups, seed_counter());
 }
 
 template <typename T, int KS, int WN>

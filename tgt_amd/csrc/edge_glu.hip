@@ -115,11 +115,7 @@ __global__ void __launch_bounds__(1024, 4) edge_glu512_kernel(const tgt_edge_lin
 template <typename T, int KIND>
 static int eglu_launch(const tgt_edge_linear_args& a, int grid, hipStream_t st) {
     constexpr int lds = 2 * 32 * 256 * 2 + 32 * 512 * 2 + 512 * 4;
-    static bool attr_set[16] = {};
-    if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&edge_glu512_kernel<T, KIND>), lds))
-        return set_error(TGT_ERR_LAUNCH, "edge_glu512_kernel: cannot reserve %d bytes of LDS", lds);
-    hipLaunchKernelGGL((edge_glu512_kernel<T, KIND>), dim3((unsigned)grid), dim3(1024), lds, st, a, seed_counter());
-    return check_launch("edge_glu512_kernel");
+    return launch_lds<edge_glu512_kernel<T, KIND>>("edge_glu512_kernel", dim3((unsigned)grid), dim3(1024), lds, st, a, seed_counter());
 }
 
 template <typename T>

@@ -359,11 +359,7 @@ __global__ void __launch_bounds__(kThreads, 2) edge_rows_wgrad_kernel(const tgt_
 
 template <typename T, int EPI>
 static int launch(const tgt_edge_linear_args& a, int grid, hipStream_t st) {
-    static bool attr_set[16] = {};
-    if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&edge_rows_wgrad_kernel<T, EPI>), kLds))
-        return set_error(TGT_ERR_LAUNCH, "edge_rows_wgrad_kernel: cannot reserve %d bytes of LDS", kLds);
-    hipLaunchKernelGGL((edge_rows_wgrad_kernel<T, EPI>), dim3((unsigned)grid), dim3(kThreads), kLds, st, a, seed_counter());
-    return check_launch("edge_rows_wgrad_kernel");
+    return launch_lds<edge_rows_wgrad_kernel<T, EPI>>("edge_rows_wgrad_kernel", dim3((unsigned)grid), dim3(kThreads), kLds, st, a, seed_counter());
 }
 
 }  // namespace wg

@@ -559,20 +559,12 @@ static int launch(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
         constexpr int kLds = L::kFwdBytes;
         static_assert(kLds <= kLdsMax, "forward LDS");
         const int grid = ((a.B + 7) / 8) * 8 * groups * nqb;
-        static bool attr_set[16] = {};
-        if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&node_att16_fwd_kernel<T, NQ, D>), kLds))
-            return set_error(TGT_ERR_LAUNCH, "node_att16_fwd_kernel: cannot reserve %d bytes of LDS", kLds);
-        hipLaunchKernelGGL((node_att16_fwd_kernel<T, NQ, D>), dim3(grid), dim3(kThreads), kLds, st, a);
-        return check_launch("node_att16_fwd_kernel");
+        return launch_lds<node_att16_fwd_kernel<T, NQ, D>>("node_att16_fwd_kernel", dim3(grid), dim3(kThreads), kLds, st, a);
     } else {
         constexpr int kLds = L::kBwdBytes;
         static_assert(kLds <= kLdsMax, "backward LDS");
         const int grid = ((a.B + 7) / 8) * 8 * groups;
-        static bool attr_set[16] = {};
-        if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&node_att16_bwd_kernel<T, NQ, D>), kLds))
-            return set_error(TGT_ERR_LAUNCH, "node_att16_bwd_kernel: cannot reserve %d bytes of LDS", kLds);
-        hipLaunchKernelGGL((node_att16_bwd_kernel<T, NQ, D>), dim3(grid), dim3(kThreads), kLds, st, a);
-        return check_launch("node_att16_bwd_kernel");
+        return launch_lds<node_att16_bwd_kernel<T, NQ, D>>("node_att16_bwd_kernel", dim3(grid), dim3(kThreads), kLds, st, a);
     }
 }
 

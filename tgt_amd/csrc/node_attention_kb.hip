@@ -326,11 +326,7 @@ static int launch_fwd(const tgt_node_attention_args& a, hipStream_t st) {
     } else {
         const int nqb = (a.N + 15) / 16, chunks = a.H / L::HW;
         const int grid = ((a.B + 7) / 8) * 8 * chunks * nqb;
-        static bool attr_set[16] = {};
-        if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&node_att_kb_fwd_kernel<T, D, HPW>), kLds))
-            return set_error(TGT_ERR_LAUNCH, "node_att_kb_fwd_kernel: cannot reserve %d bytes of LDS", kLds);
-        hipLaunchKernelGGL((node_att_kb_fwd_kernel<T, D, HPW>), dim3(grid), dim3(kThreads), kLds, st, a);
-        return check_launch("node_att_kb_fwd_kernel");
+        return launch_lds<node_att_kb_fwd_kernel<T, D, HPW>>("node_att_kb_fwd_kernel", dim3(grid), dim3(kThreads), kLds, st, a);
     }
 }
 template <typename T>

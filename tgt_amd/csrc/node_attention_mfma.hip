@@ -597,20 +597,11 @@ static int launch(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
     if (!bwd) {
         constexpr int kLds = L::lds_bytes(D, false);
         static_assert(kLds <= kLdsMax, "forward LDS");
-        static bool attr_set[16] = {};                 // per device (common.hpp: dyn_lds_once)
-        if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&node_att_mfma_fwd_kernel<T, HG, D>), kLds))
-            return set_error(TGT_ERR_LAUNCH, "node_att_mfma_fwd_kernel: cannot reserve %d bytes of LDS", kLds);
-        hipLaunchKernelGGL((node_att_mfma_fwd_kernel<T, HG, D>), dim3(grid), dim3(HG * 64), kLds, st, a, ablate);
-        return check_launch("node_att_mfma_fwd_kernel");
+        return launch_lds<node_att_mfma_fwd_kernel<T, HG, D>>("node_att_mfma_fwd_kernel", dim3(grid), dim3(HG * 64), kLds, st, a, ablate);
     } else {
         constexpr int kLds = L::lds_bytes(D, true);
-        if constexpr (kLds <= kLdsMax) {
-            static bool attr_set[16] = {};                 // per device (common.hpp: dyn_lds_once)
-            if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&node_att_mfma_bwd_kernel<T, HG, D>), kLds))
-                return set_error(TGT_ERR_LAUNCH, "node_att_mfma_bwd_kernel: cannot reserve %d bytes of LDS", kLds);
-            hipLaunchKernelGGL((node_att_mfma_bwd_kernel<T, HG, D>), dim3(grid), dim3(HG * 64), kLds, st, a, ablate);
-            return check_launch("node_att_mfma_bwd_kernel");
-        }
+        if constexpr (kLds <= kLdsMax)
+            return launch_lds<node_att_mfma_bwd_kernel<T, HG, D>>("node_att_mfma_bwd_kernel", dim3(grid), dim3(HG * 64), kLds, st, a, ablate);
         return -1;
     }
 }

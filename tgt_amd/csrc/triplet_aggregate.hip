@@ -16,44 +16,6 @@
 
 namespace tgt {
 
-struct AggCtx {
-    int b, dir, g, h, N;
-    ThirdArm ta;
-};
-
-template <typename T, int D, int HG>
-__device__ __forceinline__ AggCtx agg_ctx(const tgt_triplet_aggregate_args& a, int wave) {
-    AggCtx c;
-    const int ngroups = a.H / HG;
-    int bid = blockIdx.x;
-    c.g = bid % ngroups;
-    bid /= ngroups;
-    c.dir = bid & 1;
-    c.b = bid >> 1;
-    c.h = c.g * HG + wave;
-    c.N = a.N;
-    const bool use_mask = c.dir == 0 || (a.flags & TGT_TRI_MASK_OUT);
-    c.ta = ThirdArm{a.eg[c.dir], a.ld_eg[c.dir], a.e_off[c.dir], a.g_off[c.dir], use_mask ? a.mask : nullptr,
-                    true, (a.flags & TGT_TRI_GATED) != 0};
-    return c;
-}
-
-// buffer-addressed slabs (triplet_common.hpp): rows k of V[j,k] (inward) / V[k,j] (outward) of this head group
-template <typename T, int D, int HG>
-__device__ __forceinline__ SlabBuf agg_v_slab(const void* tensor, int64_t ld, int off, const AggCtx& c) {
-    const int64_t sz = sizeof(T), N = c.N;
-    const uint32_t ldb = (uint32_t)(ld * sz);
-    return SlabBuf{graph_rsrc(tensor, N * N * ld * sz, c.b), (uint32_t)((off + c.g * HG * D) * sz),
-                   c.dir == 0 ? ldb : (uint32_t)N * ldb, c.dir == 0 ? (uint32_t)N * ldb : ldb};
-}
-// rows i of X[i,j] (the aggregate's output and its gradient)
-template <typename T, int D, int HG>
-__device__ __forceinline__ SlabBuf agg_o_slab(const void* tensor, int64_t ld, int off, const AggCtx& c) {
-    const int64_t sz = sizeof(T), N = c.N;
-    const uint32_t ldb = (uint32_t)(ld * sz);
-    return SlabBuf{graph_rsrc(tensor, N * N * ld * sz, c.b), (uint32_t)((off + c.g * HG * D) * sz), (uint32_t)N * ldb, ldb};
-}
-
 // weights of query tile it / key tile kt in (lane = i) layout: softmax over ALL key tiles
 // (the E/G/mask tiles come through the LDS stage: two barriers inside, `lds` aliases the slabs)
 template <typename T, int HG, int NT, bool PAD>
@@ -65,27 +27,7 @@ __device__ __forceinline__ void agg_weights(const AggCtx& c, int N, int wave, in
     for (int kt = 0; kt < NT; ++kt)
         arm_stage_read<T, HG, NT, PAD>(c.ta, lds, c.dir, wave, N, r, hi, i0, kt, p[kt], gate[kt]);
     __syncthreads();
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) mx = fmaxf(mx, p[kt][q]);
-    mx = fmaxf(mx, xhalf(mx));
-    if (mx == -INFINITY) mx = 0.f;               // padding column: all weights exactly 0
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            p[kt][q] = fast_exp(p[kt][q] - mx);
-            sum += p[kt][q];
-        }
-    sum += xhalf(sum);
-    const float inv = sum > 0.f ? fast_rcp(sum) : 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) p[kt][q] *= inv;
+    tile_softmax<NT>(p);
 }
 
 template <typename T, int D, int HG, int NT>
@@ -99,7 +41,7 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_fwd_kernel(const tgt_triplet_
     constexpr int kSet = (NT + 1) * G::kSlabBytes;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hi = lane >> 5;
-    const AggCtx c = agg_ctx<T, D, HG>(a, wave);
+    const AggCtx c = agg_ctx<HG>(a, wave);
     const int N = c.N;
     F ident_d[G::kDC];
     make_ident_d<T, G::kDC>(ident_d, r, hi);
@@ -167,7 +109,7 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_bwd_kernel(const tgt_triplet_
     constexpr int kSet = (NT + 1) * G::kSlabBytes;        // {dO | V}, two sets (see forward)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hi = lane >> 5;
-    const AggCtx c = agg_ctx<T, D, HG>(a, wave);
+    const AggCtx c = agg_ctx<HG>(a, wave);
     const int N = c.N;
 
     F ident_d[G::kDC];

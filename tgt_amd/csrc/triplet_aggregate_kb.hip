@@ -13,170 +13,32 @@
 //              sums dV[j,k,:] = sum_i A[i,k] dO[i,j,:] over the four query tiles in the fp32 accumulator; dV is stored once,
 //              nothing is read back from HBM.
 // The softmax runs over all live keys: the E / G / mask tiles come through LDS one (query tile, key tile) block at a time
-// (32 x 32 pairs, ArmStage<T, HG, 1>), the raw logits stay in registers until the row maximum and sum are known.
+// (32 x 32 pairs, ArmStage<T, HG, 1>: arm_stage_* of triplet_common.hpp with key origin k0 = 32*kt), the raw logits stay in
+// registers until the row maximum and sum are known (tile_softmax).  AggCtx and the slab descriptors are those of N <= 64.
 // Dropout: unit (b*2 + dir)*H + h as for N <= 64, word index (i*128 + k) >> 1 (triplet_common.hpp).
 #include "triplet_common.hpp"
 
 namespace tgt {
 
-constexpr int kAggKbStride = 128;        // dropout word stride of a row i for N > 64
-
-struct AggKbCtx {
-    int b, dir, g, h, tile, N;
-    ThirdArm ta;
-};
-template <int HG>
-__device__ __forceinline__ AggKbCtx agg_kb_ctx(const tgt_triplet_aggregate_args& a, int wave) {
-    AggKbCtx c;
-    const int ngroups = a.H / HG, ntiles = (a.N + 31) / 32;
-    int bid = blockIdx.x;
-    c.tile = bid % ntiles;
-    bid /= ntiles;
-    c.g = bid % ngroups;
-    bid /= ngroups;
-    c.dir = bid & 1;
-    c.b = bid >> 1;
-    c.h = c.g * HG + wave;
-    c.N = a.N;
-    const bool use_mask = c.dir == 0 || (a.flags & TGT_TRI_MASK_OUT);
-    c.ta = ThirdArm{a.eg[c.dir], a.ld_eg[c.dir], a.e_off[c.dir], a.g_off[c.dir], use_mask ? a.mask : nullptr,
-                    true, (a.flags & TGT_TRI_GATED) != 0};
-    return c;
-}
-// rows k of V[j,k] (inward) / V[k,j] (outward) of this head group
-template <typename T, int HG>
-__device__ __forceinline__ SlabBuf agg_kb_v_slab(const void* tensor, int64_t ld, int off, const AggKbCtx& c) {
-    const int64_t sz = sizeof(T), N = c.N;
-    const uint32_t ldb = (uint32_t)(ld * sz);
-    return SlabBuf{graph_rsrc(tensor, N * N * ld * sz, c.b), (uint32_t)((off + c.g * HG * 16) * sz),
-                   c.dir == 0 ? ldb : (uint32_t)N * ldb, c.dir == 0 ? (uint32_t)N * ldb : ldb};
-}
-// rows i of X[i,j] (the aggregate's output and its gradient)
-template <typename T, int HG>
-__device__ __forceinline__ SlabBuf agg_kb_o_slab(const void* tensor, int64_t ld, int off, const AggKbCtx& c) {
-    const int64_t sz = sizeof(T), N = c.N;
-    const uint32_t ldb = (uint32_t)(ld * sz);
-    return SlabBuf{graph_rsrc(tensor, N * N * ld * sz, c.b), (uint32_t)((off + c.g * HG * 16) * sz), (uint32_t)N * ldb, ldb};
-}
-
-// ---------------------------------------------------------------------------
-// Third-arm stage of ONE block of 32 x 32 pairs (query tile at i0, key tile at k0): arm_stage_* of triplet_common.hpp with a
-// key offset.  inward: pair (x, y) = (i, k); outward: (x, y) = (k, i).
-// ---------------------------------------------------------------------------
-template <typename T, int HG>
-__device__ __forceinline__ void agg_kb_stage_load(const ThirdArm& ta, int b, int dir, int g, int N, int i0, int k0, char* lds, int tid) {
-    using A = ArmStage<T, HG, 1>;
-    const int x0 = dir == 0 ? i0 : k0, y0 = dir == 0 ? k0 : i0;
-    const int pitch = A::pitch(dir), mpitch = A::mpitch(dir);
-    const T* eg = reinterpret_cast<const T*>(ta.eg);
-    for (int idx = tid; idx < 32 * 32 * A::kVals; idx += HG * 64) {
-        const int v = idx % A::kVals, p = idx / A::kVals, yy = p % 32, xx = p / 32;
-        const int x = x0 + xx, y = y0 + yy;
-        T val = from_f32<T>(0.f);
-        if (x < N && y < N) {
-            const bool is_e = v < HG;
-            if (is_e ? ta.biased : ta.gated)
-                val = eg[(((int64_t)b * N + x) * N + y) * ta.ld + (is_e ? ta.e_off + g * HG + v : ta.g_off + g * HG + v - HG)];
-        }
-        *reinterpret_cast<T*>(lds + xx * pitch + yy * A::kPairBytes + v * (int)sizeof(T)) = val;
-    }
-    for (int idx = tid; idx < 32 * 32; idx += HG * 64) {
-        const int yy = idx % 32, xx = idx / 32, x = x0 + xx, y = y0 + yy;
-        float m = 0.f;
-        if (x < N && y < N && ta.mask) m = ta.mask[((int64_t)b * N + x) * N + y];
-        *reinterpret_cast<float*>(lds + A::kOffM + xx * mpitch + yy * 4) = m;
-    }
-}
-// the block of head `hh` of the group in accumulator layout: lane column i = i0 + r, register q <-> k = k0 + acc_row(q, hi)
-template <typename T, int HG, bool PAD_COLS_NEG_INF>
-__device__ __forceinline__ void agg_kb_stage_read(const ThirdArm& ta, const char* lds, int dir, int hh, int N, int r, int hi,
-                                                  int i0, int k0, float (&biasM)[16], float (&gate)[16]) {
-    using A = ArmStage<T, HG, 1>;
-    const int pitch = A::pitch(dir), mpitch = A::mpitch(dir);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int kl = acc_row(q, hi), k = k0 + kl, i = i0 + r;
-        const bool valid = i < N && k < N;
-        const int xx = dir == 0 ? r : kl, yy = dir == 0 ? kl : r;
-        const char* pp = lds + xx * pitch + yy * A::kPairBytes;
-        const float e = to_f32(*reinterpret_cast<const T*>(pp + hh * (int)sizeof(T)));
-        const float gl = to_f32(*reinterpret_cast<const T*>(pp + (HG + hh) * (int)sizeof(T)));
-        const float m = *reinterpret_cast<const float*>(lds + A::kOffM + xx * mpitch + yy * 4);
-        biasM[q] = (k < N && (!PAD_COLS_NEG_INF || i < N)) ? e + m : -INFINITY;
-        gate[q] = valid ? (ta.gated ? fast_sigmoid(gl + m) : 1.f) : 0.f;
-    }
-}
-template <typename T, int HG>
-__device__ __forceinline__ void agg_kb_stage_put_grad(char* lds, int dir, int hh, int r, int hi, const float (&dE)[16],
-                                                      const float (&dG)[16]) {
-    using A = ArmStage<T, HG, 1>;
-    const int pitch = A::pitch(dir);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int kl = acc_row(q, hi);
-        const int xx = dir == 0 ? r : kl, yy = dir == 0 ? kl : r;
-        char* pp = lds + xx * pitch + yy * A::kPairBytes;
-        *reinterpret_cast<T*>(pp + hh * (int)sizeof(T)) = from_f32<T>(dE[q]);
-        *reinterpret_cast<T*>(pp + (HG + hh) * (int)sizeof(T)) = from_f32<T>(dG[q]);
-    }
-}
-template <typename T, int HG>
-__device__ __forceinline__ void agg_kb_stage_store_grad(const ThirdArm& ta, void* d_eg, int b, int dir, int g, int N, int i0,
-                                                        int k0, const char* lds, int tid) {
-    using A = ArmStage<T, HG, 1>;
-    const int x0 = dir == 0 ? i0 : k0, y0 = dir == 0 ? k0 : i0;
-    const int pitch = A::pitch(dir);
-    T* deg = reinterpret_cast<T*>(d_eg);
-#pragma nounroll
-    for (int idx = tid; idx < 32 * 32 * A::kVals; idx += HG * 64) {
-        const int v = idx % A::kVals, p = idx / A::kVals, yy = p % 32, xx = p / 32;
-        const int x = x0 + xx, y = y0 + yy;
-        const bool is_e = v < HG;
-        if (x < N && y < N && (is_e ? ta.biased : ta.gated))
-            deg[(((int64_t)b * N + x) * N + y) * ta.ld + (is_e ? ta.e_off + g * HG + v : ta.g_off + g * HG + v - HG)] =
-                *reinterpret_cast<const T*>(lds + xx * pitch + yy * A::kPairBytes + v * (int)sizeof(T));
-    }
-}
-
 // softmax weights p and gates of query tile i0 against ALL key tiles, (lane = i) layout.  Key tiles past N are never staged:
 // their logits are -inf (weight exactly 0) and their gates 0.  Two barriers per staged tile; `lds` aliases the slab sets.
 template <typename T, int HG, bool PAD>
-__device__ __forceinline__ void agg_kb_softmax(const AggKbCtx& c, int wave, int tid, int r, int hi, int i0, char* lds,
+__device__ __forceinline__ void agg_kb_softmax(const AggCtx& c, int wave, int tid, int r, int hi, int i0, char* lds,
                                                float (&p)[4][16], float (&gate)[4][16]) {
     const int N = c.N;
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
         if (32 * kt < N) {
-            agg_kb_stage_load<T, HG>(c.ta, c.b, c.dir, c.g, N, i0, 32 * kt, lds, tid);
+            arm_stage_load<T, HG, 1>(c.ta, c.b, c.dir, c.g, N, i0, lds, tid, 32 * kt);
             __syncthreads();
-            agg_kb_stage_read<T, HG, PAD>(c.ta, lds, c.dir, wave, N, r, hi, i0, 32 * kt, p[kt], gate[kt]);
+            arm_stage_read<T, HG, 1, PAD>(c.ta, lds, c.dir, wave, N, r, hi, i0, 0, p[kt], gate[kt], 32 * kt);
             __syncthreads();
         } else {
 #pragma unroll
             for (int q = 0; q < 16; ++q) { p[kt][q] = -INFINITY; gate[kt][q] = 0.f; }
         }
     }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) mx = fmaxf(mx, p[kt][q]);
-    mx = fmaxf(mx, xhalf(mx));
-    if (mx == -INFINITY) mx = 0.f;               // padding column: all weights exactly 0 (and no exp(-inf + inf))
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            p[kt][q] = fast_exp(p[kt][q] - mx);
-            sum += p[kt][q];
-        }
-    sum += xhalf(sum);
-    const float inv = sum > 0.f ? fast_rcp(sum) : 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) p[kt][q] *= inv;
+    tile_softmax<4>(p);
 }
 // the weights the aggregate multiplies with: softmax * gate, dropout applied
 __device__ __forceinline__ f32x16 agg_kb_dropped(const float (&p)[16], const float (&gate)[16], const TriDrop& drop, uint32_t unit,
@@ -185,7 +47,7 @@ __device__ __forceinline__ f32x16 agg_kb_dropped(const float (&p)[16], const flo
 #pragma unroll
     for (int q = 0; q < 16; ++q) w[q] = p[q] * gate[q];
     if (drop.on) {
-        const uint32_t keep = tri_drop_bits(drop, unit, i, kt, hi, kAggKbStride);
+        const uint32_t keep = tri_drop_bits(drop, unit, i, kt, hi, kTriDropStrideKb);
 #pragma unroll
         for (int q = 0; q < 16; ++q) w[q] = (keep >> q) & 1u ? w[q] * drop.scale : 0.f;
     }
@@ -204,14 +66,14 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_fwd_kernel(const tgt_tripl
     constexpr int kSet = 5 * G::kSlabBytes;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hi = lane >> 5;
-    const AggKbCtx c = agg_kb_ctx<HG>(a, wave);
+    const AggCtx c = agg_ctx<HG, true>(a, wave);
     const int N = c.N, i0 = 32 * c.tile;
     F ident_d[1];
     make_ident_d<T, 1>(ident_d, r, hi);
     const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
     const uint32_t drop_unit = (uint32_t)((c.b * 2 + c.dir) * a.H + c.h);
-    const SlabBuf bV = agg_kb_v_slab<T, HG>(a.v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);
-    const SlabBuf bO = agg_kb_o_slab<T, HG>(a.out, a.ld_out, a.o_off[c.dir], c);
+    const SlabBuf bV = agg_v_slab<T, 16, HG>(a.v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);
+    const SlabBuf bO = agg_o_slab<T, 16, HG>(a.out, a.ld_out, a.o_off[c.dir], c);
 
     F pa[4][2];
     {
@@ -263,12 +125,12 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_bwd_a_kernel(const tgt_tri
     constexpr int kSet = 5 * G::kSlabBytes;               // {dO (32 rows) | V (128)}, two sets (see forward)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hi = lane >> 5;
-    const AggKbCtx c = agg_kb_ctx<HG>(a, wave);
+    const AggCtx c = agg_ctx<HG, true>(a, wave);
     const int N = c.N, i0 = 32 * c.tile;
     const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
     const uint32_t drop_unit = (uint32_t)((c.b * 2 + c.dir) * a.H + c.h);
-    const SlabBuf bV = agg_kb_v_slab<T, HG>(a.v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);
-    const SlabBuf dO = agg_kb_o_slab<T, HG>(a.d_out, a.ld_out, a.o_off[c.dir], c);
+    const SlabBuf bV = agg_v_slab<T, 16, HG>(a.v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);
+    const SlabBuf dO = agg_o_slab<T, 16, HG>(a.d_out, a.ld_out, a.o_off[c.dir], c);
 
     f32x16 dacc[4];           // dA^T[k][i], summed over j
 #pragma unroll
@@ -316,7 +178,7 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_bwd_a_kernel(const tgt_tri
     if (drop.on) {            // dacc is the gradient of the DROPPED weights
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
-            const uint32_t keep = tri_drop_bits(drop, drop_unit, i0 + r, kt, hi, kAggKbStride);
+            const uint32_t keep = tri_drop_bits(drop, drop_unit, i0 + r, kt, hi, kTriDropStrideKb);
 #pragma unroll
             for (int q = 0; q < 16; ++q) dacc[kt][q] = (keep >> q) & 1u ? dacc[kt][q] * drop.scale : 0.f;
         }
@@ -336,9 +198,9 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_bwd_a_kernel(const tgt_tri
                 dG[q] = dacc[kt][q] * p[kt][q] * gate[kt][q] * (1.f - gate[kt][q]);
                 dE[q] = p[kt][q] * (dacc[kt][q] * gate[kt][q] - delta);
             }
-            agg_kb_stage_put_grad<T, HG>(smem, c.dir, wave, r, hi, dE, dG);
+            arm_stage_put_grad<T, HG, 1>(smem, c.dir, wave, r, hi, 0, dE, dG);
             __syncthreads();
-            agg_kb_stage_store_grad<T, HG>(c.ta, a.d_eg[c.dir], c.b, c.dir, c.g, N, i0, 32 * kt, smem, tid);
+            arm_stage_store_grad<T, HG, 1>(c.ta, a.d_eg[c.dir], c.b, c.dir, c.g, N, i0, smem, tid, 32 * kt);
             __syncthreads();
         }
     }
@@ -357,7 +219,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     constexpr int kSet = 4 * G::kSlabBytes;               // {dO (128 rows i), overwritten in place by dV (128 rows k)}, two sets
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hi = lane >> 5;
-    const AggKbCtx c = agg_kb_ctx<HG>(a, wave);
+    const AggCtx c = agg_ctx<HG, true>(a, wave);
     const int N = c.N, j0 = 32 * c.tile, j1 = j0 + 32 < N ? j0 + 32 : N;
     const int kpart = blockIdx.y;                         // owns key tiles [KT*kpart, KT*kpart + KT)
     if (32 * KT * kpart >= N) return;                     // (the whole workgroup, before any barrier)
@@ -365,8 +227,8 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     make_ident_d<T, 1>(ident_d, r, hi);
     const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
     const uint32_t drop_unit = (uint32_t)((c.b * 2 + c.dir) * a.H + c.h);
-    const SlabBuf dV = agg_kb_v_slab<T, HG>(a.d_v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);      // d_v mirrors v
-    const SlabBuf dO = agg_kb_o_slab<T, HG>(a.d_out, a.ld_out, a.o_off[c.dir], c);
+    const SlabBuf dV = agg_v_slab<T, 16, HG>(a.d_v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);      // d_v mirrors v
+    const SlabBuf dO = agg_o_slab<T, 16, HG>(a.d_out, a.ld_out, a.o_off[c.dir], c);
 
     // the weights of every (query tile it, owned key tile kt) in (lane = k, registers = i) layout, as operand fragments over i
     F a2f[4][KT][2];
@@ -448,33 +310,20 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-template <typename K>
-static bool agg_kb_lds(K kernel, bool (&done)[16], int lds) {
-    return lds <= 64 * 1024 || dyn_lds_once(done, reinterpret_cast<const void*>(kernel), lds);
-}
-constexpr int agg_kb_max(int x, int y) { return x > y ? x : y; }
-
 template <typename T, int HG>
 static int launch_agg_kb(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) {
     using G = TriGeo<T, 16, HG>;
     const int grid = a.B * 2 * (a.H / HG) * ((a.N + 31) / 32);
     constexpr int kArm = ArmStage<T, HG, 1>::kBytes;
-    constexpr int kWalkLds = agg_kb_max(10 * G::kSlabBytes, kArm), kVLds = agg_kb_max(8 * G::kSlabBytes, kArm);
+    constexpr int kWalkLds = cmax(10 * G::kSlabBytes, kArm), kVLds = cmax(8 * G::kSlabBytes, kArm);
     static_assert(kWalkLds <= 160 * 1024 && kVLds <= 160 * 1024, "LDS of a CU");
-    if (!bwd) {
-        static bool done[16] = {};
-        if (!agg_kb_lds(tri_agg_kb_fwd_kernel<T, HG>, done, kWalkLds)) return set_error(TGT_ERR_LAUNCH, "triplet aggregate: cannot reserve %d bytes of LDS", kWalkLds);
-        hipLaunchKernelGGL((tri_agg_kb_fwd_kernel<T, HG>), dim3(grid), dim3(G::kThreads), kWalkLds, st, a);
-        return check_launch("tri_agg_kb_fwd_kernel");
-    }
+    if (!bwd) return launch_lds<tri_agg_kb_fwd_kernel<T, HG>>("tri_agg_kb_fwd_kernel", dim3(grid), dim3(G::kThreads), kWalkLds, st, a);
     constexpr int KT = sizeof(T) == 2 ? 4 : 2;
-    static bool done_a[16] = {}, done_v[16] = {};
-    if (!agg_kb_lds(tri_agg_kb_bwd_a_kernel<T, HG>, done_a, kWalkLds) || !agg_kb_lds(tri_agg_kb_bwd_v_kernel<T, HG, KT>, done_v, kVLds))
-        return set_error(TGT_ERR_LAUNCH, "triplet aggregate bwd: cannot reserve %d bytes of LDS", kWalkLds);
-    hipLaunchKernelGGL((tri_agg_kb_bwd_a_kernel<T, HG>), dim3(grid), dim3(G::kThreads), kWalkLds, st, a);
-    if (int rc = check_launch("tri_agg_kb_bwd_a_kernel")) return rc;
-    hipLaunchKernelGGL((tri_agg_kb_bwd_v_kernel<T, HG, KT>), dim3(grid, 4 / KT), dim3(G::kThreads), kVLds, st, a);
-    return check_launch("tri_agg_kb_bwd_v_kernel");
+    // (both reservations before the first launch: a failed one leaves nothing half-written)
+    if (int rc = reserve_lds<tri_agg_kb_bwd_a_kernel<T, HG>>("tri_agg_kb_bwd_a_kernel", kWalkLds)) return rc;
+    if (int rc = reserve_lds<tri_agg_kb_bwd_v_kernel<T, HG, KT>>("tri_agg_kb_bwd_v_kernel", kVLds)) return rc;
+    if (int rc = launch_lds<tri_agg_kb_bwd_a_kernel<T, HG>>("tri_agg_kb_bwd_a_kernel", dim3(grid), dim3(G::kThreads), kWalkLds, st, a)) return rc;
+    return launch_lds<tri_agg_kb_bwd_v_kernel<T, HG, KT>>("tri_agg_kb_bwd_v_kernel", dim3(grid, 4 / KT), dim3(G::kThreads), kVLds, st, a);
 }
 template <typename T>
 static int dispatch_agg_kb(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) {

@@ -568,20 +568,9 @@ static int launch_one(const tgt_triplet_attention_args& a_in, hipStream_t st) {
     const tgt_triplet_attention_args& a = a_in;
 #endif
     static const bool dma = !(getenv("TGT_TRI_BWD2_DMA") && atoi(getenv("TGT_TRI_BWD2_DMA")) == 0);       // A/B knob
-    if (dma) {
-        static bool attr_set[16] = {};
-        constexpr int kLds = Lay<true>::kLds;
-        if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&tri_att_bwd2_kernel<T, CS, FL, true>), kLds))
-            return set_error(TGT_ERR_LAUNCH, "tri_att_bwd2_kernel: cannot reserve %d bytes of LDS", kLds);
-        hipLaunchKernelGGL((tri_att_bwd2_kernel<T, CS, FL, true>), dim3(a.B * 2 * (a.H / HG)), dim3(kThreads), kLds, st, a);
-    } else {
-        static bool attr_set[16] = {};
-        constexpr int kLds = Lay<false>::kLds;
-        if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&tri_att_bwd2_kernel<T, CS, FL, false>), kLds))
-            return set_error(TGT_ERR_LAUNCH, "tri_att_bwd2_kernel: cannot reserve %d bytes of LDS", kLds);
-        hipLaunchKernelGGL((tri_att_bwd2_kernel<T, CS, FL, false>), dim3(a.B * 2 * (a.H / HG)), dim3(kThreads), kLds, st, a);
-    }
-    return check_launch("tri_att_bwd2_kernel");
+    const dim3 grid(a.B * 2 * (a.H / HG));
+    if (dma) return launch_lds<tri_att_bwd2_kernel<T, CS, FL, true>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<true>::kLds, st, a);
+    return launch_lds<tri_att_bwd2_kernel<T, CS, FL, false>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<false>::kLds, st, a);
 }
 template <typename T>
 static int launch(const tgt_triplet_attention_args& a, hipStream_t st) {

@@ -22,40 +22,8 @@
 
 namespace tgt {
 
-constexpr int kKbStride = 128;        // dropout word stride of a row i for N > 64
-
-struct KbCtx {
-    int b, dir, g, h, tile, N;
-};
-template <int HG>
-__device__ __forceinline__ KbCtx kb_ctx(const tgt_triplet_attention_args& a, int wave) {
-    KbCtx c;
-    const int ngroups = a.H / HG, ntiles = (a.N + 31) / 32;
-    int bid = blockIdx.x;
-    c.tile = bid % ntiles;
-    bid /= ntiles;
-    c.g = bid % ngroups;
-    bid /= ngroups;
-    c.dir = bid & 1;
-    c.b = bid >> 1;
-    c.h = c.g * HG + wave;
-    c.N = a.N;
-    return c;
-}
 __device__ __forceinline__ float* kb_stats(const tgt_triplet_attention_args& a, int b, int dir, int h, int j, int Np) {
     return reinterpret_cast<float*>(a.workspace) + ((((int64_t)b * 2 + dir) * a.H + h) * a.N + j) * 3 * Np;
-}
-// keep bits in the K sweep's layout: lane = key k, register q <-> i = i0 + acc_row(q, hi)
-__device__ __forceinline__ uint32_t kb_drop_bits_t(const TriDrop& d, uint32_t unit, int i0, int k, int hi) {
-    const uint32_t base = mix32(d.seed_lo ^ mix32(unit)) + d.seed_hi;
-    uint32_t bits = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int i = i0 + acc_row(q, hi);
-        const uint32_t r = mix32(base + (uint32_t)((i * kKbStride + k) >> 1) * 0x9e3779b9u);
-        bits |= (((k & 1) ? (r >> 16) : (r & 0xffffu)) >= d.thresh16 ? 1u : 0u) << q;
-    }
-    return bits;
 }
 
 // ---------------------------------------------------------------------------
@@ -72,7 +40,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hi = lane >> 5;
-    const KbCtx c = kb_ctx<HG>(a, wave);
+    const TriCtx c = tri_ctx<T, 16, HG, true>(a, wave);
     const int N = c.N, i0 = 32 * c.tile;
     const ThirdArm ta = tri_third_arm(a, c.dir);
     F ident_d[1];
@@ -165,7 +133,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
                 l = l * alpha + sum;             // in-lane partial: alpha is the same in both lane halves
                 m = mn;
                 if (drop.on) {
-                    const uint32_t keep = tri_drop_bits(drop, drop_unit0 + j, i0 + r, kt, hi, kKbStride);
+                    const uint32_t keep = tri_drop_bits(drop, drop_unit0 + j, i0 + r, kt, hi, kTriDropStrideKb);
 #pragma unroll
                     for (int q = 0; q < 16; ++q) s[q] = (keep >> q) & 1u ? s[q] * drop.scale : 0.f;
                 }
@@ -200,7 +168,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hi = lane >> 5;
-    const KbCtx c = kb_ctx<HG>(a, wave);
+    const TriCtx c = tri_ctx<T, 16, HG, true>(a, wave);
     const int N = c.N, i0 = 32 * c.tile, Np = (N + 31) & ~31;
     const ThirdArm ta = tri_third_arm(a, c.dir);
     F ident_d[1];
@@ -309,7 +277,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
                 const float ms = mn == -INFINITY ? 0.f : mn;        // padding column (i >= N): every weight is exactly 0
                 const float alpha = fast_exp(m - ms);
                 uint32_t keep = 0xffffu;
-                if (drop.on) keep = tri_drop_bits(drop, drop_unit0 + j, i0 + r, kt, hi, kKbStride);
+                if (drop.on) keep = tri_drop_bits(drop, drop_unit0 + j, i0 + r, kt, hi, kTriDropStrideKb);
                 float sum = 0.f, dsum = 0.f;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
@@ -352,7 +320,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
                 s = mma32(fk[0], fq[0], s);
                 da = mma32(fv[0], fo[0], da);
                 uint32_t keep = 0xffffu;
-                if (drop.on) keep = tri_drop_bits(drop, drop_unit0 + j, i0 + r, kt, hi, kKbStride);
+                if (drop.on) keep = tri_drop_bits(drop, drop_unit0 + j, i0 + r, kt, hi, kTriDropStrideKb);
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const float p = fast_exp(s[q] * a.scale + biasM[kt][q] - ms) * inv;
@@ -405,7 +373,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hi = lane >> 5;
-    const KbCtx c = kb_ctx<HG>(a, wave);
+    const TriCtx c = tri_ctx<T, 16, HG, true>(a, wave);
     const int N = c.N, k0 = 32 * c.tile, Np = (N + 31) & ~31;
     const ThirdArm ta = tri_third_arm(a, c.dir);
     F ident_d[1];
@@ -500,7 +468,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
                 qT = mma32(fq[0], ident_d[0], qT);          // Q[i][d] -> lane d
                 oT = mma32(fo[0], ident_d[0], oT);          // dO[i][d] -> lane d
                 uint32_t keep = 0xffffu;
-                if (drop.on) keep = kb_drop_bits_t(drop, drop_unit0 + j, 32 * it, k0 + r, hi);
+                if (drop.on) keep = tri_drop_bits_t(drop, drop_unit0 + j, 32 * it, k0 + r, hi);
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const int ib = 32 * it + 8 * g4 + 4 * hi;          // acc_row(4*g4 + t, hi) = 8*g4 + 4*hi + t
@@ -538,11 +506,6 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-template <typename K>
-static bool kb_lds(K kernel, bool (&done)[16], int lds) {
-    return lds <= 64 * 1024 || dyn_lds_once(done, reinterpret_cast<const void*>(kernel), lds);
-}
-
 template <typename T, int HG>
 static int launch_kb(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) {
     using G = TriGeo<T, 16, HG>;
@@ -550,22 +513,15 @@ static int launch_kb(const tgt_triplet_attention_args& a, bool bwd, hipStream_t 
     constexpr bool kPF = sizeof(T) == 2;
     const int grid = a.B * 2 * (a.H / HG) * ((a.N + 31) / 32);
     constexpr int kFwdLds = 9 * G::kSlabBytes, kBwdQLds = 10 * G::kSlabBytes, kBwdKLds = 10 * G::kSlabBytes + HG * 384 * 4;
-    if (!bwd) {
-        static bool done[16] = {};
-        if (!kb_lds(tri_kb_fwd_kernel<T, HG, kPF>, done, kFwdLds)) return set_error(TGT_ERR_LAUNCH, "triplet attention: cannot reserve %d bytes of LDS", kFwdLds);
-        hipLaunchKernelGGL((tri_kb_fwd_kernel<T, HG, kPF>), dim3(grid), dim3(G::kThreads), kFwdLds, st, a);
-        return check_launch("tri_kb_fwd_kernel");
-    }
-    static bool done_e[16] = {}, done_q[16] = {}, done_k[16] = {};
-    if (!kb_lds(tri_kb_bwd_q_kernel<T, HG, kPF, true>, done_e, kBwdQLds) || !kb_lds(tri_kb_bwd_q_kernel<T, HG, kPF, false>, done_q, kBwdQLds) ||
-        !kb_lds(tri_kb_bwd_k_kernel<T, HG, kPF>, done_k, kBwdKLds))
-        return set_error(TGT_ERR_LAUNCH, "triplet attention bwd: cannot reserve %d bytes of LDS", kBwdKLds);
-    hipLaunchKernelGGL((tri_kb_bwd_q_kernel<T, HG, kPF, true>), dim3(grid), dim3(G::kThreads), kBwdQLds, st, a);       // E sweep: statistics first
-    if (int rc = check_launch("tri_kb_bwd_e_kernel")) return rc;
-    hipLaunchKernelGGL((tri_kb_bwd_q_kernel<T, HG, kPF, false>), dim3(grid), dim3(G::kThreads), kBwdQLds, st, a);
-    if (int rc = check_launch("tri_kb_bwd_q_kernel")) return rc;
-    hipLaunchKernelGGL((tri_kb_bwd_k_kernel<T, HG, kPF>), dim3(grid), dim3(G::kThreads), kBwdKLds, st, a);
-    return check_launch("tri_kb_bwd_k_kernel");
+    const dim3 blocks(grid), threads(G::kThreads);
+    if (!bwd) return launch_lds<tri_kb_fwd_kernel<T, HG, kPF>>("tri_kb_fwd_kernel", blocks, threads, kFwdLds, st, a);
+    // (all three reservations before the first launch: a failed one leaves nothing half-written)
+    if (int rc = reserve_lds<tri_kb_bwd_q_kernel<T, HG, kPF, true>>("tri_kb_bwd_e_kernel", kBwdQLds)) return rc;
+    if (int rc = reserve_lds<tri_kb_bwd_q_kernel<T, HG, kPF, false>>("tri_kb_bwd_q_kernel", kBwdQLds)) return rc;
+    if (int rc = reserve_lds<tri_kb_bwd_k_kernel<T, HG, kPF>>("tri_kb_bwd_k_kernel", kBwdKLds)) return rc;
+    if (int rc = launch_lds<tri_kb_bwd_q_kernel<T, HG, kPF, true>>("tri_kb_bwd_e_kernel", blocks, threads, kBwdQLds, st, a)) return rc;    // E sweep: statistics first
+    if (int rc = launch_lds<tri_kb_bwd_q_kernel<T, HG, kPF, false>>("tri_kb_bwd_q_kernel", blocks, threads, kBwdQLds, st, a)) return rc;
+    return launch_lds<tri_kb_bwd_k_kernel<T, HG, kPF>>("tri_kb_bwd_k_kernel", blocks, threads, kBwdKLds, st, a);
 }
 template <typename T>
 static int dispatch_kb(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) {

@@ -326,9 +326,6 @@ template <typename T>
 static int launch_proj(const tgt_triplet_attention_args& a, const void* x, const void* w, const void* bias, hipStream_t st) {
     const int grid = a.B * 2 * (a.H / 8);
     static_assert(ArmStage<T, 8, 1>::kBytes <= proj2::kOffO, "arm stage must fit the aliased area");
-    static bool attr_set[16] = {};
-    if (!dyn_lds_once(attr_set, reinterpret_cast<const void*>(&tri_att_proj_fwd_kernel<T>), proj2::kLds))
-        return set_error(TGT_ERR_LAUNCH, "tri_att_proj_fwd_kernel: cannot reserve %d bytes of LDS", proj2::kLds);
 #ifdef TGT_PROBES
     static const int ablate = getenv("TGT_PROJ_ABLATE") ? atoi(getenv("TGT_PROJ_ABLATE")) : 0;
     tgt_triplet_attention_args aa = a;
@@ -336,9 +333,8 @@ static int launch_proj(const tgt_triplet_attention_args& a, const void* x, const
 #else
     const tgt_triplet_attention_args& aa = a;          // (_pad1 is padding: never written, never read)
 #endif
-    hipLaunchKernelGGL((tri_att_proj_fwd_kernel<T>), dim3(grid), dim3(1024), proj2::kLds, st, aa, reinterpret_cast<const T*>(x),
-                       reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias));
-    return check_launch("tri_att_proj_fwd_kernel");
+    return launch_lds<tri_att_proj_fwd_kernel<T>>("tri_att_proj_fwd_kernel", dim3(grid), dim3(1024), proj2::kLds, st, aa,
+                                                  reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias));
 }
 
 int triplet_attention_proj_supported(const tgt_triplet_attention_args* a, int C) {

@@ -321,8 +321,10 @@ __device__ __forceinline__ void store_third_arm_grad(const ThirdArm& ta, void* d
 // then picks its head's tile in accumulator layout from LDS; the backward
 // scatters dE/dG back the same way.  The staging area aliases the slab
 // buffers (used strictly before / after the walk over j).
-//   region of pass i0: inward  x in [i0,i0+32), y in [0,32NT)
-//                      outward x in [0,32NT),   y in [i0,i0+32)
+//   region of pass i0: inward  x in [i0,i0+32), y in [k0,k0+32NT)
+//                      outward x in [k0,k0+32NT), y in [i0,i0+32)
+// k0 = key origin of the staged region: 0 where all NT key tiles are staged at once, 32*kt with NT = 1 where they go
+// through one by one (N > 64).
 // row pitch + 4 bytes: lanes that differ in x hit different banks.
 // ---------------------------------------------------------------------------
 template <typename T, int HG, int NT>
@@ -339,9 +341,9 @@ struct ArmStage {
 
 template <typename T, int HG, int NT>
 __device__ __forceinline__ void arm_stage_load(const ThirdArm& ta, int b, int dir, int g, int N, int i0, char* lds,
-                                               int tid) {
+                                               int tid, int k0 = 0) {
     using A = ArmStage<T, HG, NT>;
-    const int nx = A::nx(dir), ny = A::ny(dir), x0 = dir == 0 ? i0 : 0, y0 = dir == 0 ? 0 : i0;
+    const int nx = A::nx(dir), ny = A::ny(dir), x0 = dir == 0 ? i0 : k0, y0 = dir == 0 ? k0 : i0;
     const int pitch = A::pitch(dir), mpitch = A::mpitch(dir);
     const T* eg = reinterpret_cast<const T*>(ta.eg);
     for (int idx = tid; idx < nx * ny * A::kVals; idx += HG * 64) {
@@ -363,15 +365,15 @@ __device__ __forceinline__ void arm_stage_load(const ThirdArm& ta, int b, int di
     }
 }
 
-// tile (query tile at i0, key tile kt) of head `hh` of the group, accumulator layout
+// tile (query tile at i0, key tile kt of the staged region) of head `hh` of the group, accumulator layout
 template <typename T, int HG, int NT, bool PAD_COLS_NEG_INF>
 __device__ __forceinline__ void arm_stage_read(const ThirdArm& ta, const char* lds, int dir, int hh, int N, int r, int hi,
-                                               int i0, int kt, float (&biasM)[16], float (&gate)[16]) {
+                                               int i0, int kt, float (&biasM)[16], float (&gate)[16], int k0 = 0) {
     using A = ArmStage<T, HG, NT>;
     const int pitch = A::pitch(dir), mpitch = A::mpitch(dir);
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        const int kl = 32 * kt + acc_row(q, hi), k = kl, i = i0 + r;
+        const int kl = 32 * kt + acc_row(q, hi), k = k0 + kl, i = i0 + r;
         const bool valid = i < N && k < N;
         const int xx = dir == 0 ? r : kl, yy = dir == 0 ? kl : r;
         const char* pp = lds + xx * pitch + yy * A::kPairBytes;
@@ -383,6 +385,7 @@ __device__ __forceinline__ void arm_stage_read(const ThirdArm& ta, const char* l
     }
 }
 
+// (kt counts from the staged region's first key tile, as in arm_stage_read)
 template <typename T, int HG, int NT>
 __device__ __forceinline__ void arm_stage_put_grad(char* lds, int dir, int hh, int r, int hi, int kt,
                                                    const float (&dE)[16], const float (&dG)[16]) {
@@ -402,12 +405,12 @@ __device__ __forceinline__ void arm_stage_put_grad(char* lds, int dir, int hh, i
 // ((HG*64) % kVals == 0), i.e. a partial column sum of dE (v < HG) or dG of head g*HG + v % HG.
 template <typename T, int HG, int NT>
 __device__ __forceinline__ float arm_stage_store_grad(const ThirdArm& ta, void* d_eg, int b, int dir, int g, int N,
-                                                      int i0, const char* lds, int tid) {
+                                                      int i0, const char* lds, int tid, int k0 = 0) {
     using A = ArmStage<T, HG, NT>;
     static_assert((HG * 64) % A::kVals == 0, "a thread must own one E/G column");
     float part = 0.f;
     if (!(ta.biased || ta.gated)) return part;
-    const int nx = A::nx(dir), ny = A::ny(dir), x0 = dir == 0 ? i0 : 0, y0 = dir == 0 ? 0 : i0;
+    const int nx = A::nx(dir), ny = A::ny(dir), x0 = dir == 0 ? i0 : k0, y0 = dir == 0 ? k0 : i0;
     const int pitch = A::pitch(dir);
     T* deg = reinterpret_cast<T*>(d_eg);
 #pragma nounroll
@@ -424,6 +427,33 @@ __device__ __forceinline__ float arm_stage_store_grad(const ThirdArm& ta, void* 
     return part;
 }
 
+// Softmax over the NT key tiles of logits a lane holds in accumulator layout (lane column i, both lane halves), in place.
+// A padding column (every logit -inf) gets weights of exactly 0: no exp(-inf + inf), no 0 * inf.
+template <int NT>
+__device__ __forceinline__ void tile_softmax(float (&p)[NT][16]) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) mx = fmaxf(mx, p[kt][q]);
+    mx = fmaxf(mx, xhalf(mx));
+    if (mx == -INFINITY) mx = 0.f;
+    float sum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            p[kt][q] = fast_exp(p[kt][q] - mx);
+            sum += p[kt][q];
+        }
+    sum += xhalf(sum);
+    const float inv = sum > 0.f ? fast_rcp(sum) : 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) p[kt][q] *= inv;
+}
+
 // ---------------------------------------------------------------------------
 // Attention dropout (reference lib/tgt/layers/triplet.py:223-225, :242-244, :59-60: F.dropout on
 // the gated weights).  Counter-based, so the backward recomputes the forward's pattern from the
@@ -433,10 +463,12 @@ __device__ __forceinline__ float arm_stage_store_grad(const ThirdArm& ta, void* 
 //   keep(k even) = (word & 0xffff) >= thresh16,  keep(k odd) = (word >> 16) >= thresh16,
 //   thresh16 = clamp(round(p * 65536), 1, 65535); kept weights are scaled by 1/(1-p).
 // Word stride of a row: 64 for N <= 64 (as above).  With k >= 64 that index would alias (i, k) with (i+1, k-64), so the
-// kernels for N > 64 (triplet_attention_kb.hip) use ((i*128 + k) >> 1): `stride` below.  Patterns for N <= 64 are unchanged.
+// kernels for N > 64 (triplet_attention_kb.hip, triplet_aggregate_kb.hip) use ((i*128 + k) >> 1): `stride` below =
+// kTriDropStrideKb.  Patterns for N <= 64 are unchanged.
 // (tests/golden_util.py::triplet_dropout_keep restates it in numpy for the parity tests.)
 // Returns the keep bits of the 16 accumulator elements of one lane: bit q <-> k = 32*kt + acc_row(q,hi).
 // ---------------------------------------------------------------------------
+constexpr int kTriDropStrideKb = 128;
 struct TriDrop {
     uint32_t thresh16, seed_lo, seed_hi;
     float scale;
@@ -465,19 +497,34 @@ __device__ __forceinline__ uint32_t tri_drop_bits(const TriDrop& d, uint32_t uni
     }
     return bits;
 }
+// the same bits transposed, for N > 64: lane = key k, bit q <-> i = i0 + acc_row(q, hi)
+__device__ __forceinline__ uint32_t tri_drop_bits_t(const TriDrop& d, uint32_t unit, int i0, int k, int hi) {
+    const uint32_t base = mix32(d.seed_lo ^ mix32(unit)) + d.seed_hi;
+    uint32_t bits = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int i = i0 + acc_row(q, hi);
+        const uint32_t r = mix32(base + (uint32_t)((i * kTriDropStrideKb + k) >> 1) * 0x9e3779b9u);
+        bits |= (((k & 1) ? (r >> 16) : (r & 0xffffu)) >= d.thresh16 ? 1u : 0u) << q;
+    }
+    return bits;
+}
 
 // ---------------------------------------------------------------------------
-// workgroup coordinates and slab sources of the triplet-attention kernels
+// workgroup coordinates and slab sources of the triplet kernels
 // ---------------------------------------------------------------------------
 struct TriCtx {
-    int b, dir, g, h, N;
+    int b, dir, g, h, tile, N;
 };
-
-template <typename T, int D, int HG>
+// blockIdx.x = ((b*2 + dir)*ngroups + g)*ntiles + tile.  ntiles = 1 where a workgroup owns all of (graph, direction, head
+// group) (N <= 64); TILED: the number of 32-row tiles, where it owns one of them (N > 64).
+template <typename T, int D, int HG, bool TILED = false>
 __device__ __forceinline__ TriCtx tri_ctx(const tgt_triplet_attention_args& a, int wave) {
     TriCtx c;
-    const int ngroups = a.H / HG;
+    const int ngroups = a.H / HG, ntiles = TILED ? (a.N + 31) / 32 : 1;
     int bid = blockIdx.x;
+    c.tile = bid % ntiles;
+    bid /= ntiles;
     c.g = bid % ngroups;
     bid /= ngroups;
     c.dir = bid & 1;
@@ -490,6 +537,49 @@ __device__ __forceinline__ TriCtx tri_ctx(const tgt_triplet_attention_args& a, i
 __device__ __forceinline__ ThirdArm tri_third_arm(const tgt_triplet_attention_args& a, int dir) {
     return ThirdArm{a.eg[dir], a.ld_eg[dir], a.e_off[dir], a.g_off[dir], a.mask,
                     (a.flags & TGT_TRI_BIASED) != 0, (a.flags & TGT_TRI_GATED) != 0};
+}
+
+// The same for the triplet-aggregate kernels (both files), plus their third arm.  The decode is spelled out a second time on
+// purpose: built on TriCtx (as a base or a member) or filled by a decode function shared with tri_ctx, every aggregate
+// kernel, N <= 64 included, came out of hipcc with a different schedule and register assignment; this form compiles to the
+// instruction streams the kernels were measured with.
+struct AggCtx {
+    int b, dir, g, h, N;
+    ThirdArm ta;
+    int tile;
+};
+template <int HG, bool TILED = false>
+__device__ __forceinline__ AggCtx agg_ctx(const tgt_triplet_aggregate_args& a, int wave) {
+    AggCtx c;
+    const int ngroups = a.H / HG, ntiles = TILED ? (a.N + 31) / 32 : 1;
+    int bid = blockIdx.x;
+    c.tile = bid % ntiles;
+    bid /= ntiles;
+    c.g = bid % ngroups;
+    bid /= ngroups;
+    c.dir = bid & 1;
+    c.b = bid >> 1;
+    c.h = c.g * HG + wave;
+    c.N = a.N;
+    const bool use_mask = c.dir == 0 || (a.flags & TGT_TRI_MASK_OUT);
+    c.ta = ThirdArm{a.eg[c.dir], a.ld_eg[c.dir], a.e_off[c.dir], a.g_off[c.dir], use_mask ? a.mask : nullptr,
+                    true, (a.flags & TGT_TRI_GATED) != 0};
+    return c;
+}
+// buffer-addressed slabs: rows k of V[j,k] (inward) / V[k,j] (outward) of this head group
+template <typename T, int D, int HG>
+__device__ __forceinline__ SlabBuf agg_v_slab(const void* tensor, int64_t ld, int off, const AggCtx& c) {
+    const int64_t sz = sizeof(T), N = c.N;
+    const uint32_t ldb = (uint32_t)(ld * sz);
+    return SlabBuf{graph_rsrc(tensor, N * N * ld * sz, c.b), (uint32_t)((off + c.g * HG * D) * sz),
+                   c.dir == 0 ? ldb : (uint32_t)N * ldb, c.dir == 0 ? (uint32_t)N * ldb : ldb};
+}
+// rows i of X[i,j] (the aggregate's output and its gradient)
+template <typename T, int D, int HG>
+__device__ __forceinline__ SlabBuf agg_o_slab(const void* tensor, int64_t ld, int off, const AggCtx& c) {
+    const int64_t sz = sizeof(T), N = c.N;
+    const uint32_t ldb = (uint32_t)(ld * sz);
+    return SlabBuf{graph_rsrc(tensor, N * N * ld * sz, c.b), (uint32_t)((off + c.g * HG * D) * sz), (uint32_t)N * ldb, ldb};
 }
 
 }  // namespace tgt
