@@ -40,6 +40,7 @@ enum {
     TGT_TRI_BIASED      = 1,   /* third-arm bias E present      */
     TGT_TRI_GATED       = 2,   /* third-arm sigmoid gate present */
     TGT_TRI_MASK_OUT    = 4,   /* aggregate only: mask the outward direction (ungated variant) */
+    TGT_TRI_NO_QKV_STORE = 8,  /* tgt_triplet_attention_proj_fwd only: do not write the projected Q/K/V rows (no backward follows) */
 };
 
 const char* tgt_last_error(void);
@@ -441,7 +442,10 @@ int tgt_colsum(const void* x, int32_t x_dtype, int64_t rows, int32_t C, float* o
  *          (rows q_off/k_off/v_off[dir] + h*D + d), bias: same indexing
  *   a    : as tgt_triplet_attention_fwd, but a->qkv[dir] is an OUTPUT here (the projected rows, for
  *          the backward kernel); a->eg (E/G third arm) is still an input.
- * Supported: N <= 32, D = 16, H % 8 == 0, bf16/fp16, C in {64,128,256}
+ *          With TGT_TRI_NO_QKV_STORE in a->flags (a forward that no backward follows: inference) nothing is written
+ *          through a->qkv[dir]: the pointers may be NULL, ld_qkv is not read, and q_off/k_off/v_off only select the rows
+ *          of w / bias.  `out` is bit-identical with and without the flag.  Every other entry point ignores the bit.
+ * Supported: N <= 32, D = 16, H % 8 == 0, bf16/fp16, C = 256
  * (tgt_triplet_attention_proj_supported() tells; otherwise project with a GEMM and call
  * tgt_triplet_attention_fwd). */
 int tgt_triplet_attention_proj_supported(const tgt_triplet_attention_args* a, int32_t C);

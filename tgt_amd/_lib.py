@@ -28,6 +28,7 @@ ABI_VERSION = 32
 
 TGT_F32, TGT_BF16, TGT_F16 = 0, 1, 2
 TRI_BIASED, TRI_GATED, TRI_MASK_OUT = 1, 2, 4
+TRI_NO_QKV_STORE = 8              # tgt_triplet_attention_proj_fwd only: the projected Q/K/V rows are not written
 
 _i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 

@@ -5,7 +5,8 @@
 // (0.8 GB at B=256) with a library GEMM (0.26 ms) and reads them straight back in the attention kernel (0.225 ms).
 // Here the workgroup that walks node j projects the edge rows it needs itself and feeds the attention core through
 // LDS; Q/K/V still go to HBM once (the backward kernel reads them), but nothing is read back in the forward and the
-// tall-skinny GEMM disappears.
+// tall-skinny GEMM disappears.  A forward that no backward follows (TGT_TRI_NO_QKV_STORE: inference) runs the STORE = false
+// instantiation, which keeps the projected rows in LDS only: 0.81 of the 1.24 GB the kernel moves at B = 256 are those rows.
 //
 //   workgroup = (graph b, direction, 8 heads), 16 waves in two ROLES (128 registers each, 4 waves per SIMD):
 //     waves 8-15  PROJECTION of head h = wave - 8: the 48 weight rows [W_Q(h); W_K(h); W_V(h)] x 256 k resident in 96
@@ -17,13 +18,14 @@
 //                 (global -> registers at the top of the step, -> LDS at its end);
 //   so every SIMD holds two matrix-heavy and two VALU-heavy waves.  ONE barrier per step; after it all 1024 threads store
 //   the Q/K/V rows of step j+1 and the O rows of step j as whole 256-byte row pieces (raw buffer stores, out-of-range
-//   offsets instead of branches: triplet_common.hpp).
+//   offsets instead of branches: triplet_common.hpp).  STORE = false: only the O rows leave, through threads 512-1023 as before.
 //
 // Why roles: the round-1 form kept the weights in the attention waves (128 + ~100 registers: 2 waves per
 // SIMD in ONE workgroup per CU, all phases behind the same barrier) and measured 0.77 ms; its ISA shows what that cost --
 // 256 registers + 132 bytes of scratch reloaded inside the walk behind `s_waitcnt vmcnt(0)`, i.e. every prefetch was a
 // synchronous load.
-// Supported: N <= 32, D = 16, H % 8 == 0, 16-bit dtypes, C = 256, no attention dropout.
+// Supported: N <= 32, D = 16, H % 8 == 0, 16-bit dtypes, C = 256, no attention dropout; with or without the Q/K/V rows written
+// (TGT_TRI_NO_QKV_STORE).
 #include <cstdlib>
 #include "triplet_common.hpp"
 
@@ -48,7 +50,7 @@ constexpr uint32_t kNone = 0xffffffffu;
 __device__ __forceinline__ int xoff(int row, int slot) { return row * kXPitch + (slot << 4); }
 }  // namespace proj2
 
-template <typename T, int DIR>
+template <typename T, int DIR, bool STORE>
 __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, const TriCtx& c, const T* x, const T* w,
                                            char* smem, int tid) {
     using namespace proj2;
@@ -69,7 +71,8 @@ __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, 
     char* oslab = smem + kOffO;
     const float* bias_w = reinterpret_cast<const float*>(smem + kOffBias) + hw * 48;
 
-    // global addressing: X rows of the graph (read), Q/K/V rows (written for the backward), O rows
+    // global addressing: X rows of the graph (read), Q/K/V rows (written for the backward), O rows.  (STORE = false: a.qkv may be
+    // NULL; r_dst and the Q/K/V strides are used by the STORE branch of store_step alone and are not materialised.)
     const int64_t sz = sizeof(T), Nl = N;
     const __amdgpu_buffer_rsrc_t r_x = graph_rsrc(x, Nl * Nl * kRowBytes, c.b);
     const uint32_t hch = (uint32_t)(c.g * HG * D * sz), lds_ = (uint32_t)(a.ld_qkv[DIR] * sz), ldo_ = (uint32_t)(a.ld_out * sz);
@@ -92,6 +95,17 @@ __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, 
         const int s_lds = G::lds_off(srow, sslot);
         const bool row_ok = srow < N;
         const uint32_t c16 = (uint32_t)sslot * 16u + hch;
+        if constexpr (!STORE) {
+            // the O rows alone (threads 512-1023, i.e. the projection role: the attention role does not call this at all)
+            const uint4 vb = *reinterpret_cast<const uint4*>(oslab + (jo & 1) * kSlab + s_lds);
+            const uint32_t vo_o = (uint32_t)srow * o_row + (uint32_t)jo * o_j + (uint32_t)(a.o_off[DIR] * sz) + c16;
+            u32x4_t db = {vb.x, vb.y, vb.z, vb.w};
+            if (ablate & 2) return;
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_raw_buffer_store_b128(db, r_out, (int)((row_ok && o_live && shalf == 1) ? vo_o : kNone), 0, TGT_ST_AUX);
+            __builtin_amdgcn_sched_barrier(0);
+            return;
+        }
         const char* set = sets + (jq & 1) * kSet;
         const uint4 va = *reinterpret_cast<const uint4*>(set + shalf * kSlab + s_lds);
         const uint4 vb = *reinterpret_cast<const uint4*>((shalf == 0 ? set + 2 * kSlab : oslab + (jo & 1) * kSlab) + s_lds);
@@ -182,7 +196,7 @@ __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, 
         x_commit(1);
         __syncthreads();                                // B2
         __syncthreads();                                // B3 (the projection waves produce step 0)
-        store_step(0, true, 0, false);
+        if constexpr (STORE) store_step(0, true, 0, false);
         for (int j = 0; j < N; ++j) {
             x_issue(j + 2);
             asm volatile("" ::: "memory");              // (the prefetch is issued HERE, a whole step ahead of its commit)
@@ -219,7 +233,7 @@ __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, 
             }
             x_commit(j + 2);
             __syncthreads();                            // B_j
-            store_step(j + 1, j + 1 < N, j, true);
+            if constexpr (STORE) store_step(j + 1, j + 1 < N, j, true);
         }
     } else {
         // ------------------------------------------------------------------------------------------ projection role
@@ -293,7 +307,7 @@ __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, 
         __syncthreads();                                // B2 (X tiles 0 and 1 are in LDS)
         project(0);
         __syncthreads();                                // B3
-        store_step(0, true, 0, false);
+        if constexpr (STORE) store_step(0, true, 0, false);   // (no O rows yet)
         for (int j = 0; j < N; ++j) {
             if (j + 1 < N && !(ablate & 4)) project(j + 1);
             __syncthreads();                            // B_j
@@ -302,7 +316,7 @@ __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, 
     }
 }
 
-template <typename T>
+template <typename T, bool STORE>
 __global__ void __launch_bounds__(1024, 4) tri_att_proj_fwd_kernel(const tgt_triplet_attention_args a, const T* x, const T* w,
                                                                    const T* bias) {
     constexpr int D = 16, HG = 8;
@@ -318,8 +332,8 @@ __global__ void __launch_bounds__(1024, 4) tri_att_proj_fwd_kernel(const tgt_tri
         const int off = part == 0 ? a.q_off[dir] : (part == 1 ? a.k_off[dir] : a.v_off[dir]);
         reinterpret_cast<float*>(smem + proj2::kOffBias)[(wave & 7) * 48 + lane] = to_f32(bias[off + c.h * D + d]);
     }
-    if (dir == 0) proj2_walk<T, 0>(a, c, x, w, smem, tid);
-    else proj2_walk<T, 1>(a, c, x, w, smem, tid);
+    if (dir == 0) proj2_walk<T, 0, STORE>(a, c, x, w, smem, tid);
+    else proj2_walk<T, 1, STORE>(a, c, x, w, smem, tid);
 }
 
 template <typename T>
@@ -333,8 +347,12 @@ static int launch_proj(const tgt_triplet_attention_args& a, const void* x, const
 #else
     const tgt_triplet_attention_args& aa = a;          // (_pad1 is padding: never written, never read)
 #endif
-    return launch_lds<tri_att_proj_fwd_kernel<T>>("tri_att_proj_fwd_kernel", dim3(grid), dim3(1024), proj2::kLds, st, aa,
-                                                  reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias));
+    // (the store of the projected rows is a compile-time choice: the training instantiation is the kernel it always was)
+    if (a.flags & TGT_TRI_NO_QKV_STORE)
+        return launch_lds<tri_att_proj_fwd_kernel<T, false>>("tri_att_proj_fwd_kernel", dim3(grid), dim3(1024), proj2::kLds, st, aa,
+                                                             reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias));
+    return launch_lds<tri_att_proj_fwd_kernel<T, true>>("tri_att_proj_fwd_kernel", dim3(grid), dim3(1024), proj2::kLds, st, aa,
+                                                        reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias));
 }
 
 int triplet_attention_proj_supported(const tgt_triplet_attention_args* a, int C) {
@@ -351,10 +369,13 @@ int triplet_attention_proj_run(const tgt_triplet_attention_args* a, const void* 
         return set_error(TGT_ERR_UNSUPPORTED,
                          "projected triplet attention needs N <= 32, D = 16, H %% 8 == 0, a 16-bit dtype, C = 256 and no attention dropout "
                          "(got N=%d D=%d H=%d dtype=%d C=%d)", a->N, a->D, a->H, a->dtype, C);
+    const bool store = !(a->flags & TGT_TRI_NO_QKV_STORE);      // (flag set: nothing goes through a->qkv, which may be NULL)
     for (int dir = 0; dir < 2; ++dir) {
-        if (!a->qkv[dir] || !a->out || !a->mask) return set_error(TGT_ERR_INVALID, "projected triplet attention: null tensor");
-        if ((a->ld_qkv[dir] * 2) % 16 || (a->q_off[dir] * 2) % 16 || (a->k_off[dir] * 2) % 16 || (a->v_off[dir] * 2) % 16 ||
-            (a->ld_out * 2) % 16 || (a->o_off[dir] * 2) % 16 || ((uintptr_t)a->qkv[dir] % 16) || ((uintptr_t)a->out % 16))
+        if ((store && !a->qkv[dir]) || !a->out || !a->mask) return set_error(TGT_ERR_INVALID, "projected triplet attention: null tensor");
+        if (store && ((a->ld_qkv[dir] * 2) % 16 || (a->q_off[dir] * 2) % 16 || (a->k_off[dir] * 2) % 16 || (a->v_off[dir] * 2) % 16 ||
+                      ((uintptr_t)a->qkv[dir] % 16)))
+            return set_error(TGT_ERR_INVALID, "projected triplet attention: rows/offsets must be 16-byte aligned");
+        if ((a->ld_out * 2) % 16 || (a->o_off[dir] * 2) % 16 || ((uintptr_t)a->out % 16))
             return set_error(TGT_ERR_INVALID, "projected triplet attention: rows/offsets must be 16-byte aligned");
         if ((a->flags & (TGT_TRI_BIASED | TGT_TRI_GATED)) && !a->eg[dir]) return set_error(TGT_ERR_INVALID, "projected triplet attention: eg missing");
     }

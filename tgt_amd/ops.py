@@ -25,6 +25,7 @@ _PROFILE = None
 
 _TRI_SPLIT = K.tri_split        # A/B knobs: tgt_amd/knobs.py reads the environment once; tests patch these names
 _TRI_PROJ = K.tri_proj
+_TRI_PROJ_INFER = K.tri_proj_infer
 _TRI_COLSUM = K.tri_colsum
 # graph_scale (DropPath-dropped graphs skipped by the triplet kernels) reaches the BACKWARD kernel only with TGT_TRI_SKIP=2: at the
 # BASELINE shapes the backward is 1024 workgroups in exactly four rounds on 256 CUs (one workgroup per CU), and with ~10 % of them
@@ -146,12 +147,17 @@ class TripletLayout:
 
 def _tri_args(fused, mask3, out, L, d_out=None, d_fused=None, colsum=None, dropout=(0.0, 0), eg=None, graph_scale=None):
     """eg given: `fused` holds only the Q/K/V channels (rows of 6C) and `eg` the third-arm E/G channels
-    (rows of L.used - 6C); d_fused / colsum stay ONE fused row of L.width (ld_dqkv / ld_deg)."""
-    B, N = fused.shape[0], fused.shape[1]
+    (rows of L.used - 6C); d_fused / colsum stay ONE fused row of L.width (ld_dqkv / ld_deg).
+    fused None (tgt_triplet_attention_proj_fwd without a backward): no Q/K/V tensor at all -- null pointers and
+    TRI_NO_QKV_STORE; the third arm, if the layout has one, comes through `eg`."""
+    B, N = out.shape[0], out.shape[1]
     a = _lib.TripletAttentionArgs()
     a.B, a.N, a.H, a.D = B, N, L.H, L.D
-    a.dtype, a.flags, a.scale = _DT[fused.dtype], L.flags, float(L.D) ** -0.5
-    p = fused.data_ptr()
+    a.dtype, a.flags, a.scale = _DT[out.dtype], L.flags, float(L.D) ** -0.5
+    if fused is None:
+        assert eg is not None or not L.biased
+        a.flags |= _lib.TRI_NO_QKV_STORE
+    p = fused.data_ptr() if fused is not None else None
     split = eg is not None
     wq = 6 * L.C if split else L.width                    # row length of the Q/K/V tensor
     we, eo = (L.used - 6 * L.C, 6 * L.C) if split else (L.width, 0)      # E/G rows, and where they start in a fused row
@@ -189,7 +195,7 @@ def _tri_args(fused, mask3, out, L, d_out=None, d_fused=None, colsum=None, dropo
     # in stream order afterwards.  (A negative size = a shape the kernels refuse: the entry point says why.)
     need = _lib.lib().tgt_triplet_attention_workspace_bytes(C.byref(a), 0 if d_out is None else 1) if N > 64 else 0
     if need > 0:
-        a._workspace = torch.empty(need, dtype=torch.uint8, device=fused.device)
+        a._workspace = torch.empty(need, dtype=torch.uint8, device=out.device)
         a.workspace, a.workspace_bytes = a._workspace.data_ptr(), need
     return a
 
@@ -511,7 +517,8 @@ def _slow_path_notice(key, msg):
 
 def _proj_fused_ok(x, N, L, cd):
     """the projection-fused forward kernel (tgt_triplet_attention_proj_fwd, wave roles: DESIGN.md section 4, profiles/HISTORY_rounds_1-4.md 4.1a): Q/K/V are
-    projected inside the attention kernel (still written once, for the backward); TGT_TRI_PROJ=0 is the A/B knob"""
+    projected inside the attention kernel (still written once, for the backward -- not at all when no backward follows:
+    TGT_TRI_PROJ_INFER); TGT_TRI_PROJ=0 is the A/B knob"""
     return (_TRI_PROJ and N <= 32 and L.D == 16 and L.H % 8 == 0 and L.width == L.used and
             cd in (torch.bfloat16, torch.float16) and L.C == 256 and x.numel() // L.C >= _SPLIT_MIN_ROWS)
 
@@ -550,7 +557,7 @@ class _ProjectedTripletAttention(torch.autograd.Function):
     parameters (w0, b0, w1, b1, ...), fused/unfused here with one launch each way."""
 
     @staticmethod
-    def forward(ctx, x, mask3, L, cd, table, dropout, graph_scale, *wb):
+    def forward(ctx, x, mask3, L, cd, table, dropout, graph_scale, no_backward, *wb):
         _dev(x, mask3)
         B, N = x.shape[0], x.shape[1]
         weight, bias = wb if table is None else _fuse_params(table, wb, cd)
@@ -577,8 +584,11 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             x2 = (x2 if x2.dtype == cd else x2.to(cd)).contiguous()
             w, b = _as_dtype(weight, cd).contiguous(), _as_dtype(bias, cd).contiguous()
             # the Q/K/V rows (written by the kernel, for the backward) and the narrow third-arm E/G projection as two tensors,
-            # as in the split-GEMM path below
-            fused = torch.empty(B, N, N, 6 * L.C, dtype=cd, device=x.device)
+            # as in the split-GEMM path below.  no_backward (torch.no_grad(), or no input requires grad): nothing will read
+            # those rows, so they are neither allocated nor written (TRI_NO_QKV_STORE: 2/3 of the kernel's bytes);
+            # TGT_TRI_PROJ_INFER=0 is the A/B knob
+            infer = _TRI_PROJ_INFER and no_backward
+            fused = None if infer else torch.empty(B, N, N, 6 * L.C, dtype=cd, device=x.device)
             we, be = w[6 * L.C:L.used], b[6 * L.C:L.used]
             if not L.biased:
                 eg = None                      # (axial: no third arm)
@@ -591,6 +601,8 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             _lib.check(_lib.lib().tgt_triplet_attention_proj_fwd(C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), _stream()),
                        'tgt_triplet_attention_proj_fwd')
             _prof_end('tgt_triplet_attention_proj_fwd', s0, s1)
+            if infer:
+                return out                 # (nothing to save: no backward exists)
             proj_skip = graph_scale        # (dropped graphs have NO Q/K/V rows: the backward must skip them too)
         elif _split_projection_ok(x, L):
             # two GEMMs: Q/K/V (6C = 1536 channels: six full 256-wide tile columns, 294 us) and the
@@ -637,7 +649,7 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         _call('tgt_triplet_attention_bwd', _lib.lib().tgt_triplet_attention_bwd, a)
         if _GATE_NODE_BWD == 1:
             _gate_record(d_fused.device)
-        need_p = any(ctx.needs_input_grad[7:])
+        need_p = any(ctx.needs_input_grad[8:])
         d2 = d_fused.view(-1, L.width)
         if kb:
             db = column_sum(d2) if need_p else None
@@ -664,12 +676,12 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             dx, dw, _ = _linear_backward(x2, w, d2, xs, xdt, torch.float32, None,
                                          ctx.needs_input_grad[0], need_p, False)
         if not need_p:
-            return (dx, None, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 7)
+            return (dx, None, None, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 8)
         if table is None:
-            return dx, None, None, None, None, None, None, _param_grad(dw, wdt), _param_grad(db, bdt)
+            return dx, None, None, None, None, None, None, None, _param_grad(dw, wdt), _param_grad(db, bdt)
         with _on_stream(ws):           # (the parameter gradients leave on the stream their weight gradient was computed on)
             grads = _unfuse_grads(table, params, dw, db)
-        return (dx, None, None, None, None, None, None, *grads)
+        return (dx, None, None, None, None, None, None, None, *grads)
 
 
 def projected_triplet_attention(x, weight, bias, mask3, layout, table=None, dropout=(0.0, 0), graph_scale=None):
@@ -681,7 +693,10 @@ def projected_triplet_attention(x, weight, bias, mask3, layout, table=None, drop
         return triplet_attention(linear(x, weight, bias), mask3, layout, dropout, graph_scale)
     cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
     wb = (weight, bias) if table is None else tuple(weight)
-    return _ProjectedTripletAttention.apply(x, mask3, layout, cd, table, dropout, graph_scale, *wb)
+    # (grad mode is always off INSIDE Function.forward and ctx.needs_input_grad ignores torch.no_grad(): whether a backward can
+    # follow is decided here)
+    no_backward = not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, *wb)))
+    return _ProjectedTripletAttention.apply(x, mask3, layout, cd, table, dropout, graph_scale, no_backward, *wb)
 
 
 # ---------------------------------------------------------------------------

@@ -105,6 +105,27 @@ def main():
                               graph_forwards_per_s=round(2 * S * B / dt, 1), n_gpus=1, data='synthetic',
                               gap_finite=bool(torch.isfinite(gap).all()), kernel_ms=kt)), flush=True)
 
+    if 'tgt_at' in a.only:
+        # (opt-in: --only tgt_at)  TGT-At 24L, the training benchmark's model, as a forward without autograd: eval mode, bf16
+        # autocast, 256 graphs of 32 nodes -- the forward whose triplet kernel leaves its Q/K/V stores out
+        # (TGT_TRI_PROJ_INFER=0 is the A/B knob; `knobs` in the line says which side ran)
+        from tgt_amd.knobs import K
+        from tgt_amd.pcqm import TGT_Multi
+        B = min(a.batch, 256)
+        model = TGT_Multi(**configs.tgt_at_24l(dropouts=False)).cuda().eval()
+        batch = device_batch(B, 32, 13, ragged=False)
+        prof = ops.profile_kernels(True, only=('tgt_triplet_attention_proj_fwd',), stride=3)
+
+        def fwd_at():
+            with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16):
+                model(batch)
+        dt = timed(fwd_at, 3, max(a.steps, 10))
+        ops.profile_kernels(False)
+        kt = {k: round(sum(v) / len(v), 4) for k, v in ops.kernel_times_ms(prof).items()}
+        print(json.dumps(dict(metric='graphs/sec forward, TGT-At 24L, bf16, batch 256, N = 32, no autograd', value=round(B / dt, 1),
+                              unit='graphs/s', ms_per_forward=round(dt * 1e3, 3), dtype='bf16', n_gpus=1, data='synthetic',
+                              launch='eager', kernel_ms=kt, knobs=K.non_default())), flush=True)
+
 
 if __name__ == '__main__':
     main()

@@ -82,6 +82,35 @@ def main():
             t = timeit(lambda: ops.projected_triplet_attention(x, w, bias, mask, L), a.iters)
         out['proj+tri_att_fwd'] = dict(ms=round(t, 4), fused=bool(ops._TRI_PROJ))
 
+    if 'projflag' in a.only:
+        # tgt_triplet_attention_proj_fwd itself (the C entry point, no host work around it) with the Q/K/V rows written (training)
+        # and without (TGT_TRI_NO_QKV_STORE: inference), alternating rounds in one process; algorithmic bytes = X once + O out
+        # (+ Q, K, V out): DESIGN.md section 4
+        import ctypes
+        import statistics
+        from tgt_amd import _lib
+        L = ops.TripletLayout(C, Ht)
+        x = torch.randn(B, N, N, C, device=dev, dtype=dt)
+        w = (torch.randn(L.width, C, device=dev) * C ** -0.5).to(dt)
+        bias = torch.randn(L.width, device=dev).to(dt)
+        eg = torch.addmm(bias[6 * C:], x.view(-1, C), w[6 * C:].t()).view(B, N, N, L.used - 6 * C)
+        o = torch.empty(B, N, N, 2 * C, device=dev, dtype=dt)
+        qkv = torch.empty(B, N, N, 6 * C, device=dev, dtype=dt)
+        args = {False: ops._tri_args(qkv, mask, o, L, eg=eg), True: ops._tri_args(None, mask, o, L, eg=eg)}
+        fn = _lib.lib().tgt_triplet_attention_proj_fwd
+
+        def run(flag):
+            _lib.check(fn(ctypes.byref(args[flag]), ops._ptr(x), C, ops._ptr(w), ops._ptr(bias), ops._stream()), 'tgt_triplet_attention_proj_fwd')
+        times = {False: [], True: []}
+        for _ in range(7):
+            for flag in (False, True):
+                times[flag].append(timeit(lambda: run(flag), a.iters))
+        nbytes = {False: B * n2 * (C + 2 * C + 6 * C) * esz, True: B * n2 * (C + 2 * C) * esz}
+        for flag, name in ((False, 'proj_fwd_store'), (True, 'proj_fwd_no_qkv_store')):
+            med = statistics.median(times[flag])
+            out[name] = dict(ms=round(med, 4), min=round(min(times[flag]), 4), max=round(max(times[flag]), 4),
+                             GBs=round(nbytes[flag] / med / 1e6, 1), rounds=[round(t, 4) for t in times[flag]])
+
     if not a.only or 'agg' in a.only:
         L = ops.AggregateLayout(C, Ht)
         fused = torch.randn(B, N, N, L.width, device=dev, dtype=dt).requires_grad_(True)
