@@ -188,10 +188,12 @@ int tgt_triangular_update_bwd(const void* e4, const void* v4, const float* mask,
  * Backward: the forward's vatt/lse/gsum, d_vatt (B,N,W), d_hhat (B,N,N,H, may be NULL) -> d_qkv (B,N,ld_qkv;
  * Q,K,V columns written), d_eg (B,N,N,ld_eg; E,G columns written).
  * Supported: any N, D <= 32, any H.  Kernel families behind the two entry points (one launch each way, chosen by shape; same results
- * up to the order of the softmax sums): 16-bit with D in {8,12,16} -- forward with H % 32 == 0: key-blocked, 64-byte pieces of the
- * E | G rows (csrc/node_attention_kb.hip); N <= 32, H % 8 == 0: one 32x32 tile per head (csrc/node_attention_mfma.hip);
- * 33 <= N <= 64, H % 8 == 0: 16-wide tiles (csrc/node_attention16.hip); everything else (fp32, other D / H, N > 64 backward):
- * one lane per head (csrc/node_attention.hip).
+ * up to the order of the softmax sums): 16-bit with D in {8,12,16} -- forward with H % 32 == 0, N <= 1024: key-blocked, 64-byte pieces
+ * of the E | G rows (csrc/node_attention_kb.hip); N <= 32, H % 8 == 0: one 32x32 tile per head (csrc/node_attention_mfma.hip);
+ * 33 <= N <= 64, H % 8 == 0: 16-wide tiles (csrc/node_attention16.hip); backward with 65 <= N <= 128, H % 8 == 0: key-blocked,
+ * from the saved lse / gsum / vatt, every sum in a fixed order (csrc/node_attention_kb_bwd.hip; TGT_NODE_KB_BWD=0 switches it off);
+ * everything else (fp32, other D / H, N > 64 forward with H % 32 != 0, N > 128 backward): one lane per head
+ * (csrc/node_attention.hip).  tgt_node_attention_family() tells which one a call takes.
  * ---------------------------------------------------------------------- */
 typedef struct tgt_node_attention_args {
     int32_t B, N, H, D;
@@ -220,6 +222,16 @@ typedef struct tgt_node_attention_args {
 
 int tgt_node_attention_fwd(const tgt_node_attention_args* a, void* stream);
 int tgt_node_attention_bwd(const tgt_node_attention_args* a, void* stream);
+/* The family tgt_node_attention_fwd (bwd == 0) / _bwd (bwd != 0) would launch for these arguments: the entry points route by this
+ * very function.  Host logic only -- sizes, dtype, offsets, pointer nullness and alignment; no pointer is dereferenced and the device
+ * is not touched.  Negative: the entry point would refuse the call (NULL args, bad sizes, missing tensors, a D / dtype no kernel takes). */
+enum { TGT_NODE_FAMILY_NONE = 0,      /* B == 0 or N == 0: nothing is launched */
+       TGT_NODE_FAMILY_LANE = 1,      /* one lane per head (csrc/node_attention.hip) */
+       TGT_NODE_FAMILY_MFMA32 = 2,    /* one 32x32 matrix-core tile per head (csrc/node_attention_mfma.hip) */
+       TGT_NODE_FAMILY_TILES16 = 3,   /* 16-wide tiles, whole key rows (csrc/node_attention16.hip) */
+       TGT_NODE_FAMILY_KB_FWD = 4,    /* key-blocked forward (csrc/node_attention_kb.hip) */
+       TGT_NODE_FAMILY_KB_BWD = 5 };  /* key-blocked backward, 65 <= N <= 128 (csrc/node_attention_kb_bwd.hip) */
+int tgt_node_attention_family(const tgt_node_attention_args* a, int bwd);
 
 /* ------------------------------------------------------------------------
  * Flat-buffer Adam step (replaces apex.optimizers.FusedAdam, reference

@@ -23,11 +23,13 @@ SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_w
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=9'], '.f32'), ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=2'], '.bf16'),
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=4'], '.f16'), 'triplet_aggregate.hip',
            ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=9'], '.f32'), ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=2'], '.bf16'),
-           ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=4'], '.f16'), 'node_attention.hip', 'node_attention_mfma.hip', 'node_attention16.hip', 'node_attention_kb.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip']
+           ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=4'], '.f16'), 'node_attention.hip', 'node_attention_mfma.hip', 'node_attention16.hip', 'node_attention_kb.hip', 'node_attention_kb_bwd.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip']
 ABI_VERSION = 32
 
 TGT_F32, TGT_BF16, TGT_F16 = 0, 1, 2
 TRI_BIASED, TRI_GATED, TRI_MASK_OUT = 1, 2, 4
+# tgt_node_attention_family(): the kernel family behind tgt_node_attention_fwd / _bwd for a call
+NODE_FAMILY_NONE, NODE_FAMILY_LANE, NODE_FAMILY_MFMA32, NODE_FAMILY_TILES16, NODE_FAMILY_KB_FWD, NODE_FAMILY_KB_BWD = range(6)
 TRI_NO_QKV_STORE = 8              # tgt_triplet_attention_proj_fwd only: the projected Q/K/V rows are not written
 
 _i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -122,6 +124,7 @@ SYMBOLS = {
     'tgt_triplet_aggregate_bwd': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp]),
     'tgt_node_attention_fwd': (C.c_int, [C.POINTER(NodeAttentionArgs), _vp]),
     'tgt_node_attention_bwd': (C.c_int, [C.POINTER(NodeAttentionArgs), _vp]),
+    'tgt_node_attention_family': (C.c_int, [C.POINTER(NodeAttentionArgs), _i32]),
     'tgt_triangular_update_fwd': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     'tgt_triangular_update_bwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     'tgt_gelu_dropout_fwd': (C.c_int, [_vp, _vp, _i64, _i32, _f32, C.c_uint64, _vp]),

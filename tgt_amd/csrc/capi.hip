@@ -26,6 +26,7 @@ int triplet_attention_run(const tgt_triplet_attention_args* a, bool bwd, hipStre
 int64_t tri_att_kb_workspace_bytes(const tgt_triplet_attention_args* a, int bwd);
 int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, bool bwd, hipStream_t st);
 int node_attention_run(const tgt_node_attention_args* a, bool bwd, hipStream_t st);
+int node_attention_family(const tgt_node_attention_args* a, bool bwd);
 int layer_norm_parts();
 int add_layer_norm_fwd_run(const void* x, int x_dtype, const void* res, int res_dtype, const float* scale,
                            int64_t rows_per_sample, void* s_out, const float* gamma, const float* beta, void* y,
@@ -116,6 +117,7 @@ int tgt_node_attention_fwd(const tgt_node_attention_args* a, void* stream) {
 int tgt_node_attention_bwd(const tgt_node_attention_args* a, void* stream) {
     return node_attention_run(a, true, reinterpret_cast<hipStream_t>(stream));
 }
+int tgt_node_attention_family(const tgt_node_attention_args* a, int bwd) { return node_attention_family(a, bwd != 0); }
 
 int tgt_triangular_update_fwd(const void* e4, const void* v4, const float* mask, void* out, int32_t B, int32_t N,
                               int32_t H, int32_t dtype, void* stream) {

@@ -629,6 +629,33 @@ int node_attention16_run(const tgt_node_attention_args& a, bool bwd, hipStream_t
 bool node_attention_kb_eligible(const tgt_node_attention_args& a, bool bwd);
 int node_attention_kb_run(const tgt_node_attention_args& a, bool bwd, hipStream_t st);
 
+// key-blocked backward for 65 <= N <= 128 (node_attention_kb_bwd.hip): H a multiple of 8
+bool node_attention_kb_bwd_eligible(const tgt_node_attention_args& a, bool bwd);
+int node_attention_kb_bwd_run(const tgt_node_attention_args& a, hipStream_t st);
+
+// Which family node_attention_run() launches for this call (TGT_NODE_FAMILY_*; negative: the call is refused).  Host logic on sizes,
+// dtype, offsets, pointer nullness and alignment only; node_attention_run() routes by it.
+int node_attention_family(const tgt_node_attention_args* a, bool bwd) {
+    if (!a || a->B < 0 || a->N < 0 || a->H <= 0) return -1;
+    if (a->B == 0 || a->N == 0) return TGT_NODE_FAMILY_NONE;
+    if (!a->qkv || !a->eg) return -1;
+    if (a->logits_only) {
+        if (!bwd && !a->hhat) return -1;
+    } else if (!a->mask || !a->lse || !a->gsum || !a->vatt) {
+        return -1;
+    }
+    if (bwd && (!a->d_qkv || !a->d_eg || (!a->logits_only && !a->d_vatt))) return -1;
+    if (node_attention_kb_eligible(*a, bwd)) return TGT_NODE_FAMILY_KB_FWD;          // forward, H % 32 == 0
+    if (node_attention_kb_bwd_eligible(*a, bwd)) return TGT_NODE_FAMILY_KB_BWD;      // backward, 65 <= N <= 128
+    if (node_attention16_eligible(*a, bwd)) return TGT_NODE_FAMILY_TILES16;          // N > 32 (every N <= 64 under TGT_NODE_MFMA16=2)
+    if (node_attention_mfma_eligible(*a, bwd)) return TGT_NODE_FAMILY_MFMA32;
+    if (a->dtype != TGT_F32 && a->dtype != TGT_BF16 && a->dtype != TGT_F16) return -1;
+    switch (a->D) {
+        case 4: case 8: case 12: case 16: case 24: case 32: return TGT_NODE_FAMILY_LANE;
+        default: return -1;
+    }
+}
+
 int node_attention_run(const tgt_node_attention_args* a, bool bwd, hipStream_t st) {
     if (!a) return set_error(TGT_ERR_INVALID, "node attention: null args");
     if (a->B < 0 || a->N < 0 || a->H <= 0) return set_error(TGT_ERR_INVALID, "node attention: bad sizes B=%d N=%d H=%d", a->B, a->N, a->H);
@@ -643,9 +670,13 @@ int node_attention_run(const tgt_node_attention_args* a, bool bwd, hipStream_t s
         if (!a->d_qkv || !a->d_eg) return set_error(TGT_ERR_INVALID, "node attention bwd: null d_qkv/d_eg");
         if (!a->logits_only && !a->d_vatt) return set_error(TGT_ERR_INVALID, "node attention bwd: null d_vatt");
     }
-    if (node_attention_kb_eligible(*a, bwd)) return node_attention_kb_run(*a, bwd, st);    // forward, H % 32 == 0
-    if (node_attention16_eligible(*a, bwd)) return node_attention16_run(*a, bwd, st);      // N > 32 (every N <= 64 under TGT_NODE_MFMA16=2)
-    if (node_attention_mfma_eligible(*a, bwd)) return node_attention_mfma_run(*a, bwd, st);
+    switch (node_attention_family(a, bwd)) {
+        case TGT_NODE_FAMILY_KB_FWD: return node_attention_kb_run(*a, bwd, st);
+        case TGT_NODE_FAMILY_KB_BWD: return node_attention_kb_bwd_run(*a, st);
+        case TGT_NODE_FAMILY_TILES16: return node_attention16_run(*a, bwd, st);
+        case TGT_NODE_FAMILY_MFMA32: return node_attention_mfma_run(*a, bwd, st);
+        default: break;                                    // lane-per-head, or a dtype / D it refuses below
+    }
     switch (a->dtype) {
         case TGT_F32: return dispatch_node_d<float>(*a, bwd, st);
         case TGT_BF16: return dispatch_node_d<bf16_t>(*a, bwd, st);

@@ -1,5 +1,6 @@
 // Shared pieces of the 16-wide-tile node attention kernels (node_attention16.hip: whole key rows per query block;
-// node_attention_kb.hip: key-blocked, all heads of a pair's 128-byte rows in one workgroup): operand fragments of
+// node_attention_kb.hip: key-blocked forward, all heads of a pair's 128-byte rows in one workgroup; node_attention_kb_bwd.hip: the
+// backward of 65..128 nodes, key chunks of 64): operand fragments of
 // v_mfma_f32_16x16x16, the 4 x 8 half-word transposes of the staging threads, 16-byte buffer accesses, the launch order.
 #pragma once
 #include "common.hpp"
@@ -118,6 +119,193 @@ __device__ __forceinline__ bool unit_of_block(int B, int per_graph, int& b, int&
     b = (t / per_graph) * 8 + x;
     sub = t % per_graph;
     return t < nt;
+}
+
+// ---- staging of the 8-heads-per-workgroup kernels (node_attention16.hip, node_attention_kb_bwd.hip): workgroup = 8 waves, wave = head
+constexpr int HG = 8, kThreads = HG * 64;
+
+struct Unit { int b, hg; };
+
+// ---- pair planes.  A staging task = (plane, query l, key quad mq): the 16-byte records of pairs (16 qb + l, m0 + 4 mq + i), i < 4
+// (m0: the first key of the staged key range; 0 where the planes hold every key).
+// `chan[plane]` = element offset of this head group's 8 channels inside a pair's row of the tensor (ld elements per pair).
+template <typename T, int NQ, int PLANES>
+struct PairIO {
+    static constexpr int NK = 16 * NQ, MQ = NK / 4, kPerPlane = 16 * MQ, kTasks = PLANES * kPerPlane;
+    static constexpr int kIters = (kTasks + kThreads - 1) / kThreads;
+    uint4 v[kIters][4];
+
+    __device__ __forceinline__ void issue(const void* x, int64_t ld, const int (&chan)[PLANES], int N, int b, int qb, int tid, int m0 = 0) {
+        asm volatile("" : "+v"(tid));            // (opaque: the task's addresses are recomputed here, not kept live across the query-block walk)
+        const __amdgpu_buffer_rsrc_t rs = graph_rsrc(x, (int64_t)N * N * ld * sizeof(T), b);
+#pragma unroll
+        for (int it = 0; it < kIters; ++it) {
+            const int task = it * kThreads + tid, plane = task / kPerPlane, r = task % kPerPlane, l = r / MQ, mq = r % MQ, q = 16 * qb + l;
+            int ch = chan[0];
+#pragma unroll
+            for (int p = 1; p < PLANES; ++p) ch = plane == p ? chan[p] : ch;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int m = m0 + 4 * mq + i;
+                const bool ok = x && task < kTasks && q < N && m < N;
+                v[it][i] = buf_ld16(rs, ok ? (uint32_t)(((int64_t)(q * N + m) * ld + ch) * (int64_t)sizeof(T)) : kOob);
+            }
+        }
+    }
+    template <int PITCH>
+    __device__ __forceinline__ void land(char* const (&planes)[PLANES], int tid) {
+        asm volatile("" : "+v"(tid));
+#pragma unroll
+        for (int it = 0; it < kIters; ++it) {
+            const int task = it * kThreads + tid, plane = task / kPerPlane, r = task % kPerPlane, l = r / MQ, mq = r % MQ;
+            char* base = planes[0];
+#pragma unroll
+            for (int p = 1; p < PLANES; ++p) base = plane == p ? planes[p] : base;
+            uint2 o[8];
+            tr4x8(v[it], o);
+            if (task < kTasks) lds_put8x8(base + l * PITCH + mq * 8, NK * 2, o);
+        }
+    }
+    // LDS planes -> the tensor
+    template <int PITCH>
+    static __device__ __forceinline__ void store(const char* const (&planes)[PLANES], void* x, int64_t ld, const int (&chan)[PLANES], int N, int b,
+                                                 int qb, int tid, int m0 = 0) {
+        asm volatile("" : "+v"(tid));            // (opaque: the task's addresses are recomputed here, not kept live across the query-block walk)
+        const __amdgpu_buffer_rsrc_t rs = graph_rsrc(x, (int64_t)N * N * ld * sizeof(T), b);
+#pragma unroll
+        for (int it = 0; it < kIters; ++it) {
+            const int task = it * kThreads + tid, plane = task / kPerPlane, r = task % kPerPlane, l = r / MQ, mq = r % MQ, q = 16 * qb + l;
+            const char* base = planes[0];
+            int ch = chan[0];
+#pragma unroll
+            for (int p = 1; p < PLANES; ++p) { base = plane == p ? planes[p] : base; ch = plane == p ? chan[p] : ch; }
+            if (task < kTasks) {
+                uint2 o[8];
+                lds_get8x8(base + l * PITCH + mq * 8, NK * 2, o);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int m = m0 + 4 * mq + i;
+                    const bool ok = q < N && m < N;
+                    buf_st16(rs, ok ? (uint32_t)(((int64_t)(q * N + m) * ld + ch) * (int64_t)sizeof(T)) : kOob, tr8x4_row(o, i));
+                }
+            }
+        }
+    }
+};
+
+// ---- node rows.  A staging task = (segment, row, d quad dq): the 16-byte (8 heads) records of (row, d = 4 dq + i), i < 4, of a
+// (B, N, ld) tensor whose row holds [d][H heads] from element `off[segment]`.  Segment s covers `rows[s]` rows from row0[s] into region[s].
+template <typename T, int D, int SEGS, int MAXROWS>
+struct NodeIO {
+    static constexpr int DQ = D / 4, kTasks = MAXROWS * DQ, kIters = (kTasks + kThreads - 1) / kThreads;
+    uint4 v[kIters][4];
+
+    static __device__ __forceinline__ void decode(int task, const int (&rows)[SEGS], int& seg, int& row, int& dq) {
+        int r = task / DQ;
+        dq = task % DQ;
+        seg = 0;
+#pragma unroll
+        for (int s = 0; s + 1 < SEGS; ++s)
+            if (seg == s && r >= rows[s]) { r -= rows[s]; seg = s + 1; }
+        row = r;
+    }
+    __device__ __forceinline__ void issue(const void* x, int64_t ld, const int (&off)[SEGS], const int (&rows)[SEGS], const int (&row0)[SEGS], int N,
+                                          int H, const Unit& u, int tid) {
+        asm volatile("" : "+v"(tid));            // (opaque: the task's addresses are recomputed here, not kept live across the query-block walk)
+        const __amdgpu_buffer_rsrc_t rs = graph_rsrc(x, (int64_t)N * ld * sizeof(T), u.b);
+#pragma unroll
+        for (int it = 0; it < kIters; ++it) {
+            int seg, row, dq;
+            decode(it * kThreads + tid, rows, seg, row, dq);
+            int o = off[0], r0 = row0[0], nr = rows[0];
+#pragma unroll
+            for (int s = 1; s < SEGS; ++s) { o = seg == s ? off[s] : o; r0 = seg == s ? row0[s] : r0; nr = seg == s ? rows[s] : nr; }
+            const bool ok = x && row < nr && r0 + row < N;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                v[it][i] = buf_ld16(rs, ok ? (uint32_t)(((int64_t)(r0 + row) * ld + o + (4 * dq + i) * H + u.hg * HG) * (int64_t)sizeof(T)) : kOob);
+        }
+    }
+    template <int PITCH>
+    __device__ __forceinline__ void land(char* const (&region)[SEGS], const int (&rows)[SEGS], int tid) {
+        asm volatile("" : "+v"(tid));
+#pragma unroll
+        for (int it = 0; it < kIters; ++it) {
+            int seg, row, dq;
+            decode(it * kThreads + tid, rows, seg, row, dq);
+            char* base = region[0];
+            int nr = rows[0];
+#pragma unroll
+            for (int s = 1; s < SEGS; ++s) { base = seg == s ? region[s] : base; nr = seg == s ? rows[s] : nr; }
+            uint2 o[8];
+            tr4x8(v[it], o);
+            if (row < nr) lds_put8x8(base + row * PITCH + dq * 8, D * 2, o);
+        }
+    }
+    template <int PITCH>
+    static __device__ __forceinline__ void store(const char* const (&region)[SEGS], void* x, int64_t ld, const int (&off)[SEGS], const int (&rows)[SEGS],
+                                                 const int (&row0)[SEGS], int N, int H, const Unit& u, int tid) {
+        asm volatile("" : "+v"(tid));            // (opaque: the task's addresses are recomputed here, not kept live across the query-block walk)
+        const __amdgpu_buffer_rsrc_t rs = graph_rsrc(x, (int64_t)N * ld * sizeof(T), u.b);
+#pragma unroll
+        for (int it = 0; it < kIters; ++it) {
+            int seg, row, dq;
+            decode(it * kThreads + tid, rows, seg, row, dq);
+            const char* base = region[0];
+            int o = off[0], r0 = row0[0], nr = rows[0];
+#pragma unroll
+            for (int s = 1; s < SEGS; ++s) {
+                base = seg == s ? region[s] : base; o = seg == s ? off[s] : o; r0 = seg == s ? row0[s] : r0; nr = seg == s ? rows[s] : nr;
+            }
+            if (row < nr) {
+                uint2 t[8];
+                lds_get8x8(base + row * PITCH + dq * 8, D * 2, t);
+                const bool ok = r0 + row < N;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    buf_st16(rs, ok ? (uint32_t)(((int64_t)(r0 + row) * ld + o + (4 * dq + i) * H + u.hg * HG) * (int64_t)sizeof(T)) : kOob,
+                             tr8x4_row(t, i));
+            }
+        }
+    }
+};
+
+// mask tile of the query block (keys from m0): pairs past N get -inf (weight exactly 0, gate sigmoid(-inf) = 0)
+template <int NQ, int PITCH>
+__device__ __forceinline__ void mask_load(char* lds_m, const tgt_node_attention_args& a, int b, int qb, int tid, int m0 = 0) {
+    constexpr int NK = 16 * NQ, MQ = NK / 4;
+    const int N = a.N;
+    asm volatile("" : "+v"(tid));
+    const __amdgpu_buffer_rsrc_t rs = graph_rsrc(a.mask, (int64_t)N * N * 4, b);
+    for (int task = tid; task < 16 * MQ; task += kThreads) {
+        const int l = task / MQ, mq = task % MQ, q = 16 * qb + l;
+        float mk[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int m = m0 + 4 * mq + i;
+            const bool ok = q < N && m < N;
+            const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, ok ? (q * N + m) * 4 : (int)kOob, 0, 0));
+            mk[i] = ok ? v : -INFINITY;
+        }
+        *reinterpret_cast<float4*>(lds_m + l * PITCH + mq * 16) = make_float4(mk[0], mk[1], mk[2], mk[3]);
+    }
+}
+
+// operand fragment of head hh from a node region: lane (x, g) holds X[row][d = 4g + t], t = 0..3 (0 past D)
+template <typename T, int D, int PITCH>
+__device__ __forceinline__ frag4_t<T> node_frag(const char* region, int row, int g, int hh) {
+    const int gg = 4 * g < D ? g : 0;
+    uint2 u = *reinterpret_cast<const uint2*>(region + row * PITCH + hh * (D * 2) + gg * 8);
+    if (4 * g >= D) u = make_uint2(0u, 0u);
+    frag4_t<T> f;
+    __builtin_memcpy(&f, &u, 8);
+    return f;
+}
+// transposed result X^T[d = 4g + q][row] into head hh of a node region
+template <typename T, int D, int PITCH>
+__device__ __forceinline__ void node_put(char* region, const f32x4& acc, int row, int g, int hh) {
+    const float v[4] = {acc[0], acc[1], acc[2], acc[3]};
+    if (4 * g < D) *reinterpret_cast<uint2*>(region + row * PITCH + hh * (D * 2) + g * 8) = pack4u<T>(v);
 }
 
 }  // namespace na16

@@ -45,6 +45,7 @@ _SPEC = {
     'wgrad_maxp': ('TGT_WGRAD_MAXP', 128, 'int', 'cap on the row chunks of a split-M weight gradient (in-step sweep 32..256: 128)'),
     'embed_gemm': ('TGT_EMBED_GEMM', True, 'flag', "per-node mul / bias tables of the Gaussian 3-D embedding without nn.Embedding's sort-based backward (a host read)"),
     'gate_node_bwd': ('TGT_GATE_NODE_BWD', 0, 'int', "the node side stream's backward chain of a layer waits for that layer's triplet backward kernel (1) / for the projection's data-gradient GEMM behind it (2)"),
+    'node_kb_bwd': ('TGT_NODE_KB_BWD', 1, 'int', 'node attention backward of 65..128 nodes on the key-blocked matrix-core kernel (0: the lane-per-head pair); the LIBRARY routes by the same variable, the host only words its slow-path notice by it'),
 }
 ENV_OF_LIBRARY = ('TGT_TRI_BWD2', 'TGT_TRI_BWD2_DMA', 'TGT_HIP_LIB', 'TGT_NODE_MFMA', 'TGT_NODE_MFMA16', 'TGT_NODE_KB', 'TGT_TUNING_FILE')
 
@@ -93,6 +94,7 @@ class Knobs:
     wgrad_maxp: int
     embed_gemm: bool
     gate_node_bwd: int
+    node_kb_bwd: int
 
     @classmethod
     def from_env(cls):

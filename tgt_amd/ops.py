@@ -32,6 +32,7 @@ _TRI_COLSUM = K.tri_colsum
 # finishing early the last round is still a round -- measured 0.474 vs 0.476 ms -- so by default it keeps computing every graph (the
 # forward, two workgroups per CU, gains 4 %)
 _TRI_SKIP_BWD = K.tri_skip == 2
+_NODE_KB_BWD = K.node_kb_bwd != 0       # (the library routes by the same variable; here it only words the slow-path notice)
 
 
 _PROFILE_ONLY = None     # names to time (None: every kernel that offers itself)
@@ -838,11 +839,20 @@ class _NodeAttention(torch.autograd.Function):
             eg = eg.to(qkv.dtype)
         B, N = qkv.shape[0], qkv.shape[1]
         a, W = _node_args(qkv, eg, mask3, H, scale_degree, False)
-        if B * N * N >= 65536 and (N > 64 or qkv.dtype == torch.float32 or H % 8 or (W // H) not in (8, 12, 16)):
-            why = 'N > 64' if N > 64 else 'fp32' if qkv.dtype == torch.float32 else 'heads not a multiple of 8' if H % 8 else 'head dim not in {8, 12, 16}'
-            # (N > 64 with H a multiple of 32, 16-bit: the FORWARD still runs the key-blocked matrix-core kernel, N <= 1024; only the backward
-            # is lane-per-head there)
-            which = 'the backward runs' if (why == 'N > 64' and H % 32 == 0 and N <= 1024 and (W // H) in (8, 12, 16)) else 'running'
+        D = W // H
+        tiles = qkv.dtype != torch.float32 and H % 8 == 0 and D in (8, 12, 16)       # the shapes the matrix-core families take at all
+        bwd_limit = 128 if _NODE_KB_BWD else 64                                      # (csrc/node_attention_kb_bwd.hip: 65 <= N <= 128)
+        if B * N * N >= 65536 and (N > bwd_limit or not tiles):
+            why = f'N > {bwd_limit}' if tiles else 'fp32' if qkv.dtype == torch.float32 else 'heads not a multiple of 8' if H % 8 else 'head dim not in {8, 12, 16}'
+            if tiles and H % 32 == 0 and N <= 1024:
+                # the FORWARD still runs the key-blocked matrix-core kernel (N <= 1024, H a multiple of 32); only the backward is lane-per-head
+                which = f"the backward's limit of {bwd_limit} nodes is passed, it runs"
+            elif tiles and H % 32 == 0:
+                which = f"the backward's limit of {bwd_limit} nodes and the forward's of 1024 are passed; running"
+            elif tiles:
+                which = f"the backward's limit of {bwd_limit} nodes is passed and the forward above 64 nodes needs heads a multiple of 32; running"
+            else:
+                which = 'running'
             _slow_path_notice(('node_mfma', why), f'node attention: the matrix-core kernels do not take this shape ({why}); {which} the lane-per-head '
                               'kernels (0.15-0.20 of HBM at N = 48 against 0.28-0.39; DESIGN.md section 4)')
         vatt = torch.empty(B, N, W, dtype=qkv.dtype, device=qkv.device)
