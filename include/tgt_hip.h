@@ -138,6 +138,16 @@ int tgt_triplet_attention_bwd(const tgt_triplet_attention_args* a, void* stream)
  * Supported: N <= 64 with D in {8,16,32}, and 65 <= N <= 128 with D = 16 (csrc/triplet_aggregate_kb.hip: no workspace; the
  * backward is two launches, dE / dG then dV, every sum in a fixed order).  The entry points check, before any launch: sizes
  * (TGT_ERR_INVALID), N > 128 and then D != 16 at N > 64 (TGT_ERR_UNSUPPORTED), then null / misaligned tensors (TGT_ERR_INVALID).
+ *
+ * tgt_triplet_aggregate_proj_fwd: the forward with the V projection fused in, for a call that NO backward follows
+ * (csrc/triplet_aggregate_proj.hip).  x: the LayerNorm'd edge rows (B,N,N,C); w (2C, C) and b (2C): the V projection in kernel
+ * order, rows [V_in | V_out], head-major (row dir*C + h*D + d), in the argument dtype.  V = w x + b is computed inside the kernel
+ * and never written to global memory: v / ld_v / v_off are not read (v may be NULL); eg / mask / out / dropout as above, and one
+ * seed drops the same (i, k, h) as tgt_triplet_aggregate_fwd.  eg[dir] may lie INSIDE out, in the columns [o_off[dir], o_off[dir] + C)
+ * of the same rows: the workgroup of a (graph, direction) reads all of its E/G before it writes its first O row, and it is the only
+ * writer of those columns.  Supported (tgt_triplet_aggregate_proj_supported, host only,
+ * 1 / 0): C = 256, D = 16, H = 16, N <= 32, bf16 / fp16.  Checks before any launch: sizes (TGT_ERR_INVALID), the supported
+ * predicate (TGT_ERR_UNSUPPORTED), then null / misaligned x / w / b / eg / mask / out, then e_off / g_off + H outside a row of ld_eg elements (TGT_ERR_INVALID).
  * ---------------------------------------------------------------------- */
 typedef struct tgt_triplet_aggregate_args {
     int32_t B, N, H, D;
@@ -159,6 +169,9 @@ typedef struct tgt_triplet_aggregate_args {
 
 int tgt_triplet_aggregate_fwd(const tgt_triplet_aggregate_args* a, void* stream);
 int tgt_triplet_aggregate_bwd(const tgt_triplet_aggregate_args* a, void* stream);
+int tgt_triplet_aggregate_proj_supported(const tgt_triplet_aggregate_args* a, int32_t C);
+int tgt_triplet_aggregate_proj_fwd(const tgt_triplet_aggregate_args* a, const void* x, int32_t C, const void* w, const void* b,
+                                   void* stream);
 
 /* ------------------------------------------------------------------------
  * TriangularUpdate core (reference lib/tgt/layers/triplet.py:156-172: the four

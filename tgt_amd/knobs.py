@@ -16,6 +16,7 @@ _SPEC = {
     'tri_split': ('TGT_TRI_SPLIT', True, 'flag', 'Q/K/V and E/G projected by two GEMMs (only without tri_proj)'),
     'tri_proj': ('TGT_TRI_PROJ', True, 'flag', 'Q/K/V projection inside the triplet forward kernel'),
     'tri_proj_infer': ('TGT_TRI_PROJ_INFER', True, 'flag', 'a projection-fused triplet forward that no backward follows does not write Q/K/V'),
+    'agg_proj_infer': ('TGT_AGG_PROJ_INFER', True, 'flag', 'a triplet aggregate forward that no backward follows projects V inside the kernel (tgt_triplet_aggregate_proj_fwd)'),
     'tri_colsum': ('TGT_TRI_COLSUM', True, 'flag', 'bias gradient of the fused projection from the backward kernel'),
     'tri_skip': ('TGT_TRI_SKIP', 1, 'int', 'triplet kernels skip DropPath-dropped graphs: 0 off, 1 forward, 2 backward too'),
     'defer_sums': ('TGT_DEFER_SUMS', False, 'flag', 'closing sums of the backward collected into one launch (measured slower)'),
@@ -65,6 +66,7 @@ class Knobs:
     tri_split: bool
     tri_proj: bool
     tri_proj_infer: bool
+    agg_proj_infer: bool
     tri_colsum: bool
     tri_skip: int
     defer_sums: bool

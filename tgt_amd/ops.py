@@ -26,6 +26,7 @@ _PROFILE = None
 _TRI_SPLIT = K.tri_split        # A/B knobs: tgt_amd/knobs.py reads the environment once; tests patch these names
 _TRI_PROJ = K.tri_proj
 _TRI_PROJ_INFER = K.tri_proj_infer
+_AGG_PROJ_INFER = K.agg_proj_infer
 _TRI_COLSUM = K.tri_colsum
 # graph_scale (DropPath-dropped graphs skipped by the triplet kernels) reaches the BACKWARD kernel only with TGT_TRI_SKIP=2: at the
 # BASELINE shapes the backward is 1024 workgroups in exactly four rounds on 256 CUs (one workgroup per CU), and with ~10 % of them
@@ -775,6 +776,70 @@ class _TripletAggregate(torch.autograd.Function):
 def triplet_aggregate(fused, mask3, layout, dropout=(0.0, 0)):
     """Reference arithmetic: lib/tgt/layers/triplet.py:56-70 / :107-123; dropout as triplet_attention."""
     return _TripletAggregate.apply(fused, mask3, layout, dropout)
+
+
+def _agg_proj_ok(x, N, L, cd):
+    """the projection-fused aggregate forward (tgt_triplet_aggregate_proj_fwd): the kernel's shape limits, an
+    unpadded fused row and enough edge rows for a grid of B x 2 workgroups (the gate of _proj_fused_ok)"""
+    return (x.is_cuda and N <= 32 and L.C == 256 and L.D == 16 and L.H == 16 and L.width == L.used and
+            cd in (torch.bfloat16, torch.float16) and x.numel() // L.C >= _SPLIT_MIN_ROWS)
+
+
+def _agg_proj_eg_view(out, L):
+    """where the narrow E/G rows of a fused call live: ne = used - 2C columns INSIDE `out`, ne / 2 on either side of the boundary
+    between the two directions' column blocks -- [E_in | G_in] are the last columns of the inward block, [E_out | G_out] the first of
+    the outward block.  A workgroup (graph, direction) of the kernel stages its direction's E/G before it writes its first O row,
+    and nobody else writes that direction's columns of the graph: no separate E/G tensor is needed."""
+    ne = L.used - 2 * L.C
+    c0 = L.C - ne // 2
+    return out.view(-1, 2 * L.C)[:, c0:c0 + ne], c0
+
+
+def _agg_proj_args(eg, mask3, out, L, dropout=(0.0, 0)):
+    """the argument block of tgt_triplet_aggregate_proj_fwd; V is NULL (it never exists in memory).  eg: (B,N,N,used - 2C), the
+    narrow E/G rows alone -- or `out` itself, when they were projected into _agg_proj_eg_view(out, L)"""
+    ne = L.used - 2 * L.C
+    ld, c0 = (2 * L.C, L.C - ne // 2) if eg is out else (ne, 0)
+    a = _agg_args(eg, mask3, out, L, dropout=dropout)
+    a.v = _pair(C.c_void_p, None, None)
+    a.ld_v, a.v_off = _pair(C.c_int64, 0, 0), _pair(C.c_int32, 0, 0)
+    a.ld_eg = _pair(C.c_int64, ld, ld)
+    a.e_off = _pair(C.c_int32, L.e[0] - 2 * L.C + c0, L.e[1] - 2 * L.C + c0)
+    a.g_off = _pair(C.c_int32, L.g[0] - 2 * L.C + c0, L.g[1] - 2 * L.C + c0) if L.gated else _pair(C.c_int32, 0, 0)
+    return a
+
+
+def projected_triplet_aggregate(x, params, mask3, layout, table, dropout=(0.0, 0)):
+    """triplet_aggregate(fused_linear(x, table, params), mask3, layout, dropout).  params: the module's nn.Linear parameters
+    (lin_V.weight, lin_V.bias, lin_E(G).weight, lin_E(G).bias).  A call that no backward can follow (torch.no_grad(), or nothing
+    requires grad) projects V inside the aggregate kernel where _agg_proj_ok holds: only the narrow E/G rows are projected
+    beforehand, into columns of the result itself, and no fused row is allocated (TGT_AGG_PROJ_INFER is the A/B knob)."""
+    L = layout
+    cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
+    # (whether a backward can follow is decided as in projected_triplet_attention)
+    no_backward = not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, *params)))
+    N = x.shape[1]
+    if not (no_backward and _AGG_PROJ_INFER and _agg_proj_ok(x, N, L, cd)):
+        return triplet_aggregate(fused_linear(x, table, params), mask3, L, dropout)
+    with torch.no_grad():
+        _dev(x, mask3)
+        B = x.shape[0]
+        w, b = _fuse_params(table, params, cd)
+        x2 = x.reshape(-1, L.C)
+        x2 = (x2 if x2.dtype == cd else x2.to(cd)).contiguous()
+        we, be = w[2 * L.C:L.used], b[2 * L.C:L.used]
+        out = torch.empty(B, N, N, 2 * L.C, dtype=cd, device=x.device)
+        egv, _ = _agg_proj_eg_view(out, L)                   # (the E/G rows wait inside `out` for the kernel: no tensor of their own)
+        if we.shape[0] <= 128 and _edge_kernel_ok(x2, we.shape[0], cd):
+            edge_linear_raw(x2, we, be.contiguous(), out=egv)
+        else:
+            torch.addmm(be, x2, we.t(), out=egv)
+        a = _agg_proj_args(out, mask3, out, L, dropout)
+        s0, s1 = _prof_begin('tgt_triplet_aggregate_proj_fwd')
+        _lib.check(_lib.lib().tgt_triplet_aggregate_proj_fwd(C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), _stream()),
+                   'tgt_triplet_aggregate_proj_fwd')
+        _prof_end('tgt_triplet_aggregate_proj_fwd', s0, s1)
+    return out
 
 
 # ---------------------------------------------------------------------------

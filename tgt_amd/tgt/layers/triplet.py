@@ -179,9 +179,9 @@ class TripletAggregate(_TripletBase):
         """forward_normed without lin_O (see TripletAttention.attend; the aggregate kernels compute every graph)"""
         B, N = x.shape[0], x.shape[1]
         lin_b = self.lin_EG if self.gated else self.lin_E
-        fused = ops.fused_linear(x, self._table, (self.lin_V.weight, self.lin_V.bias, lin_b.weight, lin_b.bias))
-        return ops.triplet_aggregate(fused, ops.as_mask3(mask, B, N), self._layout,
-                                     ops.draw_dropout(self.attention_dropout, self.training))
+        return ops.projected_triplet_aggregate(x, (self.lin_V.weight, self.lin_V.bias, lin_b.weight, lin_b.bias),
+                                               ops.as_mask3(mask, B, N), self._layout, self._table,
+                                               ops.draw_dropout(self.attention_dropout, self.training))
 
 
 class TripletAggregateUngated(TripletAggregate):

@@ -28,12 +28,15 @@ def timeit(fn, iters):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--B', type=int, default=256)
+    ap.add_argument('--B', type=int, default=None, help='graphs (default 256; --only aggproj: 512, the config-5 inference batch)')
     ap.add_argument('--N', type=int, default=32)
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--dtype', default='bf16')
     ap.add_argument('--only', default='')
     a = ap.parse_args()
+    rest = a.only.replace('aggproj', '')            # ('aggproj' names its own block only, not the 'agg' and 'proj' ones)
+    agg_b = a.B or 512
+    a.B = a.B or 256
     dt = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32}[a.dtype]
     esz = 4 if a.dtype == 'fp32' else 2
     B, N, C, Ht, W, Hn = a.B, a.N, 256, 16, 768, 64
@@ -72,7 +75,7 @@ def main():
         out['tricol'] = {k: round(sum(v[1:]) / max(1, len(v) - 1), 4) for k, v in ops.kernel_times_ms(prof).items()}
         del x, w, bias, g
 
-    if 'proj' in a.only:
+    if 'proj' in rest:
         # projection + attention forward as the training step runs it: fused kernel (TGT_TRI_PROJ=1, default) or GEMM + GEMM + attention
         L = ops.TripletLayout(C, Ht)
         x = torch.randn(B, N, N, C, device=dev, dtype=dt)
@@ -111,7 +114,7 @@ def main():
             out[name] = dict(ms=round(med, 4), min=round(min(times[flag]), 4), max=round(max(times[flag]), 4),
                              GBs=round(nbytes[flag] / med / 1e6, 1), rounds=[round(t, 4) for t in times[flag]])
 
-    if not a.only or 'agg' in a.only:
+    if not a.only or 'agg' in rest:
         L = ops.AggregateLayout(C, Ht)
         fused = torch.randn(B, N, N, L.width, device=dev, dtype=dt).requires_grad_(True)
         g = torch.randn(B, N, N, 2 * C, device=dev, dtype=dt)
@@ -122,6 +125,60 @@ def main():
         bb = B * (2 * (3 * n2 * C + 4 * n2 * Ht) * esz + n2 * 4)
         out['tri_agg_bwd'] = dict(ms=round(t2 - t, 4), GBs=round(bb / (t2 - t) / 1e6, 1))
         del fused, g
+
+    if 'aggproj' in a.only:
+        # tgt_triplet_aggregate_proj_fwd itself (the C entry point on pre-projected E/G rows, a.v = NULL) + the narrow E/G Linear it
+        # needs, against what it replaces: the library GEMM of the fused row [V_in | V_out | E | G] + tgt_triplet_aggregate_fwd.
+        # fp16 and bf16, 7 alternating rounds in one process; algorithmic bytes of both paths from the shapes
+        import ctypes
+        import statistics
+        from tgt_amd import _lib
+        Bp = agg_b
+        L = ops.AggregateLayout(C, Ht)
+        ne, rows = L.used - 2 * C, Bp * n2
+        maskp = torch.zeros(Bp, N, N, device=dev)
+        byts = dict(unfused=rows * (C + L.width + L.width + 2 * C) * 2, fused=rows * (C + ne + 2 * C + ne + 2 * C) * 2,
+                    kernel=rows * (2 * C + ne + 2 * C) * 2)
+        out['aggproj_bytes'] = dict(byts, B=Bp, N=N, H=Ht)
+        cases = {}
+        for name, dtp in (('fp16', torch.float16), ('bf16', torch.bfloat16)):
+            x = torch.randn(Bp, N, N, C, device=dev, dtype=dtp)
+            w = (torch.randn(L.width, C, device=dev) * C ** -0.5).to(dtp)
+            bias = torch.randn(L.width, device=dev).to(dtp)
+            x2, we, be = x.view(-1, C), w[2 * C:], bias[2 * C:].contiguous()
+            o = torch.empty(Bp, N, N, 2 * C, device=dev, dtype=dtp)
+            own_eg = ops._edge_kernel_ok(x2, ne, dtp)
+
+            egv, _ = ops._agg_proj_eg_view(o, L)                 # (as ops.projected_triplet_aggregate: E/G inside the result's own columns)
+
+            def narrow(x2=x2, we=we, be=be, own_eg=own_eg, egv=egv):
+                return ops.edge_linear_raw(x2, we, be, out=egv) if own_eg else torch.addmm(be, x2, we.t(), out=egv)
+            ap_ = ops._agg_proj_args(o, maskp, o, L)
+            fn = _lib.lib().tgt_triplet_aggregate_proj_fwd
+
+            def kernel(ap_=ap_, x=x, w=w, bias=bias):
+                _lib.check(fn(ctypes.byref(ap_), ops._ptr(x), C, ops._ptr(w), ops._ptr(bias), ops._stream()), 'tgt_triplet_aggregate_proj_fwd')
+
+            def fused(narrow=narrow, kernel=kernel):
+                narrow()
+                kernel()
+            narrow()                 # ('kernel' alone then runs on whatever the previous launch left in those columns: finite, same work)
+
+            def unfused(x2=x2, w=w, bias=bias, o=o):
+                f = torch.addmm(bias, x2, w.t()).view(Bp, N, N, L.width)
+                au = ops._agg_args(f, maskp, o, L)
+                _lib.check(_lib.lib().tgt_triplet_aggregate_fwd(ctypes.byref(au), ops._stream()), 'tgt_triplet_aggregate_fwd')
+            cases[name] = dict(kernel=kernel, fused=fused, unfused=unfused, keep=(x, w, bias, o))
+        times = {(n_, k): [] for n_ in cases for k in ('kernel', 'fused', 'unfused')}
+        for _ in range(7):
+            for key in times:
+                times[key].append(timeit(cases[key[0]][key[1]], a.iters))
+        for (n_, k), ts in times.items():
+            med = statistics.median(ts)
+            out[f'aggproj_{k}_{n_}'] = dict(ms=round(med, 4), min=round(min(ts), 4), max=round(max(ts), 4),
+                                           GBs=round(byts[k] / med / 1e6, 1), share_of_8TBs=round(byts[k] / med / 1e6 / 8000, 3),
+                                           rounds=[round(t, 4) for t in ts])
+        del cases
 
     if not a.only or 'node' in a.only:
         qkv = torch.randn(B, N, 3 * W, device=dev, dtype=dt).requires_grad_(True)
