@@ -125,6 +125,29 @@ int64_t tgt_triplet_attention_workspace_bytes(const tgt_triplet_attention_args* 
 int tgt_triplet_attention_fwd(const tgt_triplet_attention_args* a, void* stream);
 int tgt_triplet_attention_bwd(const tgt_triplet_attention_args* a, void* stream);
 
+/* Ragged batches: skip the padded nodes of every graph (N <= 64).  As tgt_triplet_attention_fwd / _bwd /
+ * tgt_triplet_attention_proj_fwd (below), plus node_counts: (B) int32 DEVICE memory, or NULL (= the entry point without
+ * _counts, which forwards here with NULL).  A workgroup walks the shared node j ("unit" j) of its graph; with
+ * n = clamp(node_counts[b], 0, N) the walk ends at n instead of N:
+ *   forward : rows out[b, :, j, :] of both directions are zeros for j >= n; the Q/K/V rows of those units are not read, and in the
+ *             projection-fused training forward they are not projected or written either (their qkv rows keep what the buffer held).
+ *             Everything with j < n is computed exactly as without counts (same strides, same dropout pattern: N keeps its role).
+ *   backward: d_out[b, :, j, :] for j >= n is NOT READ and taken as zero; the d_qkv rows of those units -- [:, j] (Q) and
+ *             [j, :] inward / [:, j] outward (K, V) -- get zeros; d_eg and the optional column sums get no contribution from them.
+ *             A backward must be given the counts its forward got.
+ * A count is a permission to skip, never an obligation.  It is exact when every key k >= n of the graph is closed by the mask
+ * (weight exactly 0) and the caller's loss ignores the padded columns (their cotangent is zero): the real block of `out` and all
+ * gradients are then bit-identical with and without counts.  graph_scale keeps its meaning and wins: a dropped graph is all zeros
+ * whatever its count.  The kernels clamp the count; no entry point reads it on the host (no synchronisation, capturable).
+ * N > 64 (key-blocked kernels): counts are accepted and ignored.  The aggregate and node attention families take no counts. */
+int tgt_triplet_attention_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, void* stream);
+int tgt_triplet_attention_bwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, void* stream);
+/* counts[b] = 1 + the largest j for which some i has an OPEN mask[b,i,j] (open: value > -FLT_MAX/2); 0 when every entry of the
+ * graph is closed.  mask: (B,N,N) float32 as the attention kernels take it; counts: (B) int32, both DEVICE memory.  For a
+ * prefix mask (nodes 0..n-1 real) this is n; for any other mask it is the largest count that is still safe.
+ * One small launch, no host synchronisation, capturable. */
+int tgt_mask_node_counts(const float* mask, int32_t B, int32_t N, int32_t* counts, void* stream);
+
 /* ------------------------------------------------------------------------
  * Triplet aggregate core (TripletAggregate / TripletAggregateUngated).
  * Replaces reference lib/tgt/layers/triplet.py:56-70 (gated; outward
@@ -476,6 +499,9 @@ int tgt_colsum(const void* x, int32_t x_dtype, int64_t rows, int32_t C, float* o
 int tgt_triplet_attention_proj_supported(const tgt_triplet_attention_args* a, int32_t C);
 int tgt_triplet_attention_proj_fwd(const tgt_triplet_attention_args* a, const void* x, int32_t C, const void* w,
                                    const void* bias, void* stream);
+/* the same with per-graph node counts (see tgt_triplet_attention_fwd_counts): the projection waves skip the padded units too */
+int tgt_triplet_attention_proj_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x, int32_t C,
+                                          const void* w, const void* bias, void* stream);
 
 /* Kernel-order parameters of a triplet module in one launch.  The reference holds the
  * projections as separate nn.Linear with head-minor channels (lib/tgt/layers/triplet.py:198-203,

@@ -117,6 +117,10 @@ SYMBOLS = {
     'tgt_abi_version': (C.c_int, []),
     'tgt_triplet_attention_fwd': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp]),
     'tgt_triplet_attention_bwd': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp]),
+    'tgt_triplet_attention_fwd_counts': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _vp]),
+    'tgt_triplet_attention_bwd_counts': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _vp]),
+    'tgt_triplet_attention_proj_fwd_counts': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _vp, _i32, _vp, _vp, _vp]),
+    'tgt_mask_node_counts': (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     'tgt_triplet_attention_workspace_bytes': (_i64, [C.POINTER(TripletAttentionArgs), _i32]),
     'tgt_triplet_attention_proj_supported': (C.c_int, [C.POINTER(TripletAttentionArgs), _i32]),
     'tgt_triplet_attention_proj_fwd': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _i32, _vp, _vp, _vp]),

@@ -22,7 +22,8 @@ int check_launch(const char* what) {
     return TGT_OK;
 }
 
-int triplet_attention_run(const tgt_triplet_attention_args* a, bool bwd, hipStream_t st);
+int triplet_attention_run(const tgt_triplet_attention_args* a, const int32_t* node_counts, bool bwd, hipStream_t st);
+int mask_node_counts_run(const float* mask, int B, int N, int32_t* counts, hipStream_t st);
 int64_t tri_att_kb_workspace_bytes(const tgt_triplet_attention_args* a, int bwd);
 int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, bool bwd, hipStream_t st);
 int node_attention_run(const tgt_node_attention_args* a, bool bwd, hipStream_t st);
@@ -48,8 +49,8 @@ int gelu_dropout_bwd_colsum_run(const void* x, const void* dy, void* out, int64_
                                 hipStream_t st);
 int gelu_colsum_parts();
 int triplet_attention_proj_supported(const tgt_triplet_attention_args* a, int C);
-int triplet_attention_proj_run(const tgt_triplet_attention_args* a, const void* x, int C, const void* w, const void* bias,
-                               hipStream_t st);
+int triplet_attention_proj_run(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x, int C, const void* w,
+                               const void* bias, hipStream_t st);
 int triplet_aggregate_proj_supported(const tgt_triplet_aggregate_args* a, int C);
 int triplet_aggregate_proj_run(const tgt_triplet_aggregate_args* a, const void* x, int C, const void* w, const void* bias,
                                hipStream_t st);
@@ -101,11 +102,16 @@ int tgt_set_seed_counter(const void* device_counter) {
     return TGT_OK;
 }
 
-int tgt_triplet_attention_fwd(const tgt_triplet_attention_args* a, void* stream) {
-    return triplet_attention_run(a, false, reinterpret_cast<hipStream_t>(stream));
+int tgt_triplet_attention_fwd(const tgt_triplet_attention_args* a, void* stream) { return tgt_triplet_attention_fwd_counts(a, nullptr, stream); }
+int tgt_triplet_attention_bwd(const tgt_triplet_attention_args* a, void* stream) { return tgt_triplet_attention_bwd_counts(a, nullptr, stream); }
+int tgt_triplet_attention_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, void* stream) {
+    return triplet_attention_run(a, node_counts, false, reinterpret_cast<hipStream_t>(stream));
 }
-int tgt_triplet_attention_bwd(const tgt_triplet_attention_args* a, void* stream) {
-    return triplet_attention_run(a, true, reinterpret_cast<hipStream_t>(stream));
+int tgt_triplet_attention_bwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, void* stream) {
+    return triplet_attention_run(a, node_counts, true, reinterpret_cast<hipStream_t>(stream));
+}
+int tgt_mask_node_counts(const float* mask, int32_t B, int32_t N, int32_t* counts, void* stream) {
+    return mask_node_counts_run(mask, B, N, counts, reinterpret_cast<hipStream_t>(stream));
 }
 int64_t tgt_triplet_attention_workspace_bytes(const tgt_triplet_attention_args* a, int32_t bwd) { return tri_att_kb_workspace_bytes(a, bwd); }
 int tgt_triplet_aggregate_fwd(const tgt_triplet_aggregate_args* a, void* stream) {
@@ -182,7 +188,11 @@ int tgt_layer_norm_parts(void) { return layer_norm_parts(); }
 int tgt_triplet_attention_proj_supported(const tgt_triplet_attention_args* a, int32_t C) { return triplet_attention_proj_supported(a, C); }
 int tgt_triplet_attention_proj_fwd(const tgt_triplet_attention_args* a, const void* x, int32_t C, const void* w, const void* bias,
                                    void* stream) {
-    return triplet_attention_proj_run(a, x, C, w, bias, reinterpret_cast<hipStream_t>(stream));
+    return tgt_triplet_attention_proj_fwd_counts(a, nullptr, x, C, w, bias, stream);
+}
+int tgt_triplet_attention_proj_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x, int32_t C,
+                                          const void* w, const void* bias, void* stream) {
+    return triplet_attention_proj_run(a, node_counts, x, C, w, bias, reinterpret_cast<hipStream_t>(stream));
 }
 int tgt_triplet_aggregate_proj_supported(const tgt_triplet_aggregate_args* a, int32_t C) { return triplet_aggregate_proj_supported(a, C); }
 int tgt_triplet_aggregate_proj_fwd(const tgt_triplet_aggregate_args* a, const void* x, int32_t C, const void* w, const void* b,

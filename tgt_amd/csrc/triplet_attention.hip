@@ -39,8 +39,8 @@ namespace tgt {
 // forward.  NT = node tiles of 32 (N <= 32*NT).  The workgroup makes one pass
 // per query tile `it`; inside a pass the key axis spans all NT tiles.
 // ---------------------------------------------------------------------------
-template <typename T, int D, int HG, int NT, int PF, bool DROP>
-__global__ void __launch_bounds__(HG * 64, (NT == 1 && sizeof(T) == 2) ? 4 : (sizeof(T) == 2 ? 2 : 1)) tri_att_fwd_kernel(const tgt_triplet_attention_args a) {
+template <typename T, int D, int HG, int NT, int PF, bool DROP, bool RG>
+__global__ void __launch_bounds__(HG * 64, (NT == 1 && sizeof(T) == 2) ? 4 : (sizeof(T) == 2 ? 2 : 1)) tri_att_fwd_kernel(const tgt_triplet_attention_args a, const int32_t* node_counts) {
     using G = TriGeo<T, D, HG>;
     using F = frag_t<T>;
     constexpr int KR = 32 * NT;
@@ -70,8 +70,10 @@ __global__ void __launch_bounds__(HG * 64, (NT == 1 && sizeof(T) == 2) ? 4 : (si
     const SlabBuf bO = {graph_rsrc(a.out, Nl * Nl * a.ld_out * sz, c.b), (uint32_t)(a.o_off[c.dir] * sz) + hch, (uint32_t)N * ldo_, ldo_};
 
     // a graph DropPath dropped (graph_scale[b] == 0): the residual add multiplies this branch by zero, so nothing is
-    // read or computed; the rows get the zeros that product would give (workgroup-uniform branch)
-    if (a.graph_scale && a.graph_scale[c.b] == 0.f) {
+    // read or computed; the rows get the zeros that product would give (workgroup-uniform branch).  The same for the
+    // units j >= n of a ragged batch (node_counts: padded nodes), after the walk over the n real ones.
+    const int n = tri_node_count<RG>(node_counts, c.b, N);
+    if ((a.graph_scale && a.graph_scale[c.b] == 0.f) || (RG && n == 0)) {
         for (int i0 = 0; i0 < N; i0 += 32)
             for (int j = 0; j < N; ++j) slab_store_zero<G, 32>(bO, j, i0, N, tid);
         return;
@@ -98,13 +100,13 @@ __global__ void __launch_bounds__(HG * 64, (NT == 1 && sizeof(T) == 2) ? 4 : (si
         slab_commit<G, 32>(pqA, smem, tid);
         slab_commit<G, KR>(pkA, smem + G::kSlabBytes, tid);
         slab_commit<G, KR>(pvA, smem + (1 + NT) * G::kSlabBytes, tid);
-        if (N > 1) {
+        if (n > 1) {
             slab_issue<G, 32>(pqA, bQ, 1, i0, N, tid);
             slab_issue<G, KR>(pkA, bK, 1, 0, N, tid);
             slab_issue<G, KR>(pvA, bV, 1, 0, N, tid);
         }
         if constexpr (PF > 1) {
-            if (N > 2) {
+            if (n > 2) {
                 slab_issue<G, 32>(pqB, bQ, 2, i0, N, tid);
                 slab_issue<G, KR>(pkB, bK, 2, 0, N, tid);
                 slab_issue<G, KR>(pvB, bV, 2, 0, N, tid);
@@ -122,13 +124,13 @@ __global__ void __launch_bounds__(HG * 64, (NT == 1 && sizeof(T) == 2) ? 4 : (si
             char* sQ = smem + (j & 1) * kSet;
             char* sK = sQ + G::kSlabBytes;
             char* sV = sK + NT * G::kSlabBytes;
-            if (j + 1 < N) {
+            if (j + 1 < n) {
                 char* nQ = smem + ((j + 1) & 1) * kSet;
                 slab_commit<G, 32>(pq, nQ, tid);
                 slab_commit<G, KR>(pk, nQ + G::kSlabBytes, tid);
                 slab_commit<G, KR>(pv, nQ + (1 + NT) * G::kSlabBytes, tid);
             }
-            if (j + 1 + PF < N) {
+            if (j + 1 + PF < n) {
                 slab_issue<G, 32>(pq, bQ, j + 1 + PF, i0, N, tid);
                 slab_issue<G, KR>(pk, bK, j + 1 + PF, 0, N, tid);
                 slab_issue<G, KR>(pv, bV, j + 1 + PF, 0, N, tid);
@@ -185,12 +187,14 @@ __global__ void __launch_bounds__(HG * 64, (NT == 1 && sizeof(T) == 2) ? 4 : (si
             __syncthreads();
             slab_store<G, 32>(sQ, bO, j, i0, N, tid);
         };
-        for (int j = 0; j < N; j += PF) {
+        for (int j = 0; j < n; j += PF) {
             step(j, pqA, pkA, pvA);
             if constexpr (PF > 1) {
-                if (j + 1 < N) step(j + 1, pqB, pkB, pvB);
+                if (j + 1 < n) step(j + 1, pqB, pkB, pvB);
             }
         }
+        if constexpr (RG)
+            for (int j = n; j < N; ++j) slab_store_zero<G, 32>(bO, j, i0, N, tid);
         __syncthreads();      // the next query-tile pass re-fills both sets
     }
 }
@@ -224,9 +228,9 @@ __device__ __forceinline__ unsigned long long probe_now() {
 
 // FL >= 0: the BIASED/GATED flags are compile-time (the hot gated+biased instantiation: no
 // per-element selects); FL < 0: read from the arguments.
-template <typename T, int D, int HG, int NT, int OCC, bool CS, int FL, bool DROP>
+template <typename T, int D, int HG, int NT, int OCC, bool CS, int FL, bool DROP, bool RG>
 // (waves_per_eu(1,1) for the one-wave variants: lets the allocator park values in the 256 AGPRs instead of scratch)
-__global__ void __launch_bounds__(HG * 64, OCC) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) tri_att_bwd_kernel(const tgt_triplet_attention_args a) {
+__global__ void __launch_bounds__(HG * 64, OCC) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) tri_att_bwd_kernel(const tgt_triplet_attention_args a, const int32_t* node_counts) {
     using G = TriGeo<T, D, HG>;
     using F = frag_t<T>;
     constexpr int KR = 32 * NT;
@@ -312,6 +316,9 @@ __global__ void __launch_bounds__(HG * 64, OCC) __attribute__((amdgpu_waves_per_
     for (int it = 0; it < NT; ++it) {
         const int i0 = 32 * it;
         if (i0 >= N) break;
+        // Units j >= n of a ragged batch (node_counts) are the dropped-graph case one unit at a time: their d_out rows are not
+        // read and taken as zero, their gradient rows get zeros.  (n = 0: no unit is read -- N0 -- or computed.)
+        const int n = tri_node_count<RG>(node_counts, c.b, N), N0 = (RG && n == 0) ? 0 : N;
         // The 32 x 32 tile of a wave is 16 values per lane; all element-wise arithmetic below runs on PAIRS (f32x2: v_pk_fma_f32 /
         // v_pk_mul_f32 / v_pk_add_f32 -- two results per VALU issue).  Written on scalars hipcc packed 28 of ~190 operations of
         // the j-loop; the loop is 2 waves per SIMD in lockstep behind one barrier per j, so its VALU phase is issue-bound.
@@ -339,17 +346,24 @@ __global__ void __launch_bounds__(HG * 64, OCC) __attribute__((amdgpu_waves_per_
         }
         __syncthreads();
 
+        for (int j = n; j < N; ++j) {      // padded units: zero gradient rows (ahead of the walk: nothing of it stays live through the walk)
+            slab_store_zero<G, 32>(gQ, j, i0, N, tid);
+            if (it == 0) {
+                slab_store_zero<G, KR>(dK, j, 0, N, tid);
+                slab_store_zero<G, KR>(dV, j, 0, N, tid);
+            }
+        }
         uint4 pq[SlabIO<G, 32>::kIters], po[SlabIO<G, 32>::kIters];
         uint4 pk[SlabIO<G, KR>::kIters], pv[SlabIO<G, KR>::kIters];
-        slab_issue<G, 32>(pq, bQ, 0, i0, N, tid);
-        slab_issue<G, 32>(po, dO, 0, i0, N, tid);
-        slab_issue<G, KR>(pk, bK, 0, 0, N, tid);
-        slab_issue<G, KR>(pv, bV, 0, 0, N, tid);
+        slab_issue<G, 32>(pq, bQ, 0, i0, N0, tid);
+        slab_issue<G, 32>(po, dO, 0, i0, N0, tid);
+        slab_issue<G, KR>(pk, bK, 0, 0, N0, tid);
+        slab_issue<G, KR>(pv, bV, 0, 0, N0, tid);
         slab_commit<G, 32>(pq, smem, tid);
         slab_commit<G, 32>(po, smem + G::kSlabBytes, tid);
         slab_commit<G, KR>(pk, smem + 2 * G::kSlabBytes, tid);
         slab_commit<G, KR>(pv, smem + (2 + NT) * G::kSlabBytes, tid);
-        if (N > 1) {
+        if (n > 1) {
             slab_issue<G, 32>(pq, bQ, 1, i0, N, tid);
             slab_issue<G, 32>(po, dO, 1, i0, N, tid);
             slab_issue<G, KR>(pk, bK, 1, 0, N, tid);
@@ -357,7 +371,7 @@ __global__ void __launch_bounds__(HG * 64, OCC) __attribute__((amdgpu_waves_per_
         }
         __syncthreads();
 
-        for (int j = 0; j < N; ++j) {
+        for (int j = 0; j < n; ++j) {
             if constexpr (DROP && NT > 1) {
                 // The two-tile dropout variants are the most register-starved instantiations, and hipcc
                 // (ROCm 7.2) miscompiled the spill of these loop-invariant fragments there (3 dwords to
@@ -373,7 +387,7 @@ __global__ void __launch_bounds__(HG * 64, OCC) __attribute__((amdgpu_waves_per_
             char* sK = sQ + 2 * G::kSlabBytes;
             char* sV = sK + NT * G::kSlabBytes;
             TGT_PROBE_T(0);                // (loop overhead + whatever the previous iteration left)
-            if (j + 1 < N) {
+            if (j + 1 < n) {
                 char* nQ = smem + ((j + 1) & 1) * kSet;
                 slab_commit<G, 32>(pq, nQ, tid);
                 slab_commit<G, 32>(po, nQ + G::kSlabBytes, tid);
@@ -381,7 +395,7 @@ __global__ void __launch_bounds__(HG * 64, OCC) __attribute__((amdgpu_waves_per_
                 slab_commit<G, KR>(pv, nQ + (2 + NT) * G::kSlabBytes, tid);
             }
             TGT_PROBE_T(1);                // commit: the wait for the prefetched slabs + 4 LDS writes
-            if (j + 2 < N && !(ablate & 1)) {
+            if (j + 2 < n && !(ablate & 1)) {
                 slab_issue<G, 32>(pq, bQ, j + 2, i0, N, tid);
                 slab_issue<G, 32>(po, dO, j + 2, i0, N, tid);
                 slab_issue<G, KR>(pk, bK, j + 2, 0, N, tid);
@@ -622,8 +636,9 @@ __global__ void __launch_bounds__(HG * 64, OCC) __attribute__((amdgpu_waves_per_
 #ifndef TGT_NT2_OCC
 #define TGT_NT2_OCC 1      // measured: capping the two-tile backward at 256 registers (2 waves per SIMD) spills -- 7.0 ms against 1.6 ms
 #endif
-template <typename T, int D, int HG, int NT>
-static int launch_tri_nt(const tgt_triplet_attention_args& a_in, bool bwd, hipStream_t st) {
+// RG: the instantiations with the count handling (nc != nullptr) or without it (triplet_common.hpp, tri_node_count)
+template <typename T, int D, int HG, int NT, bool RG>
+static int launch_tri_rg(const tgt_triplet_attention_args& a_in, const int32_t* nc, bool bwd, hipStream_t st) {
     using G = TriGeo<T, D, HG>;
 #ifdef TGT_PROBES
     tgt_triplet_attention_args a = a_in;
@@ -640,10 +655,10 @@ static int launch_tri_nt(const tgt_triplet_attention_args& a_in, bool bwd, hipSt
     if (!bwd) {
         // (a prefetch depth of 2 was measured neutral in round 1 and is gone)
         if (drop)
-            hipLaunchKernelGGL((tri_att_fwd_kernel<T, D, HG, NT, 1, true>), dim3(grid), dim3(G::kThreads), kFwdLds, st, a);
+            hipLaunchKernelGGL((tri_att_fwd_kernel<T, D, HG, NT, 1, true, RG>), dim3(grid), dim3(G::kThreads), kFwdLds, st, a, nc);
         else
-            hipLaunchKernelGGL((tri_att_fwd_kernel<T, D, HG, NT, 1, false>), dim3(grid), dim3(G::kThreads),
-                               kFwdLds, st, a);
+            hipLaunchKernelGGL((tri_att_fwd_kernel<T, D, HG, NT, 1, false, RG>), dim3(grid), dim3(G::kThreads),
+                               kFwdLds, st, a, nc);
     } else {
         // one node tile: registers capped for 2 waves per SIMD (kOcc)
         const bool cs = a.d_qkv_colsum[0] != nullptr;
@@ -652,56 +667,60 @@ static int launch_tri_nt(const tgt_triplet_attention_args& a_in, bool bwd, hipSt
         constexpr int kBG = TGT_TRI_BIASED | TGT_TRI_GATED;
         if (drop) {                 // attention dropout (p = 0 in every shipped config): one generic variant each
             if (cs)
-                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, true, -1, true>), dim3(grid), dim3(G::kThreads),
-                                   kBwdLds + kCs, st, a);
+                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, true, -1, true, RG>), dim3(grid), dim3(G::kThreads),
+                                   kBwdLds + kCs, st, a, nc);
             else
-                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, false, -1, true>), dim3(grid), dim3(G::kThreads),
-                                   kBwdLds, st, a);
+                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, false, -1, true, RG>), dim3(grid), dim3(G::kThreads),
+                                   kBwdLds, st, a, nc);
         } else if (NT == 1) {
             if (cs && HG == 8 && (a.flags & kBG) == kBG)         // the training hot path: flags compiled in
-                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, true, (HG == 8 ? kBG : -1), false>), dim3(grid),
-                                   dim3(G::kThreads), kBwdLds + kCs, st, a);
+                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, true, (HG == 8 ? kBG : -1), false, RG>), dim3(grid),
+                                   dim3(G::kThreads), kBwdLds + kCs, st, a, nc);
             else if (cs)
-                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, true, -1, false>), dim3(grid),
-                                   dim3(G::kThreads), kBwdLds + kCs, st, a);
+                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, true, -1, false, RG>), dim3(grid),
+                                   dim3(G::kThreads), kBwdLds + kCs, st, a, nc);
             else
-                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, false, -1, false>), dim3(grid),
-                                   dim3(G::kThreads), kBwdLds, st, a);
+                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, false, -1, false, RG>), dim3(grid),
+                                   dim3(G::kThreads), kBwdLds, st, a, nc);
         } else {
             // two node tiles (N in 33..64): TGT_NT2_OCC waves per SIMD (register cap 512 / TGT_NT2_OCC)
             constexpr int kOcc2 = NT == 2 ? TGT_NT2_OCC : 1;
             if (cs)
-                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc2, true, -1, false>), dim3(grid), dim3(G::kThreads),
-                                   kBwdLds + kCs, st, a);
+                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc2, true, -1, false, RG>), dim3(grid), dim3(G::kThreads),
+                                   kBwdLds + kCs, st, a, nc);
             else
-                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc2, false, -1, false>), dim3(grid), dim3(G::kThreads),
-                                   kBwdLds, st, a);
+                hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc2, false, -1, false, RG>), dim3(grid), dim3(G::kThreads),
+                                   kBwdLds, st, a, nc);
         }
     }
     return check_launch(bwd ? "tri_att_bwd_kernel" : "tri_att_fwd_kernel");
 }
+template <typename T, int D, int HG, int NT>
+static int launch_tri_nt(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) {
+    return nc ? launch_tri_rg<T, D, HG, NT, true>(a, nc, bwd, st) : launch_tri_rg<T, D, HG, NT, false>(a, nc, bwd, st);
+}
 template <typename T, int D, int HG>
-static int launch_tri(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) {
-    if (a.N <= 32) return launch_tri_nt<T, D, HG, 1>(a, bwd, st);
-    return launch_tri_nt<T, D, HG, 2>(a, bwd, st);
+static int launch_tri(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) {
+    if (a.N <= 32) return launch_tri_nt<T, D, HG, 1>(a, nc, bwd, st);
+    return launch_tri_nt<T, D, HG, 2>(a, nc, bwd, st);
 }
 
 template <typename T, int D>
-static int dispatch_hg(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) {
+static int dispatch_hg(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) {
     if constexpr (D == 16 && sizeof(T) == 2) {         // 8 heads per workgroup: 256-byte row pieces
-        if (a.H % 8 == 0 && a.N <= 32) return launch_tri_nt<T, D, 8, 1>(a, bwd, st);
+        if (a.H % 8 == 0 && a.N <= 32) return launch_tri_nt<T, D, 8, 1>(a, nc, bwd, st);
     }
-    if (a.H % 4 == 0) return launch_tri<T, D, 4>(a, bwd, st);
-    if constexpr (D * sizeof(T) >= 16) return launch_tri<T, D, 1>(a, bwd, st);
+    if (a.H % 4 == 0) return launch_tri<T, D, 4>(a, nc, bwd, st);
+    if constexpr (D * sizeof(T) >= 16) return launch_tri<T, D, 1>(a, nc, bwd, st);
     return set_error(TGT_ERR_UNSUPPORTED, "triplet attention: H=%d not a multiple of 4 with D=%d", a.H, D);
 }
 
 template <typename T>
-static int dispatch_d(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) {
+static int dispatch_d(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) {
     switch (a.D) {
-        case 8: return dispatch_hg<T, 8>(a, bwd, st);
-        case 16: return dispatch_hg<T, 16>(a, bwd, st);
-        case 32: return dispatch_hg<T, 32>(a, bwd, st);
+        case 8: return dispatch_hg<T, 8>(a, nc, bwd, st);
+        case 16: return dispatch_hg<T, 16>(a, nc, bwd, st);
+        case 32: return dispatch_hg<T, 32>(a, nc, bwd, st);
         default: return set_error(TGT_ERR_UNSUPPORTED, "triplet attention: D=%d not in {8,16,32}", a.D);
     }
 }
@@ -712,14 +731,14 @@ static int dispatch_d(const tgt_triplet_attention_args& a, bool bwd, hipStream_t
 #ifndef TGT_TRI_INST
 #define TGT_TRI_INST 15
 #endif
-int tri_att_run_f32(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st);
-int tri_att_run_bf16(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st);
-int tri_att_run_f16(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st);
+int tri_att_run_f32(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st);
+int tri_att_run_bf16(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st);
+int tri_att_run_f16(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st);
 #if TGT_TRI_INST & 1
-int tri_att_run_f32(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) { return dispatch_d<float>(a, bwd, st); }
+int tri_att_run_f32(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) { return dispatch_d<float>(a, nc, bwd, st); }
 #endif
 #if TGT_TRI_INST & 2
-int tri_att_run_bf16(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) { return dispatch_d<bf16_t>(a, bwd, st); }
+int tri_att_run_bf16(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) { return dispatch_d<bf16_t>(a, nc, bwd, st); }
 #ifdef TGT_PROBES
 }  // namespace tgt
 // probe build only: the segment cycle totals the last bf16 backward launch left (8 per workgroup, see TGT_PROBE_T)
@@ -730,19 +749,42 @@ namespace tgt {
 #endif
 #endif
 #if TGT_TRI_INST & 4
-int tri_att_run_f16(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) { return dispatch_d<f16_t>(a, bwd, st); }
+int tri_att_run_f16(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) { return dispatch_d<f16_t>(a, nc, bwd, st); }
 #endif
 
 #if TGT_TRI_INST & 8
 bool tri_att16_fwd_eligible(const tgt_triplet_attention_args& a);
-int tri_att16_fwd_run(const tgt_triplet_attention_args& a, hipStream_t st);
+int tri_att16_fwd_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st);
 bool tri_att16_bwd_eligible(const tgt_triplet_attention_args& a);
-int tri_att16_bwd_run(const tgt_triplet_attention_args& a, hipStream_t st);
+int tri_att16_bwd_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st);
 bool tri_att_bwd2_eligible(const tgt_triplet_attention_args& a);       // triplet_attention_bwd2.hip: 16-bit, D = 16, N <= 32, H % 8 == 0
-int tri_att_bwd2_run(const tgt_triplet_attention_args& a, hipStream_t st);
+int tri_att_bwd2_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st);
 int tri_att_kb_run(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st);      // triplet_attention_kb.hip: 65 <= N <= 128, D = 16
 
-int triplet_attention_run(const tgt_triplet_attention_args* a, bool bwd, hipStream_t st) {
+// tgt_mask_node_counts: one workgroup per graph; every thread keeps the largest j + 1 of the OPEN entries (value > -FLT_MAX/2)
+// it meets, the workgroup folds them with an LDS max
+__global__ void __launch_bounds__(256) mask_node_counts_kernel(const float* mask, int N, int32_t* counts) {
+    __shared__ int best;
+    if (threadIdx.x == 0) best = 0;
+    __syncthreads();
+    const float* m = mask + (int64_t)blockIdx.x * N * N;
+    int mine = 0;
+    for (int idx = threadIdx.x; idx < N * N; idx += 256)
+        if (m[idx] > -3.402823466e38f * 0.5f) mine = max(mine, idx % N + 1);
+    if (mine > 0) atomicMax(&best, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = best;
+}
+int mask_node_counts_run(const float* mask, int B, int N, int32_t* counts, hipStream_t st) {
+    if (B < 0 || N < 0 || N > 32768) return set_error(TGT_ERR_INVALID, "mask node counts: bad sizes B=%d N=%d", B, N);
+    if (B == 0) return TGT_OK;
+    if (!mask || !counts) return set_error(TGT_ERR_INVALID, "mask node counts: null tensor");
+    hipLaunchKernelGGL(mask_node_counts_kernel, dim3(B), dim3(256), 0, st, mask, N, counts);
+    return check_launch("mask_node_counts_kernel");
+}
+
+// nc: per-graph node counts (tgt_hip.h, the *_counts entry points) or nullptr; DEVICE memory, never read here
+int triplet_attention_run(const tgt_triplet_attention_args* a, const int32_t* nc, bool bwd, hipStream_t st) {
     if (!a) return set_error(TGT_ERR_INVALID, "triplet attention: null args");
 
     if (a->B < 0 || a->N < 0 || a->H <= 0) return set_error(TGT_ERR_INVALID, "triplet attention: bad sizes B=%d N=%d H=%d", a->B, a->N, a->H);
@@ -768,14 +810,14 @@ int triplet_attention_run(const tgt_triplet_attention_args* a, bool bwd, hipStre
             if ((a->flags & (TGT_TRI_BIASED | TGT_TRI_GATED)) && !a->d_eg[dir]) return set_error(TGT_ERR_INVALID, "triplet attention bwd: d_eg missing");
         }
     }
-    if (a->N > 64) return tri_att_kb_run(*a, bwd, st);                             // key-blocked kernels; checks D and the workspace before any launch
-    if (!bwd && tri_att16_fwd_eligible(*a)) return tri_att16_fwd_run(*a, st);      // 33 <= N <= 64: 16-wide tiles (triplet_attention16.hip)
-    if (bwd && tri_att16_bwd_eligible(*a)) return tri_att16_bwd_run(*a, st);
-    if (bwd && tri_att_bwd2_eligible(*a)) return tri_att_bwd2_run(*a, st);
+    if (a->N > 64) return tri_att_kb_run(*a, bwd, st);                             // key-blocked kernels; checks D and the workspace before any launch (node counts: ignored)
+    if (!bwd && tri_att16_fwd_eligible(*a)) return tri_att16_fwd_run(*a, nc, st);      // 33 <= N <= 64: 16-wide tiles (triplet_attention16.hip)
+    if (bwd && tri_att16_bwd_eligible(*a)) return tri_att16_bwd_run(*a, nc, st);
+    if (bwd && tri_att_bwd2_eligible(*a)) return tri_att_bwd2_run(*a, nc, st);
     switch (a->dtype) {
-        case TGT_F32: return tri_att_run_f32(*a, bwd, st);
-        case TGT_BF16: return tri_att_run_bf16(*a, bwd, st);
-        case TGT_F16: return tri_att_run_f16(*a, bwd, st);
+        case TGT_F32: return tri_att_run_f32(*a, nc, bwd, st);
+        case TGT_BF16: return tri_att_run_bf16(*a, nc, bwd, st);
+        case TGT_F16: return tri_att_run_f16(*a, nc, bwd, st);
         default: return set_error(TGT_ERR_INVALID, "triplet attention: bad dtype %d", a->dtype);
     }
 }

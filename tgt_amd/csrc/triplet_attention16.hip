@@ -110,8 +110,10 @@ struct Arm16 {
     static constexpr int kBytes = kOffM + R * kMPitch;
 };
 
-template <typename T, int HG, int NQ>
-__global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_triplet_attention_args a) {
+template <typename T, int HG, int NQ, typename... NC>
+__global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_triplet_attention_args a, NC... nc) {
+    constexpr bool RG = sizeof...(NC) > 0;          // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
+    const int32_t* node_counts = tri_counts_ptr(nc...);
     using G = Geo16<T, HG, NQ>;
     using A = Arm16<T, HG, NQ>;
     using F = frag4_t<T>;
@@ -126,8 +128,10 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_t
     const int dir = bid & 1, b = bid >> 1, N = a.N;
     const bool biased = (a.flags & TGT_TRI_BIASED) != 0, gated = (a.flags & TGT_TRI_GATED) != 0;
 
-    // a graph DropPath dropped (graph_scale[b] == 0, see tgt_hip.h): nothing is read or computed, its rows get zeros
-    if (a.graph_scale && a.graph_scale[b] == 0.f) {
+    // a graph DropPath dropped (graph_scale[b] == 0, see tgt_hip.h): nothing is read or computed, its rows get zeros; so do
+    // the units j >= n of a ragged batch (node_counts), after the walk over the n real ones
+    const int n = tri_node_count<RG>(node_counts, b, N);
+    if ((a.graph_scale && a.graph_scale[b] == 0.f) || (RG && n == 0)) {
         const int64_t sz0 = sizeof(T);
         const uint32_t ld0 = (uint32_t)(a.ld_out * sz0);
         const SlabBuf zO = {graph_rsrc(a.out, (int64_t)N * N * a.ld_out * sz0, b), (uint32_t)(a.o_off[dir] * sz0) + (uint32_t)(grp * HG * 16 * sz0),
@@ -191,7 +195,7 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_t
     slab_commit<G, R>(pq, smem, tid);
     slab_commit<G, R>(pk, smem + G::kSlabBytes, tid);
     slab_commit<G, R>(pv, smem + 2 * G::kSlabBytes, tid);
-    if (N > 1) {
+    if (n > 1) {
         slab_issue<G, R>(pq, bQ, 1, 0, N, tid);
         slab_issue<G, R>(pk, bK, 1, 0, N, tid);
         slab_issue<G, R>(pv, bV, 1, 0, N, tid);
@@ -201,17 +205,17 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_t
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     // one barrier per j: hazards as in triplet_attention.hip (the other set is rewritten at the top of the iteration by the
     // thread that last read those chunks; O goes into this wave's own rows / columns of the Q slab)
-    for (int j = 0; j < N; ++j) {
+    for (int j = 0; j < n; ++j) {
         char* sQ = smem + (j & 1) * kSet;
         char* sK = sQ + G::kSlabBytes;
         char* sV = sK + G::kSlabBytes;
-        if (j + 1 < N) {
+        if (j + 1 < n) {
             char* nQ = smem + ((j + 1) & 1) * kSet;
             slab_commit<G, R>(pq, nQ, tid);
             slab_commit<G, R>(pk, nQ + G::kSlabBytes, tid);
             slab_commit<G, R>(pv, nQ + 2 * G::kSlabBytes, tid);
         }
-        if (j + 2 < N) {
+        if (j + 2 < n) {
             slab_issue<G, R>(pq, bQ, j + 2, 0, N, tid);
             slab_issue<G, R>(pk, bK, j + 2, 0, N, tid);
             slab_issue<G, R>(pv, bV, j + 2, 0, N, tid);
@@ -259,6 +263,8 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_t
         __syncthreads();
         slab_store<G, R>(sQ, bO, j, 0, N, tid);
     }
+    if constexpr (RG)
+        for (int j = n; j < N; ++j) slab_store_zero<G, R>(bO, j, 0, N, tid);
 }
 
 // ---------------------------------------------------------------------------
@@ -273,8 +279,20 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_t
 // Stores, fused gradient row (ld_dqkv / ld_deg) and the in-kernel bias-gradient column sums as in triplet_attention.hip;
 // the per-thread column accumulators live in registers here (24 of them: this kernel has the room).
 // ---------------------------------------------------------------------------
-template <typename T, int HG, int NQ, bool CS>
-__global__ void __launch_bounds__(HG * NQ * 64) tri_att16_bwd_kernel(const tgt_triplet_attention_args a) {
+// zeros to the dQ / dK / dV rows of the units j0 .. N-1 (a dropped graph: all of them; a ragged one: its padded units)
+template <typename G, int R>
+__device__ __forceinline__ void zero_grad_rows(const SlabBuf& gQ, const SlabBuf& gK, const SlabBuf& gV, int j0, int N, int tid) {
+    for (int j = j0; j < N; ++j) {
+        slab_store_zero<G, R>(gQ, j, 0, N, tid);
+        slab_store_zero<G, R>(gK, j, 0, N, tid);
+        slab_store_zero<G, R>(gV, j, 0, N, tid);
+    }
+}
+
+template <typename T, int HG, int NQ, bool CS, typename... NC>
+__global__ void __launch_bounds__(HG * NQ * 64) tri_att16_bwd_kernel(const tgt_triplet_attention_args a, NC... nc) {
+    constexpr bool RG = sizeof...(NC) > 0;          // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
+    const int32_t* node_counts = tri_counts_ptr(nc...);
     using G = Geo16<T, HG, NQ>;
     using A = Arm16<T, HG, NQ>;
     using F = frag4_t<T>;
@@ -360,15 +378,15 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_bwd_kernel(const tgt_t
     // query block (lane = query, d = 4g + q), dK^T / dV^T of its key block (lane = key); lanes and blocks are summed after the walk
     f32x4 cq = {0.f, 0.f, 0.f, 0.f}, ck = {0.f, 0.f, 0.f, 0.f}, cv = {0.f, 0.f, 0.f, 0.f};
     // a graph DropPath dropped (graph_scale[b] == 0) receives an all-zero d_out: zeros to its gradient rows, nothing read or
-    // computed; dE / dG (zero-initialised above) and the column sums leave through the common tail below
+    // computed; dE / dG (zero-initialised above) and the column sums leave through the common tail below.  Ragged batches
+    // (node_counts): the walk ends at the graph's own n, and the units j >= n get those zero rows ahead of it (n = 0: every load of
+    // the walk is out of range).
     const bool dead = a.graph_scale && a.graph_scale[b] == 0.f;          // workgroup-uniform
     if (dead) {
-        for (int j = 0; j < N; ++j) {
-            slab_store_zero<G, R>(gQ, j, 0, N, tid);
-            slab_store_zero<G, R>(gK, j, 0, N, tid);
-            slab_store_zero<G, R>(gV, j, 0, N, tid);
-        }
+        zero_grad_rows<G, R>(gQ, gK, gV, 0, N, tid);
     } else {
+    const int n = tri_node_count<RG>(node_counts, b, N);
+    if constexpr (RG) zero_grad_rows<G, R>(gQ, gK, gV, n, N, tid);
     // Loads (round 4, as triplet_attention_bwd2.hip): buffer_load ... lds straight into set (step % 3), two steps ahead; each wave
     // owns two 1 KB pieces of a set (piece t = wave and wave + #waves of the 4 * kPieces pieces {Q | dO | K | V}); a lane's 16 bytes
     // land at physical chunk (row, slot'), i.e. it fetches slot' ^ swizzle(row) of the row (the LDS image keeps Geo16's layout);
@@ -394,7 +412,7 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_bwd_kernel(const tgt_t
         l_do[u] = slab == 1;
     }
     auto dma = [&](int jj, int set) {
-        const bool live = jj < N;
+        const bool live = jj < n;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const uint64_t base = l_do[u] ? do_base : src_base;
@@ -434,7 +452,7 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_bwd_kernel(const tgt_t
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     char* xw = smem + kOffX + (hw * NQ + qb) * kXWave;          // this wave's exchange blocks (phase 1)
     int cur = 0;
-    for (int j = 0; j < N; ++j) {
+    for (int j = 0; j < n; ++j) {
         char* sQ = smem + cur * kSet;
         char* sO = sQ + G::kSlabBytes;
         char* sK = sQ + 2 * G::kSlabBytes;
@@ -631,7 +649,7 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_bwd_kernel(const tgt_t
 }
 
 template <typename T, int HG, int NQ>
-static int launch_bwd(const tgt_triplet_attention_args& a, hipStream_t st) {
+static int launch_bwd(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
     using G = Geo16<T, HG, NQ>;
     constexpr int E = 16 / (int)sizeof(T);
     constexpr int kArm = Arm16<T, HG, NQ>::kBytes;
@@ -641,22 +659,22 @@ static int launch_bwd(const tgt_triplet_attention_args& a, hipStream_t st) {
     static_assert(kLds <= 160 * 1024, "LDS");
     const bool cs = a.d_qkv_colsum[0] != nullptr;
     const int grid = a.B * 2 * (a.H / HG);
-    if (cs) return launch_lds<tri_att16_bwd_kernel<T, HG, NQ, true>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a);
-    return launch_lds<tri_att16_bwd_kernel<T, HG, NQ, false>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a);
+    if (cs) return (nc ? launch_lds<tri_att16_bwd_kernel<T, HG, NQ, true, const int32_t*>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a, nc) : launch_lds<tri_att16_bwd_kernel<T, HG, NQ, true>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a));
+    return (nc ? launch_lds<tri_att16_bwd_kernel<T, HG, NQ, false, const int32_t*>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a, nc) : launch_lds<tri_att16_bwd_kernel<T, HG, NQ, false>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a));
 }
 
 template <typename T, int HG, int NQ>
-static int launch(const tgt_triplet_attention_args& a, hipStream_t st) {
+static int launch(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
     using G = Geo16<T, HG, NQ>;
     constexpr int kArm = Arm16<T, HG, NQ>::kBytes, kSlabs = 2 * 3 * G::kSlabBytes;
     constexpr int kLds = kArm > kSlabs ? kArm : kSlabs;
     static_assert(kLds <= 160 * 1024, "LDS");
-    return launch_lds<tri_att16_fwd_kernel<T, HG, NQ>>("tri_att16_fwd_kernel", dim3(a.B * 2 * (a.H / HG)), dim3(G::kThreads), kLds, st, a);
+    return (nc ? launch_lds<tri_att16_fwd_kernel<T, HG, NQ, const int32_t*>>("tri_att16_fwd_kernel", dim3(a.B * 2 * (a.H / HG)), dim3(G::kThreads), kLds, st, a, nc) : launch_lds<tri_att16_fwd_kernel<T, HG, NQ>>("tri_att16_fwd_kernel", dim3(a.B * 2 * (a.H / HG)), dim3(G::kThreads), kLds, st, a));
 }
 
 template <typename T>
-static int run(const tgt_triplet_attention_args& a, hipStream_t st) {
-    return a.N <= 48 ? launch<T, 4, 3>(a, st) : launch<T, 4, 4>(a, st);
+static int run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
+    return a.N <= 48 ? launch<T, 4, 3>(a, nc, st) : launch<T, 4, 4>(a, nc, st);
 }
 
 }  // namespace t16
@@ -668,18 +686,18 @@ bool tri_att16_bwd_eligible(const tgt_triplet_attention_args& a) {
     return (a.dtype == TGT_BF16 || a.dtype == TGT_F16) && a.D == 16 && ((a.N > 32 && a.N <= 48 && a.H % 4 == 0) || (a.N > 48 && a.N <= 64 && a.H % 2 == 0)) &&
            !(a.dropout_p > 0.f);
 }
-int tri_att16_bwd_run(const tgt_triplet_attention_args& a, hipStream_t st) {
+int tri_att16_bwd_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
     // four blocks: 2 heads x 4 waves (8 waves, up to 256 registers; 64-byte row pieces) -- 16 waves would leave 128 registers
-    if (a.N > 48) return a.dtype == TGT_BF16 ? t16::launch_bwd<bf16_t, 2, 4>(a, st) : t16::launch_bwd<f16_t, 2, 4>(a, st);
-    return a.dtype == TGT_BF16 ? t16::launch_bwd<bf16_t, 4, 3>(a, st) : t16::launch_bwd<f16_t, 4, 3>(a, st);
+    if (a.N > 48) return a.dtype == TGT_BF16 ? t16::launch_bwd<bf16_t, 2, 4>(a, nc, st) : t16::launch_bwd<f16_t, 2, 4>(a, nc, st);
+    return a.dtype == TGT_BF16 ? t16::launch_bwd<bf16_t, 4, 3>(a, nc, st) : t16::launch_bwd<f16_t, 4, 3>(a, nc, st);
 }
 
 // forward on 16-wide tiles: 16-bit, D = 16, 33 <= N <= 64, H a multiple of 4, no attention dropout
 bool tri_att16_fwd_eligible(const tgt_triplet_attention_args& a) {
     return (a.dtype == TGT_BF16 || a.dtype == TGT_F16) && a.D == 16 && a.N > 32 && a.N <= 64 && a.H % 4 == 0 && !(a.dropout_p > 0.f);
 }
-int tri_att16_fwd_run(const tgt_triplet_attention_args& a, hipStream_t st) {
-    return a.dtype == TGT_BF16 ? t16::run<bf16_t>(a, st) : t16::run<f16_t>(a, st);
+int tri_att16_fwd_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
+    return a.dtype == TGT_BF16 ? t16::run<bf16_t>(a, nc, st) : t16::run<f16_t>(a, nc, st);
 }
 
 }  // namespace tgt

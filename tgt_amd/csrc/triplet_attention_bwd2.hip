@@ -139,9 +139,23 @@ __device__ __forceinline__ void arm_store16(const ThirdArm& ta, void* d_eg, int 
     }
 }
 
+// zeros to the dQ / dK / dV rows of the units j0 .. N-1 (a dropped graph: all of them; a ragged one: its padded units);
+// wQ / wK: the thread's chunk of a Q-type / partner slab, out of range past N
+__device__ __forceinline__ void zero_grad_rows(__amdgpu_buffer_rsrc_t r_grd, uint32_t wQ, uint32_t wK, uint32_t qo, uint32_t ko, uint32_t vo,
+                                               uint32_t gQj, uint32_t gKj, int j0, int N) {
+    const u32x4_t z = {0, 0, 0, 0};
+    for (int j = j0; j < N; ++j) {
+        __builtin_amdgcn_raw_buffer_store_b128(z, r_grd, (int)wQ, (int)(qo + (uint32_t)j * gQj), TGT_ST_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(z, r_grd, (int)wK, (int)(ko + (uint32_t)j * gKj), TGT_ST_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(z, r_grd, (int)wK, (int)(vo + (uint32_t)j * gKj), TGT_ST_AUX);
+    }
+}
+
 // FL >= 0: BIASED / GATED compiled in (the training instantiation); FL < 0: read from the arguments
-template <typename T, bool CS, int FL, bool DMA>
-__global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) tri_att_bwd2_kernel(const tgt_triplet_attention_args a) {
+template <typename T, bool CS, int FL, bool DMA, typename... NC>
+__global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) tri_att_bwd2_kernel(const tgt_triplet_attention_args a, NC... nc) {
+    constexpr bool RG = sizeof...(NC) > 0;          // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
+    const int32_t* node_counts = tri_counts_ptr(nc...);
     using F = frag_t<T>;
     constexpr int kOffXch = Lay<DMA>::kOffXch, kOffPart = Lay<DMA>::kOffPart;
     using G = TriGeo<T, D, HG>;            // (third-arm staging only)
@@ -210,12 +224,7 @@ __global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_e
     // a graph DropPath dropped (graph_scale[b] == 0) receives an all-zero d_out: zeros to its gradient rows and column sums
     const bool dead = a.graph_scale && a.graph_scale[c.b] == 0.f;          // workgroup-uniform
     if (dead) {
-        const u32x4_t z = {0, 0, 0, 0};
-        for (int j = 0; j < N; ++j) {
-            __builtin_amdgcn_raw_buffer_store_b128(z, r_grd, (int)wQ, (int)(qo + (uint32_t)j * gQj), TGT_ST_AUX);
-            __builtin_amdgcn_raw_buffer_store_b128(z, r_grd, (int)wK, (int)(ko + (uint32_t)j * gKj), TGT_ST_AUX);
-            __builtin_amdgcn_raw_buffer_store_b128(z, r_grd, (int)wK, (int)(vo + (uint32_t)j * gKj), TGT_ST_AUX);
-        }
+        zero_grad_rows(r_grd, wQ, wK, qo, ko, vo, gQj, gKj, 0, N);
         const float zero16[16] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         arm_stage_put_grad<T, HG, 1>(smem, c.dir, wave, r, hi, 0, zero16, zero16);
         __syncthreads();
@@ -237,6 +246,10 @@ __global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_e
         return;
     }
 
+    // Ragged batches (node_counts): the walk ends at the graph's own n (n = 0: every load of it is out of range)
+    // The padded units get their zero rows AHEAD of the walk: older entries of the memory queue only make its counted waits conservative.
+    const int n = tri_node_count<RG>(node_counts, c.b, N);
+    if constexpr (RG) zero_grad_rows(r_grd, wQ, wK, qo, ko, vo, gQj, gKj, n, N);
     // third-arm tile of this head (accumulator layout), staged through LDS once (aliases the slab sets)
     f32x2 biasM[8], gate[8], dE[8], dG[8];
     arm_load16<T>(ta, c.b, c.dir, c.g, N, smem, tid);
@@ -287,7 +300,7 @@ __global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_e
     }
 
     auto issue = [&](u32x4_t (&pre)[4], int jj) {
-        const bool live = jj < N && !(ablate & 1);                      // (scalar: past the end every load is out of range)
+        const bool live = jj < n && !(ablate & 1);                      // (scalar: past the end every load is out of range)
         const __amdgpu_buffer_rsrc_t rs = live ? r_src : r_src0, ro = live ? r_do : r_do0;
         pre[0] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vQ, (int)(qo + (uint32_t)jj * sQj), TGT_LD_AUX);
         pre[1] = __builtin_amdgcn_raw_buffer_load_b128(ro, (int)vO, (int)(oo + (uint32_t)jj * oQj), TGT_LD_AUX);
@@ -308,7 +321,7 @@ __global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_e
     const uint64_t do_base = (uint64_t)(uintptr_t)a.d_out + (uint64_t)c.b * (uint64_t)(Nl * Nl * a.ld_out * 2);
     const uint32_t src_bytes = (uint32_t)(Nl * Nl * a.ld_qkv[c.dir] * 2), do_bytes = (uint32_t)(Nl * Nl * a.ld_out * 2);
     auto dma = [&](int jj, int set) {
-        const bool live = jj < N && !(ablate & 1);                      // (scalar: past the end every load is out of range)
+        const bool live = jj < n && !(ablate & 1);                      // (scalar: past the end every load is out of range)
         const u32x4_t rs = {(uint32_t)src_base, (uint32_t)(src_base >> 32) & 0xffffu, live ? src_bytes : 0u, 0x00020000u};
         const u32x4_t ro = {(uint32_t)do_base, (uint32_t)(do_base >> 32) & 0xffffu, live ? do_bytes : 0u, 0x00020000u};
         const uint32_t l0 = sbase + (uint32_t)(set * kSet + wave_u * 1024);
@@ -355,7 +368,7 @@ __global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_e
     }
 
     int cur = 0;
-    for (int j = 0; j < N; ++j) {
+    for (int j = 0; j < n; ++j) {
         if constexpr (DMA) {
             // set of step j + 2 = set of step j - 1: every wave finished reading it before the last barrier, and this thread's
             // loads write the chunks this thread itself read for the stores of step j - 1
@@ -560,7 +573,7 @@ __global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_e
 }
 
 template <typename T, bool CS, int FL>
-static int launch_one(const tgt_triplet_attention_args& a_in, hipStream_t st) {
+static int launch_one(const tgt_triplet_attention_args& a_in, const int32_t* nc, hipStream_t st) {
 #ifdef TGT_PROBES
     tgt_triplet_attention_args a = a_in;
     a._pad0 = getenv("TGT_TRI_BWD_ABLATE") ? atoi(getenv("TGT_TRI_BWD_ABLATE")) : 0;
@@ -569,16 +582,16 @@ static int launch_one(const tgt_triplet_attention_args& a_in, hipStream_t st) {
 #endif
     static const bool dma = !(getenv("TGT_TRI_BWD2_DMA") && atoi(getenv("TGT_TRI_BWD2_DMA")) == 0);       // A/B knob
     const dim3 grid(a.B * 2 * (a.H / HG));
-    if (dma) return launch_lds<tri_att_bwd2_kernel<T, CS, FL, true>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<true>::kLds, st, a);
-    return launch_lds<tri_att_bwd2_kernel<T, CS, FL, false>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<false>::kLds, st, a);
+    if (dma) return (nc ? launch_lds<tri_att_bwd2_kernel<T, CS, FL, true, const int32_t*>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<true>::kLds, st, a, nc) : launch_lds<tri_att_bwd2_kernel<T, CS, FL, true>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<true>::kLds, st, a));
+    return (nc ? launch_lds<tri_att_bwd2_kernel<T, CS, FL, false, const int32_t*>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<false>::kLds, st, a, nc) : launch_lds<tri_att_bwd2_kernel<T, CS, FL, false>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<false>::kLds, st, a));
 }
 template <typename T>
-static int launch(const tgt_triplet_attention_args& a, hipStream_t st) {
+static int launch(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
     constexpr int kBG = TGT_TRI_BIASED | TGT_TRI_GATED;
     const bool cs = a.d_qkv_colsum[0] != nullptr;
-    if (cs && (a.flags & kBG) == kBG) return launch_one<T, true, kBG>(a, st);
-    if (cs) return launch_one<T, true, -1>(a, st);
-    return launch_one<T, false, -1>(a, st);
+    if (cs && (a.flags & kBG) == kBG) return launch_one<T, true, kBG>(a, nc, st);
+    if (cs) return launch_one<T, true, -1>(a, nc, st);
+    return launch_one<T, false, -1>(a, nc, st);
 }
 
 }  // namespace bwd2
@@ -595,8 +608,8 @@ bool tri_att_bwd2_eligible(const tgt_triplet_attention_args& a) {
         }
     return true;
 }
-int tri_att_bwd2_run(const tgt_triplet_attention_args& a, hipStream_t st) {
-    return a.dtype == TGT_BF16 ? bwd2::launch<bf16_t>(a, st) : bwd2::launch<f16_t>(a, st);
+int tri_att_bwd2_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
+    return a.dtype == TGT_BF16 ? bwd2::launch<bf16_t>(a, nc, st) : bwd2::launch<f16_t>(a, nc, st);
 }
 
 }  // namespace tgt

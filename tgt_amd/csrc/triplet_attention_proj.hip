@@ -50,9 +50,20 @@ constexpr uint32_t kNone = 0xffffffffu;
 __device__ __forceinline__ int xoff(int row, int slot) { return row * kXPitch + (slot << 4); }
 }  // namespace proj2
 
-template <typename T, int DIR, bool STORE>
-__device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, const TriCtx& c, const T* x, const T* w,
-                                           char* smem, int tid) {
+// zeros to the O rows of the units j0 .. N-1 of this head group (threads 512-1023, the chunk map of store_step; the others go out
+// of range): a dropped graph (all units) and the padded units of a ragged one
+__device__ __forceinline__ void zero_o_rows(__amdgpu_buffer_rsrc_t r_out, int tid, int N, uint32_t o_row, uint32_t o_base, uint32_t o_j, int j0) {
+    const int srow = (tid & 511) >> 4, sslot = tid & 15;
+    const uint32_t vo = (srow < N && tid >= 512) ? (uint32_t)srow * o_row + o_base + (uint32_t)sslot * 16u : proj2::kNone;
+    for (int j = j0; j < N; ++j) {
+        u32x4_t z = {0, 0, 0, 0};
+        __builtin_amdgcn_raw_buffer_store_b128(z, r_out, (int)vo, (int)((uint32_t)j * o_j), TGT_ST_AUX);
+    }
+}
+
+template <typename T, int DIR, bool STORE, bool RG>
+__device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, const int32_t* node_counts, const TriCtx& c,
+                                           const T* x, const T* w, char* smem, int tid) {
     using namespace proj2;
     constexpr int D = 16, HG = 8;
     using G = TriGeo<T, D, HG>;
@@ -123,14 +134,11 @@ __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, 
     };
 
     // ---- a DropPath-dropped graph: zeros to the O rows, nothing else is read, computed or written (the backward of such a graph
-    //      gets a zero d_out and must be given graph_scale too: ops.py)
-    if (a.graph_scale && a.graph_scale[c.b] == 0.f) {
-        const int srow = (tid & 511) >> 4, sslot = tid & 15;
-        const uint32_t vo = (srow < N && tid >= 512) ? (uint32_t)srow * o_row + (uint32_t)(a.o_off[DIR] * sz) + hch + (uint32_t)sslot * 16u : kNone;
-        for (int j = 0; j < N; ++j) {
-            u32x4_t z = {0, 0, 0, 0};
-            __builtin_amdgcn_raw_buffer_store_b128(z, r_out, (int)vo, (int)((uint32_t)j * o_j), TGT_ST_AUX);
-        }
+    //      gets a zero d_out and must be given graph_scale too: ops.py).  Ragged batches (node_counts): both roles walk the n real
+    //      units only -- the padded ones are not loaded, projected or stored -- and the O rows of units j >= n get the same zeros.
+    const int n = tri_node_count<RG>(node_counts, c.b, N);
+    if ((a.graph_scale && a.graph_scale[c.b] == 0.f) || (RG && n == 0)) {
+        zero_o_rows(r_out, tid, N, o_row, (uint32_t)(a.o_off[DIR] * sz) + hch, o_j, 0);
         return;
     }
 
@@ -174,7 +182,7 @@ __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, 
         }
         uint4 px[kXIt];
         auto x_issue = [&](int jx) {                    // (jx >= N: out of range, zeros)
-            const bool live = jx < N && !(ablate & 1);
+            const bool live = jx < n && !(ablate & 1);
 #pragma unroll
             for (int it = 0; it < kXIt; ++it) {
                 const bool kvrows = DIR == 0 && it >= 2;
@@ -197,7 +205,7 @@ __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, 
         __syncthreads();                                // B2
         __syncthreads();                                // B3 (the projection waves produce step 0)
         if constexpr (STORE) store_step(0, true, 0, false);
-        for (int j = 0; j < N; ++j) {
+        for (int j = 0; j < n; ++j) {
             x_issue(j + 2);
             asm volatile("" ::: "memory");              // (the prefetch is issued HERE, a whole step ahead of its commit)
             if (!(ablate & 8)) {
@@ -233,7 +241,7 @@ __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, 
             }
             x_commit(j + 2);
             __syncthreads();                            // B_j
-            if constexpr (STORE) store_step(j + 1, j + 1 < N, j, true);
+            if constexpr (STORE) store_step(j + 1, j + 1 < n, j, true);
         }
     } else {
         // ------------------------------------------------------------------------------------------ projection role
@@ -308,17 +316,28 @@ __device__ __forceinline__ void proj2_walk(const tgt_triplet_attention_args& a, 
         project(0);
         __syncthreads();                                // B3
         if constexpr (STORE) store_step(0, true, 0, false);   // (no O rows yet)
-        for (int j = 0; j < N; ++j) {
-            if (j + 1 < N && !(ablate & 4)) project(j + 1);
+        for (int j = 0; j < n; ++j) {
+            if (j + 1 < n && !(ablate & 4)) project(j + 1);
             __syncthreads();                            // B_j
-            store_step(j + 1, j + 1 < N, j, true);
+            store_step(j + 1, j + 1 < n, j, true);
         }
+    }
+    if constexpr (RG) {
+        // The thread index goes through an opaque copy, as in store_step: given the plain one, hipcc computes the chunk offsets of
+        // these stores above the walk and keeps them next to the 96 weight registers of the projection role -- the with-counts
+        // instantiations then spill 34 (STORE = false) / 16-19 (STORE = true) vector registers instead of the 2 / 4 of the
+        // kernels without counts (.s metadata, both forms built).  It can go when that no longer happens.
+        int t_ = tid;
+        asm volatile("" : "+v"(t_));
+        zero_o_rows(r_out, t_, N, o_row, (uint32_t)(a.o_off[DIR] * sz) + hch, o_j, n);
     }
 }
 
-template <typename T, bool STORE>
-__global__ void __launch_bounds__(1024, 4) tri_att_proj_fwd_kernel(const tgt_triplet_attention_args a, const T* x, const T* w,
-                                                                   const T* bias) {
+template <typename T, bool STORE, typename... NC>
+__global__ void __launch_bounds__(1024, 4) tri_att_proj_fwd_kernel(const tgt_triplet_attention_args a, const T* x, const T* w, const T* bias,
+                                                                   NC... nc) {
+    constexpr bool RG = sizeof...(NC) > 0;          // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
+    const int32_t* node_counts = tri_counts_ptr(nc...);
     constexpr int D = 16, HG = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -332,12 +351,12 @@ __global__ void __launch_bounds__(1024, 4) tri_att_proj_fwd_kernel(const tgt_tri
         const int off = part == 0 ? a.q_off[dir] : (part == 1 ? a.k_off[dir] : a.v_off[dir]);
         reinterpret_cast<float*>(smem + proj2::kOffBias)[(wave & 7) * 48 + lane] = to_f32(bias[off + c.h * D + d]);
     }
-    if (dir == 0) proj2_walk<T, 0, STORE>(a, c, x, w, smem, tid);
-    else proj2_walk<T, 1, STORE>(a, c, x, w, smem, tid);
+    if (dir == 0) proj2_walk<T, 0, STORE, RG>(a, node_counts, c, x, w, smem, tid);
+    else proj2_walk<T, 1, STORE, RG>(a, node_counts, c, x, w, smem, tid);
 }
 
 template <typename T>
-static int launch_proj(const tgt_triplet_attention_args& a, const void* x, const void* w, const void* bias, hipStream_t st) {
+static int launch_proj(const tgt_triplet_attention_args& a, const int32_t* nc, const void* x, const void* w, const void* bias, hipStream_t st) {
     const int grid = a.B * 2 * (a.H / 8);
     static_assert(ArmStage<T, 8, 1>::kBytes <= proj2::kOffO, "arm stage must fit the aliased area");
 #ifdef TGT_PROBES
@@ -348,11 +367,14 @@ static int launch_proj(const tgt_triplet_attention_args& a, const void* x, const
     const tgt_triplet_attention_args& aa = a;          // (_pad1 is padding: never written, never read)
 #endif
     // (the store of the projected rows is a compile-time choice: the training instantiation is the kernel it always was)
+    // (... and so is the count handling: without counts, the RG = false instantiation has none of it)
+    const T *xp = reinterpret_cast<const T*>(x), *wp = reinterpret_cast<const T*>(w), *bp = reinterpret_cast<const T*>(bias);
+    const dim3 g(grid), blk(1024);
     if (a.flags & TGT_TRI_NO_QKV_STORE)
-        return launch_lds<tri_att_proj_fwd_kernel<T, false>>("tri_att_proj_fwd_kernel", dim3(grid), dim3(1024), proj2::kLds, st, aa,
-                                                             reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias));
-    return launch_lds<tri_att_proj_fwd_kernel<T, true>>("tri_att_proj_fwd_kernel", dim3(grid), dim3(1024), proj2::kLds, st, aa,
-                                                        reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias));
+        return nc ? launch_lds<tri_att_proj_fwd_kernel<T, false, const int32_t*>>("tri_att_proj_fwd_kernel", g, blk, proj2::kLds, st, aa, xp, wp, bp, nc)
+                  : launch_lds<tri_att_proj_fwd_kernel<T, false>>("tri_att_proj_fwd_kernel", g, blk, proj2::kLds, st, aa, xp, wp, bp);
+    return nc ? launch_lds<tri_att_proj_fwd_kernel<T, true, const int32_t*>>("tri_att_proj_fwd_kernel", g, blk, proj2::kLds, st, aa, xp, wp, bp, nc)
+              : launch_lds<tri_att_proj_fwd_kernel<T, true>>("tri_att_proj_fwd_kernel", g, blk, proj2::kLds, st, aa, xp, wp, bp);
 }
 
 int triplet_attention_proj_supported(const tgt_triplet_attention_args* a, int C) {
@@ -360,8 +382,8 @@ int triplet_attention_proj_supported(const tgt_triplet_attention_args* a, int C)
            C == 256;
 }
 
-int triplet_attention_proj_run(const tgt_triplet_attention_args* a, const void* x, int C, const void* w, const void* bias,
-                               hipStream_t st) {
+int triplet_attention_proj_run(const tgt_triplet_attention_args* a, const int32_t* nc, const void* x, int C, const void* w,
+                               const void* bias, hipStream_t st) {
     if (!a || !x || !w || !bias) return set_error(TGT_ERR_INVALID, "projected triplet attention: null argument");
     if (a->B < 0 || a->N < 0 || a->H <= 0) return set_error(TGT_ERR_INVALID, "projected triplet attention: bad sizes");
     if (a->B == 0 || a->N == 0) return TGT_OK;
@@ -380,7 +402,7 @@ int triplet_attention_proj_run(const tgt_triplet_attention_args* a, const void* 
         if ((a->flags & (TGT_TRI_BIASED | TGT_TRI_GATED)) && !a->eg[dir]) return set_error(TGT_ERR_INVALID, "projected triplet attention: eg missing");
     }
     if (((uintptr_t)x | (uintptr_t)w) % 16) return set_error(TGT_ERR_INVALID, "projected triplet attention: x / w must be 16-byte aligned");
-    return a->dtype == TGT_BF16 ? launch_proj<bf16_t>(*a, x, w, bias, st) : launch_proj<f16_t>(*a, x, w, bias, st);
+    return a->dtype == TGT_BF16 ? launch_proj<bf16_t>(*a, nc, x, w, bias, st) : launch_proj<f16_t>(*a, nc, x, w, bias, st);
 }
 
 }  // namespace tgt

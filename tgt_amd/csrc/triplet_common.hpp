@@ -88,6 +88,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t graph_rsrc(const void* tensor,
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(tensor)) + (int64_t)b * graph_bytes, 0,
                                              (int)graph_bytes, 0x00020000);
 }
+// (N is used as the ROW bound only -- never in an address: the backward passes 0 to issue a step that must read nothing)
 template <typename G, int ROWS, int IT = SlabIO<G, ROWS>::kIters>
 __device__ __forceinline__ void slab_issue(uint4 (&pre)[IT], const SlabBuf& s, int j, int row0, int N, int tid) {
     const uint32_t so = s.chan + (uint32_t)j * s.j_stride + (uint32_t)row0 * s.row_stride;
@@ -532,6 +533,23 @@ __device__ __forceinline__ TriCtx tri_ctx(const tgt_triplet_attention_args& a, i
     c.h = c.g * HG + wave;
     c.N = a.N;
     return c;
+}
+
+// Units j of graph b a triplet ATTENTION kernel computes (tgt_hip.h, tgt_triplet_attention_*_counts): clamp(node_counts[b], 0, N).
+// Units past it are not read or computed; their rows get the zeros a dropped graph gets.  Workgroup-uniform (b comes from
+// blockIdx): one scalar load.  N keeps every stride, row bound and dropout unit index.
+// RG (ragged) is a compile-time flag of every kernel that takes counts: a call without counts launches the RG = false
+// instantiation, where n IS N and all of the count handling folds away -- the instruction streams of the kernels every caller
+// without counts runs are the ones they were before the counts existed (hipcc's register allocation of these kernels moves with
+// any added live scalar: profiles/tri_ragged_ab.txt).  Where even an unused kernel ARGUMENT moved the allocation (a longer
+// argument segment lets hipcc widen its scalar loads), the counts are a trailing parameter pack `NC... nc`: empty without counts,
+// so that instantiation has the argument list it always had; `const int32_t*` with them.
+__device__ __forceinline__ const int32_t* tri_counts_ptr() { return nullptr; }
+__device__ __forceinline__ const int32_t* tri_counts_ptr(const int32_t* p) { return p; }
+template <bool RG>
+__device__ __forceinline__ int tri_node_count(const int32_t* node_counts, int b, int N) {
+    if constexpr (RG) return min(max(node_counts[b], 0), N);
+    else return N;
 }
 
 __device__ __forceinline__ ThirdArm tri_third_arm(const tgt_triplet_attention_args& a, int dir) {

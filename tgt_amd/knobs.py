@@ -19,6 +19,7 @@ _SPEC = {
     'agg_proj_infer': ('TGT_AGG_PROJ_INFER', True, 'flag', 'a triplet aggregate forward that no backward follows projects V inside the kernel (tgt_triplet_aggregate_proj_fwd)'),
     'tri_colsum': ('TGT_TRI_COLSUM', True, 'flag', 'bias gradient of the fused projection from the backward kernel'),
     'tri_skip': ('TGT_TRI_SKIP', 1, 'int', 'triplet kernels skip DropPath-dropped graphs: 0 off, 1 forward, 2 backward too'),
+    'tri_ragged': ('TGT_TRI_RAGGED', False, 'flag', 'triplet attention skips the padded nodes of every graph (N <= 64): per-graph node counts from the mask, once per forward; padded positions of the edge stream then hold other finite values'),
     'defer_sums': ('TGT_DEFER_SUMS', False, 'flag', 'closing sums of the backward collected into one launch (measured slower)'),
     'defer_max': ('TGT_DEFER_MAX', 56, 'int', 'sums per queue before it flushes itself'),
     'epi_ln_bwd': ('TGT_EPI_LN_BWD', True, 'flag', 'LayerNorm backward as the epilogue of the data-gradient GEMM'),
@@ -69,6 +70,7 @@ class Knobs:
     agg_proj_infer: bool
     tri_colsum: bool
     tri_skip: int
+    tri_ragged: bool
     defer_sums: bool
     defer_max: int
     epi_ln_bwd: bool

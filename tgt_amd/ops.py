@@ -105,6 +105,35 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _check_node_counts(node_counts, B):
+    """per-graph node counts of the triplet attention kernels (tgt_hip.h, tgt_triplet_attention_fwd_counts): checked like
+    graph_scale; the values stay on the device (the kernels clamp them)"""
+    if node_counts is not None and (node_counts.dtype != torch.int32 or node_counts.numel() != B or not node_counts.is_contiguous() or
+                                    not node_counts.is_cuda):
+        raise RuntimeError('triplet attention: node_counts must be a contiguous int32 device tensor with one value per graph')
+    return node_counts
+
+
+def _call_counts(name, args, node_counts):
+    """tgt_triplet_attention_fwd / _bwd (`name`), through the _counts entry point when node counts are given"""
+    if node_counts is None:
+        return _call(name, getattr(_lib.lib(), name), args)
+    fn = getattr(_lib.lib(), name + '_counts')
+    _call(name, lambda a, st: fn(a, _ptr(node_counts), st), args)
+
+
+def mask_node_counts(mask3):
+    """(B,N,N) float32 additive mask -> (B,) int32 on the device: 1 + the largest column j with an open entry (value >
+    finfo.min / 2) in some row, 0 for a graph with none -- num_nodes for the collate's prefix masks, and for any other mask the
+    largest count the triplet attention kernels may still skip behind.  One launch, no host synchronisation."""
+    _dev(mask3)
+    if mask3.dim() != 3 or mask3.shape[1] != mask3.shape[2] or mask3.dtype != torch.float32 or not mask3.is_contiguous():
+        raise RuntimeError('mask_node_counts: expects a contiguous float32 (B,N,N) mask')
+    counts = torch.empty(mask3.shape[0], dtype=torch.int32, device=mask3.device)
+    _lib.check(_lib.lib().tgt_mask_node_counts(_ptr(mask3), mask3.shape[0], mask3.shape[1], _ptr(counts), _stream()), 'tgt_mask_node_counts')
+    return counts
+
+
 def _pair(cls, a, b):
     return (cls * 2)(a, b)
 
@@ -262,16 +291,17 @@ def draw_dropout(p, training):
 
 class _TripletAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, fused, mask3, L, dropout=(0.0, 0), graph_scale=None):
+    def forward(ctx, fused, mask3, L, dropout=(0.0, 0), graph_scale=None, node_counts=None):
         _dev(fused, mask3)
         fused = fused.contiguous()
         B, N = fused.shape[0], fused.shape[1]
         assert fused.shape == (B, N, N, L.width), (fused.shape, L.width)
         out = torch.empty(B, N, N, 2 * L.C, dtype=fused.dtype, device=fused.device)
         a = _tri_args(fused, mask3, out, L, dropout=dropout, graph_scale=graph_scale)
-        _call('tgt_triplet_attention_fwd', _lib.lib().tgt_triplet_attention_fwd, a)
+        _call_counts('tgt_triplet_attention_fwd', a, _check_node_counts(node_counts, B))
         ctx.save_for_backward(fused, mask3, out)
         ctx.L, ctx.dropout, ctx.graph_scale = L, dropout, (graph_scale if _TRI_SKIP_BWD else None)
+        ctx.node_counts = node_counts          # (the backward must skip what the forward skipped)
         return out
 
     @staticmethod
@@ -282,19 +312,22 @@ class _TripletAttention(torch.autograd.Function):
         if ctx.L.width > ctx.L.used:
             d_fused[..., ctx.L.used:] = 0
         a = _tri_args(fused, mask3, out, ctx.L, d_out, d_fused, dropout=ctx.dropout, graph_scale=ctx.graph_scale)
-        _call('tgt_triplet_attention_bwd', _lib.lib().tgt_triplet_attention_bwd, a)
-        return d_fused, None, None, None, None
+        _call_counts('tgt_triplet_attention_bwd', a, ctx.node_counts)
+        return d_fused, None, None, None, None, None
 
 
-def triplet_attention(fused, mask3, layout, dropout=(0.0, 0), graph_scale=None):
+def triplet_attention(fused, mask3, layout, dropout=(0.0, 0), graph_scale=None, node_counts=None):
     """fused: (B,N,N,layout.width) fused projections (head-major Q/K/V), mask3:
     (B,N,N) float32.  Returns Va (B,N,N,2C) with channel = dir*C + h*D + d.
     dropout: (p, seed) of the attention dropout on the gated weights (draw_dropout).
     graph_scale (B,) float32: the DropPath factor of the residual branch the result feeds (drawn by the caller, applied by
     the caller): graphs whose factor is exactly 0 are skipped -- zeros out, zero gradients -- which equals computing them
     and multiplying by that zero (the incoming gradient of such a graph MUST be zero, as it is behind that multiplication).
+    node_counts (B,) int32 on the device (mask_node_counts): ragged batches, N <= 64 -- the columns j >= node_counts[b] of a
+    graph are not read or computed: Va[b, :, j] is zeros there and the incoming gradient of those columns is NOT READ and taken as
+    zero (exact when the mask closes every key past the count and the loss ignores the padded columns).  N > 64: ignored.
     Reference arithmetic: lib/tgt/layers/triplet.py:213-246."""
-    return _TripletAttention.apply(fused, mask3, layout, dropout, graph_scale)
+    return _TripletAttention.apply(fused, mask3, layout, dropout, graph_scale, node_counts)
 
 
 def _colsum_workspace(B, width, used, device):
@@ -559,9 +592,10 @@ class _ProjectedTripletAttention(torch.autograd.Function):
     parameters (w0, b0, w1, b1, ...), fused/unfused here with one launch each way."""
 
     @staticmethod
-    def forward(ctx, x, mask3, L, cd, table, dropout, graph_scale, no_backward, *wb):
+    def forward(ctx, x, mask3, L, cd, table, dropout, graph_scale, no_backward, node_counts, *wb):
         _dev(x, mask3)
         B, N = x.shape[0], x.shape[1]
+        _check_node_counts(node_counts, B)
         weight, bias = wb if table is None else _fuse_params(table, wb, cd)
         out = torch.empty(B, N, N, 2 * L.C, dtype=cd, device=x.device)
         eg = None
@@ -600,8 +634,12 @@ class _ProjectedTripletAttention(torch.autograd.Function):
                 eg = torch.addmm(be, x2, we.t()).view(B, N, N, L.used - 6 * L.C)
             a = _tri_args(fused, mask3, out, L, eg=eg, graph_scale=graph_scale)
             s0, s1 = _prof_begin('tgt_triplet_attention_proj_fwd')
-            _lib.check(_lib.lib().tgt_triplet_attention_proj_fwd(C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), _stream()),
-                       'tgt_triplet_attention_proj_fwd')
+            if node_counts is None:
+                _lib.check(_lib.lib().tgt_triplet_attention_proj_fwd(C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), _stream()),
+                           'tgt_triplet_attention_proj_fwd')
+            else:              # (padded units: no Q/K/V rows either -- the backward below gets the same counts)
+                _lib.check(_lib.lib().tgt_triplet_attention_proj_fwd_counts(C.byref(a), _ptr(node_counts), _ptr(x2), L.C, _ptr(w), _ptr(b),
+                                                                            _stream()), 'tgt_triplet_attention_proj_fwd_counts')
             _prof_end('tgt_triplet_attention_proj_fwd', s0, s1)
             if infer:
                 return out                 # (nothing to save: no backward exists)
@@ -621,15 +659,16 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             else:
                 eg = torch.addmm(be, x2, we.t()).view(B, N, N, L.used - 6 * L.C)
             a = _tri_args(fused, mask3, out, L, dropout=dropout, eg=eg, graph_scale=graph_scale)
-            _call('tgt_triplet_attention_fwd', _lib.lib().tgt_triplet_attention_fwd, a)
+            _call_counts('tgt_triplet_attention_fwd', a, node_counts)
         else:
             x2, w, fused = _linear_forward(x, weight, bias, cd)
             a = _tri_args(fused, mask3, out, L, dropout=dropout, graph_scale=graph_scale)
-            _call('tgt_triplet_attention_fwd', _lib.lib().tgt_triplet_attention_fwd, a)
+            _call_counts('tgt_triplet_attention_fwd', a, node_counts)
         ctx.save_for_backward(x2, w, fused, mask3, out, eg if eg is not None else fused.new_empty(0),
                               *(wb if table is not None else ()))
         ctx.L, ctx.table, ctx.dropout = L, table, dropout
         ctx.graph_scale = proj_skip if proj_skip is not None else (graph_scale if _TRI_SKIP_BWD else None)
+        ctx.node_counts = node_counts
         ctx.meta = (x.shape, x.dtype, weight.dtype, bias.dtype)
         return out
 
@@ -648,10 +687,10 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         kb = fused.shape[1] > 64
         colsum = None if kb else _colsum_workspace(fused.shape[0], L.width, L.used, fused.device)
         a = _tri_args(fused, mask3, out, L, d_out, d_fused, colsum, dropout=ctx.dropout, eg=eg, graph_scale=ctx.graph_scale)
-        _call('tgt_triplet_attention_bwd', _lib.lib().tgt_triplet_attention_bwd, a)
+        _call_counts('tgt_triplet_attention_bwd', a, ctx.node_counts)
         if _GATE_NODE_BWD == 1:
             _gate_record(d_fused.device)
-        need_p = any(ctx.needs_input_grad[8:])
+        need_p = any(ctx.needs_input_grad[9:])
         d2 = d_fused.view(-1, L.width)
         if kb:
             db = column_sum(d2) if need_p else None
@@ -678,27 +717,28 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             dx, dw, _ = _linear_backward(x2, w, d2, xs, xdt, torch.float32, None,
                                          ctx.needs_input_grad[0], need_p, False)
         if not need_p:
-            return (dx, None, None, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 8)
+            return (dx, None, None, None, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 9)
         if table is None:
-            return dx, None, None, None, None, None, None, None, _param_grad(dw, wdt), _param_grad(db, bdt)
+            return dx, None, None, None, None, None, None, None, None, _param_grad(dw, wdt), _param_grad(db, bdt)
         with _on_stream(ws):           # (the parameter gradients leave on the stream their weight gradient was computed on)
             grads = _unfuse_grads(table, params, dw, db)
-        return (dx, None, None, None, None, None, None, None, *grads)
+        return (dx, None, None, None, None, None, None, None, None, *grads)
 
 
-def projected_triplet_attention(x, weight, bias, mask3, layout, table=None, dropout=(0.0, 0), graph_scale=None):
+def projected_triplet_attention(x, weight, bias, mask3, layout, table=None, dropout=(0.0, 0), graph_scale=None, node_counts=None):
     """triplet_attention(linear(x, weight, bias), mask3, layout) with the bias gradient of the
     projection produced inside the backward kernel.  weight/bias: the fused (layout.width, C)
     projection in kernel order (see TripletLayout) -- or, with a ParamTable, `weight` is the
-    tuple of the module's nn.Linear parameters (w0, b0, w1, b1, ...) and bias is None."""
+    tuple of the module's nn.Linear parameters (w0, b0, w1, b1, ...) and bias is None.  node_counts: as triplet_attention; in
+    the projection-fused forward the padded columns are not projected either."""
     if not _TRI_COLSUM and table is None:      # A/B knob: separate bias-gradient pass
-        return triplet_attention(linear(x, weight, bias), mask3, layout, dropout, graph_scale)
+        return triplet_attention(linear(x, weight, bias), mask3, layout, dropout, graph_scale, node_counts)
     cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
     wb = (weight, bias) if table is None else tuple(weight)
     # (grad mode is always off INSIDE Function.forward and ctx.needs_input_grad ignores torch.no_grad(): whether a backward can
     # follow is decided here)
     no_backward = not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, *wb)))
-    return _ProjectedTripletAttention.apply(x, mask3, layout, cd, table, dropout, graph_scale, no_backward, *wb)
+    return _ProjectedTripletAttention.apply(x, mask3, layout, cd, table, dropout, graph_scale, no_backward, node_counts, *wb)
 
 
 # ---------------------------------------------------------------------------

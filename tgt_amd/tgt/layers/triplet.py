@@ -122,20 +122,24 @@ class TripletAttention(_TripletBase):
 
     takes_graph_scale = True          # forward_normed(..., graph_scale=): DropPath-dropped graphs are not computed
 
-    def forward_normed(self, x, mask, graph_scale=None):
+    takes_node_counts = True          # forward_normed(..., node_counts=): padded nodes of a ragged batch are not computed
+
+    def forward_normed(self, x, mask, graph_scale=None, node_counts=None):
         """the block after tri_ln_e (TGT_Layer fuses that LayerNorm with the residual add before it).
         graph_scale (B,) float32: the DropPath factor the CALLER multiplies this block's result with at the residual add
-        (reference layers.py:286-287); graphs whose factor is 0 are skipped by the attention kernels"""
-        return self._out_proj(self.attend(x, mask, graph_scale))
+        (reference layers.py:286-287); graphs whose factor is 0 are skipped by the attention kernels.
+        node_counts (B,) int32 (ops.mask_node_counts): the attention kernels skip the columns j >= node_counts[b] of a graph --
+        Va is zero there, so the result there is lin_O's bias instead of finite garbage (N <= 64; ops.triplet_attention)"""
+        return self._out_proj(self.attend(x, mask, graph_scale, node_counts))
 
-    def attend(self, x, mask, graph_scale=None):
+    def attend(self, x, mask, graph_scale=None, node_counts=None):
         """forward_normed without lin_O: Va in the kernels' channel order (TGT_Layer fuses lin_O with what follows it:
         out_proj_residual_ln)"""
         B, N = x.shape[0], x.shape[1]
         return ops.projected_triplet_attention(x, self._projection_params(), None, ops.as_mask3(mask, B, N),
                                                self._layout, table=self._table,
                                                dropout=ops.draw_dropout(self.attention_dropout, self.training),
-                                               graph_scale=graph_scale)
+                                               graph_scale=graph_scale, node_counts=node_counts)
 
 
 class TripletAttentionUngated(TripletAttention):

@@ -3,12 +3,14 @@ Same public behaviour and state_dict prefixes (`TGT_layers.{i}.`) as the referen
 lib/tgt/encoder.py."""
 from torch import nn
 
+from .. import ops
 from ..knobs import K
 from .layers import TGT_Layer
 from .layers.blocks import PendingResidual
 
 
 _DEFER_EDGE = K.defer_edge      # A/B knob (tgt_amd/knobs.py)
+_TRI_RAGGED = K.tri_ragged      # triplet attention skips the padded nodes of every graph (default off)
 
 
 class Graph(dict):
@@ -68,6 +70,11 @@ class TGT_Encoder(nn.Module):
 
     def forward(self, inputs):
         graph = Graph(inputs)
+        # ragged batches: the per-graph node counts the triplet attention kernels skip behind, once per forward from the mask
+        # (one launch, nothing read on the host); a caller that knows num_nodes may put its own int32 `node_counts` in the inputs
+        own_counts = _TRI_RAGGED and graph.get('node_counts') is None and graph.mask.is_cuda
+        if own_counts:
+            graph['node_counts'] = ops.mask_node_counts(ops.as_mask3(graph.mask, graph.e.shape[0], graph.e.shape[1]))
         for idx in range(self.model_height):
             # between layers the closing edge residual travels un-added (layers.PendingResidual)
             graph = self.apply_layer(idx, graph, defer_edge=_DEFER_EDGE)
@@ -76,4 +83,6 @@ class TGT_Encoder(nn.Module):
         side = graph.pop('node_side', None)
         if side is not None:
             side.join(graph.h)
+        if own_counts:
+            graph.pop('node_counts', None)
         return graph
