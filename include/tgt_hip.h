@@ -41,6 +41,7 @@ enum {
     TGT_TRI_GATED       = 2,   /* third-arm sigmoid gate present */
     TGT_TRI_MASK_OUT    = 4,   /* aggregate only: mask the outward direction (ungated variant) */
     TGT_TRI_NO_QKV_STORE = 8,  /* tgt_triplet_attention_proj_fwd only: do not write the projected Q/K/V rows (no backward follows) */
+    TGT_TRI_COUNTS_KB   = 16,  /* tgt_triplet_attention_fwd_counts / _bwd_counts only, N > 64, node_counts != NULL: the key-blocked kernels use the counts */
 };
 
 const char* tgt_last_error(void);
@@ -125,21 +126,38 @@ int64_t tgt_triplet_attention_workspace_bytes(const tgt_triplet_attention_args* 
 int tgt_triplet_attention_fwd(const tgt_triplet_attention_args* a, void* stream);
 int tgt_triplet_attention_bwd(const tgt_triplet_attention_args* a, void* stream);
 
-/* Ragged batches: skip the padded nodes of every graph (N <= 64).  As tgt_triplet_attention_fwd / _bwd /
+/* Ragged batches: skip the padded nodes of every graph.  As tgt_triplet_attention_fwd / _bwd /
  * tgt_triplet_attention_proj_fwd (below), plus node_counts: (B) int32 DEVICE memory, or NULL (= the entry point without
  * _counts, which forwards here with NULL).  A workgroup walks the shared node j ("unit" j) of its graph; with
- * n = clamp(node_counts[b], 0, N) the walk ends at n instead of N:
+ * n = clamp(node_counts[b], 0, N) the walk ends at n instead of N.
+ * N <= 64:
  *   forward : rows out[b, :, j, :] of both directions are zeros for j >= n; the Q/K/V rows of those units are not read, and in the
  *             projection-fused training forward they are not projected or written either (their qkv rows keep what the buffer held).
  *             Everything with j < n is computed exactly as without counts (same strides, same dropout pattern: N keeps its role).
  *   backward: d_out[b, :, j, :] for j >= n is NOT READ and taken as zero; the d_qkv rows of those units -- [:, j] (Q) and
  *             [j, :] inward / [:, j] outward (K, V) -- get zeros; d_eg and the optional column sums get no contribution from them.
  *             A backward must be given the counts its forward got.
+ * N > 64 (key-blocked kernels): the counts are used only with TGT_TRI_COUNTS_KB in a->flags; with the bit clear they are accepted
+ * and ignored (the code path and results of a call without counts), and every other entry point ignores the bit.  With the bit
+ * set a workgroup owns a tile of 32 rows, so a count bounds three axes: the walk, the 32-row query tiles and the 32-key blocks.
+ * With n32 = n rounded up to 32:
+ *   forward : out[b, :, j, :] is zeros for j >= n (both directions) and out[b, i, j, :] is zeros for i >= n32; rows n <= i < n32
+ *             of a computed unit hold finite values that need not be those of a call without counts; out[b, :n, :n] is
+ *             bit-identical to that call.  The Q/K/V rows of skipped units, skipped query tiles (i >= n32) and skipped key blocks
+ *             (k >= n32) are not read.  N keeps every stride, row bound, dropout unit index and dropout word index: the drop
+ *             pattern of a computed element does not move.
+ *   backward: d_out[b, :, j, :] for j >= n is NOT READ; d_out[b, i, j, :] with i >= n MUST be zero (it may or may not be read).
+ *             Every element of d_qkv and of the E/G columns of d_eg is still written; the elements of a padded unit, a padded
+ *             query tile or a padded key tile get zeros.  A backward must be given its forward's counts AND flag.  With a
+ *             cotangent that is zero at every padded row and column the whole gradient is bit-identical to the call without counts.
+ *   workspace: tgt_triplet_attention_workspace_bytes does not depend on the bit (the count is unknown on the host); no sweep of
+ *             the backward reads a statistics entry that no sweep of the same call wrote.
  * A count is a permission to skip, never an obligation.  It is exact when every key k >= n of the graph is closed by the mask
- * (weight exactly 0) and the caller's loss ignores the padded columns (their cotangent is zero): the real block of `out` and all
+ * (weight exactly 0) and the caller's loss ignores the padded columns (their cotangent is zero) -- for N > 64 with the bit set,
+ * the padded rows too, and every real row i < n must have an open key k < n (a prefix mask): the real block of `out` and all
  * gradients are then bit-identical with and without counts.  graph_scale keeps its meaning and wins: a dropped graph is all zeros
  * whatever its count.  The kernels clamp the count; no entry point reads it on the host (no synchronisation, capturable).
- * N > 64 (key-blocked kernels): counts are accepted and ignored.  The aggregate and node attention families take no counts. */
+ * The aggregate and node attention families take no counts. */
 int tgt_triplet_attention_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, void* stream);
 int tgt_triplet_attention_bwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, void* stream);
 /* counts[b] = 1 + the largest j for which some i has an OPEN mask[b,i,j] (open: value > -FLT_MAX/2); 0 when every entry of the

@@ -31,6 +31,7 @@ TRI_BIASED, TRI_GATED, TRI_MASK_OUT = 1, 2, 4
 # tgt_node_attention_family(): the kernel family behind tgt_node_attention_fwd / _bwd for a call
 NODE_FAMILY_NONE, NODE_FAMILY_LANE, NODE_FAMILY_MFMA32, NODE_FAMILY_TILES16, NODE_FAMILY_KB_FWD, NODE_FAMILY_KB_BWD = range(6)
 TRI_NO_QKV_STORE = 8              # tgt_triplet_attention_proj_fwd only: the projected Q/K/V rows are not written
+TRI_COUNTS_KB = 16                # tgt_triplet_attention_fwd_counts / _bwd_counts only: the kernels for N > 64 use the node counts
 
 _i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 

@@ -759,7 +759,7 @@ bool tri_att16_bwd_eligible(const tgt_triplet_attention_args& a);
 int tri_att16_bwd_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st);
 bool tri_att_bwd2_eligible(const tgt_triplet_attention_args& a);       // triplet_attention_bwd2.hip: 16-bit, D = 16, N <= 32, H % 8 == 0
 int tri_att_bwd2_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st);
-int tri_att_kb_run(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st);      // triplet_attention_kb.hip: 65 <= N <= 128, D = 16
+int tri_att_kb_run(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st);      // triplet_attention_kb.hip: 65 <= N <= 128, D = 16
 
 // tgt_mask_node_counts: one workgroup per graph; every thread keeps the largest j + 1 of the OPEN entries (value > -FLT_MAX/2)
 // it meets, the workgroup folds them with an LDS max
@@ -810,7 +810,7 @@ int triplet_attention_run(const tgt_triplet_attention_args* a, const int32_t* nc
             if ((a->flags & (TGT_TRI_BIASED | TGT_TRI_GATED)) && !a->d_eg[dir]) return set_error(TGT_ERR_INVALID, "triplet attention bwd: d_eg missing");
         }
     }
-    if (a->N > 64) return tri_att_kb_run(*a, bwd, st);                             // key-blocked kernels; checks D and the workspace before any launch (node counts: ignored)
+    if (a->N > 64) return tri_att_kb_run(*a, nc, bwd, st);                         // key-blocked kernels; checks D and the workspace before any launch (node counts: used with TGT_TRI_COUNTS_KB only)
     if (!bwd && tri_att16_fwd_eligible(*a)) return tri_att16_fwd_run(*a, nc, st);      // 33 <= N <= 64: 16-wide tiles (triplet_attention16.hip)
     if (bwd && tri_att16_bwd_eligible(*a)) return tri_att16_bwd_run(*a, nc, st);
     if (bwd && tri_att_bwd2_eligible(*a)) return tri_att_bwd2_run(*a, nc, st);

@@ -18,6 +18,25 @@
 //              S is produced directly as S[i][k] (lane = k), so no re-layout through the identity is needed.
 //   workspace layout: float [B][2][H][N (j)][3 (max, 1/sum, delta)][Np (i)], Np = N rounded up to 32.
 // Dropout: word index (i*128 + k) >> 1 inside a unit (triplet_common.hpp).  In-kernel column sums are not provided here.
+//
+// Ragged batches (TGT_TRI_COUNTS_KB with node counts, tgt_hip.h): every kernel has a second instantiation that takes the per-graph
+// counts as a trailing argument (`NC... nc`, RG = true: triplet_common.hpp, tri_node_count; without it the pack is empty and the
+// kernel is the one it was before the counts existed).  With n = clamp(node_counts[b], 0, N) and n32 = n rounded up to 32 it
+// bounds all three axes of the work:
+//   owned tile   a workgroup whose tile starts at or past n32 (query tile i0; K sweep: key tile k0) holds padded nodes only: it
+//                writes the zeros a dropped graph gets and returns;
+//   walk         j ends at n (the register prefetch of j + 1 too); the rows of the units n..N-1 get zeros, in the backward ahead
+//                of the walk;
+//   inner tiles  key blocks (forward, E sweep, Q sweep) / query tiles (K sweep) at or past n32 are neither loaded nor computed:
+//                their third-arm tiles take the -inf / 0 of blocks past N and the 128-row slabs are loaded up to min(n32, N).
+// Why skipping a key block keeps the bits of a real query row (i < n; the mask closes every key k >= n and opens at least one
+// k < n): every logit of the block is finfo.min, so its maximum cannot raise the running maximum; alpha = exp(m - m) = exp(0)
+// is exactly 1; every exp(finfo.min - m) underflows to exactly 0; the row sum gains 0 and the matrix-core product adds
+// 0 * V (finite) = 0 to O.  The backward is the same argument on P = 0: dS = P (...) = 0, so dE, dG, dQ, dK gain zeros, and dV
+// gains dO^T A with A = P gate = 0.  A skipped QUERY tile (K sweep) has d_out = 0 (the contract) and delta = 0, so dS = 0 and
+// dV gains 0 * A.  Rows n <= i < n32 of a computed tile see fewer keys than without counts (finite, different) and, with their
+// zero d_out, contribute zeros either way.  N keeps every stride, row bound, Np and dropout index; the E sweep writes and the
+// other two sweeps read the statistics of (j < n, i < n32) only.
 #include "triplet_common.hpp"
 
 namespace tgt {
@@ -29,8 +48,9 @@ __device__ __forceinline__ float* kb_stats(const tgt_triplet_attention_args& a, 
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
-template <typename T, int HG, bool PF>
-__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_fwd_kernel(const tgt_triplet_attention_args a) {
+template <typename T, int HG, bool PF, typename... NC>
+__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_fwd_kernel(const tgt_triplet_attention_args a, NC... nc) {
+    constexpr bool RG = sizeof...(NC) > 0;          // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -57,15 +77,18 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     const SlabBuf bV = {r_src, (uint32_t)(a.v_off[c.dir] * sz) + hch, bK.row_stride, bK.j_stride};
     const SlabBuf bO = {graph_rsrc(a.out, Nl * Nl * a.ld_out * sz, c.b), (uint32_t)(a.o_off[c.dir] * sz) + hch, (uint32_t)N * ldo_, ldo_};
 
-    if (a.graph_scale && a.graph_scale[c.b] == 0.f) {          // DropPath-dropped graph: zero rows, nothing read
-        for (int j = 0; j < N; ++j) slab_store_zero<G, 32>(bO, j, i0, N, tid);
+    // n real nodes (RG; else N): key blocks at or past nkb are skipped, the 128-row slabs are loaded up to row nrow
+    const int n = tri_node_count<RG>(tri_counts_ptr(nc...), c.b, N);
+    const int nkb = RG ? tri_count32(n) : N, nrow = RG ? min(nkb, N) : N;
+    if ((RG && i0 >= nkb) || (a.graph_scale && a.graph_scale[c.b] == 0.f)) {          // DropPath-dropped graph / query tile of padded nodes: zero rows, nothing read
+        slab_zero_units<G>(0, N, i0, N, tid, bO);
         return;
     }
 
     float biasM[4][16], gate[4][16];
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
-        if (32 * kt < N) {
+        if (32 * kt < nkb) {
             load_third_arm<T, false>(ta, c.b, c.dir, c.h, N, r, hi, biasM[kt], gate[kt], i0, 32 * kt);
         } else {
 #pragma unroll
@@ -76,25 +99,25 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     uint4 pq[SlabIO<G, 32>::kIters], pk[SlabIO<G, 128>::kIters], pv[SlabIO<G, 128>::kIters];
     if constexpr (PF) {
         slab_issue<G, 32>(pq, bQ, 0, i0, N, tid);
-        slab_issue<G, 128>(pk, bK, 0, 0, N, tid);
-        slab_issue<G, 128>(pv, bV, 0, 0, N, tid);
+        slab_issue<G, 128>(pk, bK, 0, 0, nrow, tid);
+        slab_issue<G, 128>(pv, bV, 0, 0, nrow, tid);
     }
     // one LDS set, two barriers per j: the commit of j+1 follows barrier 2 of j (every wave is done reading K / V);
     // the O rows in sQ are stored by the thread that overwrites the same chunk next (same chunk map)
-    for (int j = 0; j < N; ++j) {
+    for (int j = 0; j < n; ++j) {
         if constexpr (!PF) {
             slab_issue<G, 32>(pq, bQ, j, i0, N, tid);
-            slab_issue<G, 128>(pk, bK, j, 0, N, tid);
-            slab_issue<G, 128>(pv, bV, j, 0, N, tid);
+            slab_issue<G, 128>(pk, bK, j, 0, nrow, tid);
+            slab_issue<G, 128>(pv, bV, j, 0, nrow, tid);
         }
         slab_commit<G, 32>(pq, sQ, tid);
         slab_commit<G, 128>(pk, sK, tid);
         slab_commit<G, 128>(pv, sV, tid);
         if constexpr (PF) {
-            if (j + 1 < N) {
+            if (j + 1 < n) {
                 slab_issue<G, 32>(pq, bQ, j + 1, i0, N, tid);
-                slab_issue<G, 128>(pk, bK, j + 1, 0, N, tid);
-                slab_issue<G, 128>(pv, bV, j + 1, 0, N, tid);
+                slab_issue<G, 128>(pk, bK, j + 1, 0, nrow, tid);
+                slab_issue<G, 128>(pv, bV, j + 1, 0, nrow, tid);
             }
         }
         __syncthreads();
@@ -105,7 +128,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
         f32x16 o = {0};
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
-            if (32 * kt < N) {
+            if (32 * kt < nkb) {
                 F fk[1], fv[1];
                 read_frags<T, 16, HG>(fk, sK, wave, 32 * kt + r, hi);
                 read_frags<T, 16, HG>(fv, sV, wave, 32 * kt + r, hi);
@@ -151,13 +174,15 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
         __syncthreads();
         slab_store<G, 32>(sQ, bO, j, i0, N, tid);
     }
+    if constexpr (RG) slab_zero_units<G>(n, N, i0, N, tid, bO);          // the padded units of a ragged batch
 }
 
 // ---------------------------------------------------------------------------
 // backward, E sweep (EG = true): statistics, dE / dG;  Q sweep (EG = false): dQ from the E sweep's statistics
 // ---------------------------------------------------------------------------
-template <typename T, int HG, bool PF, bool EG>
-__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_bwd_q_kernel(const tgt_triplet_attention_args a) {
+template <typename T, int HG, bool PF, bool EG, typename... NC>
+__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_bwd_q_kernel(const tgt_triplet_attention_args a, NC... nc) {
+    constexpr bool RG = sizeof...(NC) > 0;          // ragged: as tri_kb_fwd_kernel
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -200,21 +225,25 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
         for (int q = 0; q < 16; ++q) dE[kt][q] = dG[kt][q] = 0.f;
 
-    if (a.graph_scale && a.graph_scale[c.b] == 0.f) {          // dropped graph: zero gradient rows, nothing read
+    const int n = tri_node_count<RG>(tri_counts_ptr(nc...), c.b, N);
+    const int nkb = RG ? tri_count32(n) : N, nrow = RG ? min(nkb, N) : N;
+    if ((RG && i0 >= nkb) || (a.graph_scale && a.graph_scale[c.b] == 0.f)) {          // dropped graph / query tile of padded nodes: zero gradient rows, nothing read
         if constexpr (EG) {
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt)
                 if (32 * kt < N) store_third_arm_grad<T>(dta, a.d_eg[c.dir], c.b, c.dir, c.h, N, r, hi, dE[kt], dG[kt], i0, 32 * kt);
         } else {
-            for (int j = 0; j < N; ++j) slab_store_zero<G, 32>(gQ, j, i0, N, tid);
+            slab_zero_units<G>(0, N, i0, N, tid, gQ);
         }
         return;
     }
+    // the padded units of a ragged batch, ahead of the walk (its stores go to other rows)
+    if constexpr (RG && !EG) slab_zero_units<G>(n, N, i0, N, tid, gQ);
 
     float biasM[4][16], gate[4][16];
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
-        if (32 * kt < N) {
+        if (32 * kt < nkb) {
             load_third_arm<T, true>(ta, c.b, c.dir, c.h, N, r, hi, biasM[kt], gate[kt], i0, 32 * kt);
         } else {
 #pragma unroll
@@ -226,26 +255,26 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     if constexpr (PF) {
         slab_issue<G, 32>(pq, bQ, 0, i0, N, tid);
         slab_issue<G, 32>(po, dO, 0, i0, N, tid);
-        slab_issue<G, 128>(pk, bK, 0, 0, N, tid);
-        slab_issue<G, 128>(pv, bV, 0, 0, N, tid);
+        slab_issue<G, 128>(pk, bK, 0, 0, nrow, tid);
+        slab_issue<G, 128>(pv, bV, 0, 0, nrow, tid);
     }
-    for (int j = 0; j < N; ++j) {
+    for (int j = 0; j < n; ++j) {
         if constexpr (!PF) {
             slab_issue<G, 32>(pq, bQ, j, i0, N, tid);
             slab_issue<G, 32>(po, dO, j, i0, N, tid);
-            slab_issue<G, 128>(pk, bK, j, 0, N, tid);
-            slab_issue<G, 128>(pv, bV, j, 0, N, tid);
+            slab_issue<G, 128>(pk, bK, j, 0, nrow, tid);
+            slab_issue<G, 128>(pv, bV, j, 0, nrow, tid);
         }
         slab_commit<G, 32>(pq, sQ, tid);
         slab_commit<G, 32>(po, sO, tid);
         slab_commit<G, 128>(pk, sK, tid);
         slab_commit<G, 128>(pv, sV, tid);
         if constexpr (PF) {
-            if (j + 1 < N) {
+            if (j + 1 < n) {
                 slab_issue<G, 32>(pq, bQ, j + 1, i0, N, tid);
                 slab_issue<G, 32>(po, dO, j + 1, i0, N, tid);
-                slab_issue<G, 128>(pk, bK, j + 1, 0, N, tid);
-                slab_issue<G, 128>(pv, bV, j + 1, 0, N, tid);
+                slab_issue<G, 128>(pk, bK, j + 1, 0, nrow, tid);
+                slab_issue<G, 128>(pv, bV, j + 1, 0, nrow, tid);
             }
         }
         __syncthreads();
@@ -259,7 +288,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
         if constexpr (EG) {
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
-            if (32 * kt < N) {
+            if (32 * kt < nkb) {
                 F fk[1], fv[1];
                 read_frags<T, 16, HG>(fk, sK, wave, 32 * kt + r, hi);
                 read_frags<T, 16, HG>(fv, sV, wave, 32 * kt + r, hi);
@@ -312,7 +341,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
         f32x16 dq = {0};
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
-            if (32 * kt < N) {
+            if (32 * kt < nkb) {
                 F fk[1], fv[1];
                 read_frags<T, 16, HG>(fk, sK, wave, 32 * kt + r, hi);
                 read_frags<T, 16, HG>(fv, sV, wave, 32 * kt + r, hi);
@@ -360,8 +389,9 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
 // ---------------------------------------------------------------------------
 // backward, K sweep: dK, dV.  Lane = key k of the owned tile, register q <-> query i = 32*it + acc_row(q, hi).
 // ---------------------------------------------------------------------------
-template <typename T, int HG, bool PF>
-__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_bwd_k_kernel(const tgt_triplet_attention_args a) {
+template <typename T, int HG, bool PF, typename... NC>
+__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_bwd_k_kernel(const tgt_triplet_attention_args a, NC... nc) {
+    constexpr bool RG = sizeof...(NC) > 0;          // ragged: as tri_kb_fwd_kernel, with the roles of query and key tiles exchanged
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -397,20 +427,22 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     const SlabBuf dK = {r_grd, ko, c.dir == 0 ? ldg_ : (uint32_t)N * ldg_, c.dir == 0 ? (uint32_t)N * ldg_ : ldg_};
     const SlabBuf dV = {r_grd, vo, dK.row_stride, dK.j_stride};
 
-    if (a.graph_scale && a.graph_scale[c.b] == 0.f) {
-        for (int j = 0; j < N; ++j) {
-            slab_store_zero<G, 32>(dK, j, k0, N, tid);
-            slab_store_zero<G, 32>(dV, j, k0, N, tid);
-        }
+    // n real nodes (RG; else N): query tiles at or past nqt are skipped, the 128-row slabs are loaded up to row nrow
+    const int n = tri_node_count<RG>(tri_counts_ptr(nc...), c.b, N);
+    const int nqt = RG ? tri_count32(n) : N, nrow = RG ? min(nqt, N) : N;
+    if ((RG && k0 >= nqt) || (a.graph_scale && a.graph_scale[c.b] == 0.f)) {          // dropped graph / key tile of padded nodes: zero gradient rows, nothing read
+        slab_zero_units<G>(0, N, k0, N, tid, dK, dV);
         return;
     }
+    // the padded units of a ragged batch, ahead of the walk (its stores go to other rows)
+    if constexpr (RG) slab_zero_units<G>(n, N, k0, N, tid, dK, dV);
 
     // third-arm tiles with the roles of the two indices exchanged: load_third_arm's "lane" index is the key here and its
     // "register" index the query, which is the other direction's pair order
     float biasT[4][16], gateT[4][16];
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
-        if (32 * it < N) {
+        if (32 * it < nqt) {
             load_third_arm<T, true>(ta, c.b, 1 - c.dir, c.h, N, r, hi, biasT[it], gateT[it], k0, 32 * it);
         } else {
 #pragma unroll
@@ -422,31 +454,40 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     if constexpr (PF) {
         slab_issue<G, 32>(pk, bK, 0, k0, N, tid);
         slab_issue<G, 32>(pv, bV, 0, k0, N, tid);
-        slab_issue<G, 128>(pq, bQ, 0, 0, N, tid);
-        slab_issue<G, 128>(po, dO, 0, 0, N, tid);
+        slab_issue<G, 128>(pq, bQ, 0, 0, nrow, tid);
+        slab_issue<G, 128>(po, dO, 0, 0, nrow, tid);
     }
-    for (int j = 0; j < N; ++j) {
+    for (int j = 0; j < n; ++j) {
         if constexpr (!PF) {
             slab_issue<G, 32>(pk, bK, j, k0, N, tid);
             slab_issue<G, 32>(pv, bV, j, k0, N, tid);
-            slab_issue<G, 128>(pq, bQ, j, 0, N, tid);
-            slab_issue<G, 128>(po, dO, j, 0, N, tid);
+            slab_issue<G, 128>(pq, bQ, j, 0, nrow, tid);
+            slab_issue<G, 128>(po, dO, j, 0, nrow, tid);
         }
         slab_commit<G, 32>(pk, sK, tid);
         slab_commit<G, 32>(pv, sV, tid);
         slab_commit<G, 128>(pq, sQ, tid);
         slab_commit<G, 128>(po, sO, tid);
-        // the Q sweep's statistics of (j, every i) for this group's heads
-        for (int idx = tid; idx < HG * 3 * Np; idx += HG * 64) {
-            const int hh = idx / (3 * Np), rem = idx - hh * 3 * Np, t = rem / Np, i = rem - t * Np;
-            sS[hh * 384 + t * 128 + i] = kb_stats(a, c.b, c.dir, c.g * HG + hh, j, Np)[rem];
+        // the E sweep's statistics of (j, every i) for this group's heads; ragged: of the i < nqt it wrote
+        if constexpr (RG) {
+            // idx = the LDS slot: no division by a run-time count, and no branch around the load (the loads of one step go out
+            // back to back).  Slots i >= nqt, which nothing reads, get a copy of entry nqt - 1 -- an entry the E sweep wrote.
+            for (int idx = tid; idx < HG * 384; idx += HG * 64) {
+                const int hh = idx / 384, t = (idx >> 7) % 3, i = min(idx & 127, nqt - 1);
+                sS[idx] = kb_stats(a, c.b, c.dir, c.g * HG + hh, j, Np)[t * Np + i];
+            }
+        } else {
+            for (int idx = tid; idx < HG * 3 * Np; idx += HG * 64) {
+                const int hh = idx / (3 * Np), rem = idx - hh * 3 * Np, t = rem / Np, i = rem - t * Np;
+                sS[hh * 384 + t * 128 + i] = kb_stats(a, c.b, c.dir, c.g * HG + hh, j, Np)[rem];
+            }
         }
         if constexpr (PF) {
-            if (j + 1 < N) {
+            if (j + 1 < n) {
                 slab_issue<G, 32>(pk, bK, j + 1, k0, N, tid);
                 slab_issue<G, 32>(pv, bV, j + 1, k0, N, tid);
-                slab_issue<G, 128>(pq, bQ, j + 1, 0, N, tid);
-                slab_issue<G, 128>(po, dO, j + 1, 0, N, tid);
+                slab_issue<G, 128>(pq, bQ, j + 1, 0, nrow, tid);
+                slab_issue<G, 128>(po, dO, j + 1, 0, nrow, tid);
             }
         }
         __syncthreads();
@@ -458,7 +499,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
         f32x16 dk = {0}, dv = {0};
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            if (32 * it < N) {
+            if (32 * it < nqt) {
                 F fq[1], fo[1];
                 read_frags<T, 16, HG>(fq, sQ, wave, 32 * it + r, hi);
                 read_frags<T, 16, HG>(fo, sO, wave, 32 * it + r, hi);
@@ -506,25 +547,27 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-template <typename T, int HG>
-static int launch_kb(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) {
+// nc: the node counts of a call with TGT_TRI_COUNTS_KB (a trailing kernel argument: the RG instantiations), or nothing
+template <typename T, int HG, typename... NC>
+static int launch_kb(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st, NC... nc) {
     using G = TriGeo<T, 16, HG>;
     // register prefetch of slab j+1 under the math of j where the register file has room for it (16-bit); fp32 loads in place
     constexpr bool kPF = sizeof(T) == 2;
     const int grid = a.B * 2 * (a.H / HG) * ((a.N + 31) / 32);
     constexpr int kFwdLds = 9 * G::kSlabBytes, kBwdQLds = 10 * G::kSlabBytes, kBwdKLds = 10 * G::kSlabBytes + HG * 384 * 4;
     const dim3 blocks(grid), threads(G::kThreads);
-    if (!bwd) return launch_lds<tri_kb_fwd_kernel<T, HG, kPF>>("tri_kb_fwd_kernel", blocks, threads, kFwdLds, st, a);
+    if (!bwd) return launch_lds<tri_kb_fwd_kernel<T, HG, kPF, NC...>>("tri_kb_fwd_kernel", blocks, threads, kFwdLds, st, a, nc...);
     // (all three reservations before the first launch: a failed one leaves nothing half-written)
-    if (int rc = reserve_lds<tri_kb_bwd_q_kernel<T, HG, kPF, true>>("tri_kb_bwd_e_kernel", kBwdQLds)) return rc;
-    if (int rc = reserve_lds<tri_kb_bwd_q_kernel<T, HG, kPF, false>>("tri_kb_bwd_q_kernel", kBwdQLds)) return rc;
-    if (int rc = reserve_lds<tri_kb_bwd_k_kernel<T, HG, kPF>>("tri_kb_bwd_k_kernel", kBwdKLds)) return rc;
-    if (int rc = launch_lds<tri_kb_bwd_q_kernel<T, HG, kPF, true>>("tri_kb_bwd_e_kernel", blocks, threads, kBwdQLds, st, a)) return rc;    // E sweep: statistics first
-    if (int rc = launch_lds<tri_kb_bwd_q_kernel<T, HG, kPF, false>>("tri_kb_bwd_q_kernel", blocks, threads, kBwdQLds, st, a)) return rc;
-    return launch_lds<tri_kb_bwd_k_kernel<T, HG, kPF>>("tri_kb_bwd_k_kernel", blocks, threads, kBwdKLds, st, a);
+    if (int rc = reserve_lds<tri_kb_bwd_q_kernel<T, HG, kPF, true, NC...>>("tri_kb_bwd_e_kernel", kBwdQLds)) return rc;
+    if (int rc = reserve_lds<tri_kb_bwd_q_kernel<T, HG, kPF, false, NC...>>("tri_kb_bwd_q_kernel", kBwdQLds)) return rc;
+    if (int rc = reserve_lds<tri_kb_bwd_k_kernel<T, HG, kPF, NC...>>("tri_kb_bwd_k_kernel", kBwdKLds)) return rc;
+    if (int rc = launch_lds<tri_kb_bwd_q_kernel<T, HG, kPF, true, NC...>>("tri_kb_bwd_e_kernel", blocks, threads, kBwdQLds, st, a, nc...)) return rc;    // E sweep: statistics first
+    if (int rc = launch_lds<tri_kb_bwd_q_kernel<T, HG, kPF, false, NC...>>("tri_kb_bwd_q_kernel", blocks, threads, kBwdQLds, st, a, nc...)) return rc;
+    return launch_lds<tri_kb_bwd_k_kernel<T, HG, kPF, NC...>>("tri_kb_bwd_k_kernel", blocks, threads, kBwdKLds, st, a, nc...);
 }
 template <typename T>
-static int dispatch_kb(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) {
+static int dispatch_kb(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) {
+    if (nc) return a.H % 4 == 0 ? launch_kb<T, 4>(a, bwd, st, nc) : launch_kb<T, 1>(a, bwd, st, nc);
     if (a.H % 4 == 0) return launch_kb<T, 4>(a, bwd, st);
     return launch_kb<T, 1>(a, bwd, st);
 }
@@ -534,17 +577,17 @@ static int dispatch_kb(const tgt_triplet_attention_args& a, bool bwd, hipStream_
 #ifndef TGT_TRIKB_INST
 #define TGT_TRIKB_INST 15
 #endif
-int tri_att_kb_run_f32(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st);
-int tri_att_kb_run_bf16(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st);
-int tri_att_kb_run_f16(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st);
+int tri_att_kb_run_f32(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st);
+int tri_att_kb_run_bf16(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st);
+int tri_att_kb_run_f16(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st);
 #if TGT_TRIKB_INST & 1
-int tri_att_kb_run_f32(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) { return dispatch_kb<float>(a, bwd, st); }
+int tri_att_kb_run_f32(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) { return dispatch_kb<float>(a, nc, bwd, st); }
 #endif
 #if TGT_TRIKB_INST & 2
-int tri_att_kb_run_bf16(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) { return dispatch_kb<bf16_t>(a, bwd, st); }
+int tri_att_kb_run_bf16(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) { return dispatch_kb<bf16_t>(a, nc, bwd, st); }
 #endif
 #if TGT_TRIKB_INST & 4
-int tri_att_kb_run_f16(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) { return dispatch_kb<f16_t>(a, bwd, st); }
+int tri_att_kb_run_f16(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) { return dispatch_kb<f16_t>(a, nc, bwd, st); }
 #endif
 
 #if TGT_TRIKB_INST & 8
@@ -560,8 +603,10 @@ int64_t tri_att_kb_workspace_bytes(const tgt_triplet_attention_args* a, int bwd)
     return (int64_t)a->B * 2 * a->H * a->N * 3 * Np * (int64_t)sizeof(float);
 }
 
-// 65 <= N <= 128, arguments already validated by triplet_attention_run
-int tri_att_kb_run(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st) {
+// 65 <= N <= 128, arguments already validated by triplet_attention_run.  nc: the node counts of a *_counts call or nullptr; they
+// reach the kernels only with TGT_TRI_COUNTS_KB in a.flags (DEVICE memory, never read here)
+int tri_att_kb_run(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) {
+    if (!(a.flags & TGT_TRI_COUNTS_KB)) nc = nullptr;
     if (a.D != 16) return set_error(TGT_ERR_UNSUPPORTED, "triplet attention: N=%d > 64 is supported for D = 16 only (D=%d)", a.N, a.D);
     if (bwd) {
         if (a.d_qkv_colsum[0] || a.d_qkv_colsum[1] || a.d_eg_colsum[0] || a.d_eg_colsum[1])
@@ -572,9 +617,9 @@ int tri_att_kb_run(const tgt_triplet_attention_args& a, bool bwd, hipStream_t st
                              a.N, (long long)need, (long long)a.workspace_bytes);
     }
     switch (a.dtype) {
-        case TGT_F32: return tri_att_kb_run_f32(a, bwd, st);
-        case TGT_BF16: return tri_att_kb_run_bf16(a, bwd, st);
-        case TGT_F16: return tri_att_kb_run_f16(a, bwd, st);
+        case TGT_F32: return tri_att_kb_run_f32(a, nc, bwd, st);
+        case TGT_BF16: return tri_att_kb_run_bf16(a, nc, bwd, st);
+        case TGT_F16: return tri_att_kb_run_f16(a, nc, bwd, st);
         default: return set_error(TGT_ERR_INVALID, "triplet attention: bad dtype %d", a.dtype);
     }
 }

@@ -552,6 +552,16 @@ __device__ __forceinline__ int tri_node_count(const int32_t* node_counts, int b,
     else return N;
 }
 
+// Key-blocked kernels (triplet_attention_kb.hip) with TGT_TRI_COUNTS_KB: tiles of 32 rows at or past n rounded up to 32 hold
+// padded nodes only and are skipped as query tiles, key blocks and owned tiles.
+__device__ __forceinline__ int tri_count32(int n) { return (n + 31) & ~31; }
+// zeros to rows [row0, row0 + 32) of the units j0 <= j < j1 of the slab tensors `bufs`: every unit of a tile that is not
+// computed (a DropPath-dropped graph, a tile of padded nodes) or the padded units n..N-1 of one that is
+template <typename G, typename... Bufs>
+__device__ __forceinline__ void slab_zero_units(int j0, int j1, int row0, int N, int tid, const Bufs&... bufs) {
+    for (int j = j0; j < j1; ++j) (slab_store_zero<G, 32>(bufs, j, row0, N, tid), ...);
+}
+
 __device__ __forceinline__ ThirdArm tri_third_arm(const tgt_triplet_attention_args& a, int dir) {
     return ThirdArm{a.eg[dir], a.ld_eg[dir], a.e_off[dir], a.g_off[dir], a.mask,
                     (a.flags & TGT_TRI_BIASED) != 0, (a.flags & TGT_TRI_GATED) != 0};

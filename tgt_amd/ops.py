@@ -33,6 +33,8 @@ _TRI_COLSUM = K.tri_colsum
 # finishing early the last round is still a round -- measured 0.474 vs 0.476 ms -- so by default it keeps computing every graph (the
 # forward, two workgroups per CU, gains 4 %)
 _TRI_SKIP_BWD = K.tri_skip == 2
+# node counts reach the key-blocked kernels (N > 64) only with this switch: the flag bit TRI_COUNTS_KB on the argument block
+_TRI_RAGGED_KB = K.tri_ragged_kb
 _NODE_KB_BWD = K.node_kb_bwd != 0       # (the library routes by the same variable; here it only words the slow-path notice)
 
 
@@ -114,8 +116,16 @@ def _check_node_counts(node_counts, B):
     return node_counts
 
 
-def _call_counts(name, args, node_counts):
-    """tgt_triplet_attention_fwd / _bwd (`name`), through the _counts entry point when node counts are given"""
+def _counts_kb(node_counts, N):
+    """does this forward hand its node counts to the key-blocked kernels?  (its backward takes the answer from ctx)"""
+    return bool(_TRI_RAGGED_KB and node_counts is not None and N > 64)
+
+
+def _call_counts(name, args, node_counts, counts_kb=False):
+    """tgt_triplet_attention_fwd / _bwd (`name`), through the _counts entry point when node counts are given; counts_kb: with
+    TRI_COUNTS_KB on the argument block (N > 64)"""
+    if counts_kb:
+        args.flags |= _lib.TRI_COUNTS_KB
     if node_counts is None:
         return _call(name, getattr(_lib.lib(), name), args)
     fn = getattr(_lib.lib(), name + '_counts')
@@ -298,10 +308,11 @@ class _TripletAttention(torch.autograd.Function):
         assert fused.shape == (B, N, N, L.width), (fused.shape, L.width)
         out = torch.empty(B, N, N, 2 * L.C, dtype=fused.dtype, device=fused.device)
         a = _tri_args(fused, mask3, out, L, dropout=dropout, graph_scale=graph_scale)
-        _call_counts('tgt_triplet_attention_fwd', a, _check_node_counts(node_counts, B))
+        ctx.counts_kb = _counts_kb(_check_node_counts(node_counts, B), N)
+        _call_counts('tgt_triplet_attention_fwd', a, node_counts, ctx.counts_kb)
         ctx.save_for_backward(fused, mask3, out)
         ctx.L, ctx.dropout, ctx.graph_scale = L, dropout, (graph_scale if _TRI_SKIP_BWD else None)
-        ctx.node_counts = node_counts          # (the backward must skip what the forward skipped)
+        ctx.node_counts = node_counts          # (the backward must skip what the forward skipped: same counts, same flag)
         return out
 
     @staticmethod
@@ -312,7 +323,7 @@ class _TripletAttention(torch.autograd.Function):
         if ctx.L.width > ctx.L.used:
             d_fused[..., ctx.L.used:] = 0
         a = _tri_args(fused, mask3, out, ctx.L, d_out, d_fused, dropout=ctx.dropout, graph_scale=ctx.graph_scale)
-        _call_counts('tgt_triplet_attention_bwd', a, ctx.node_counts)
+        _call_counts('tgt_triplet_attention_bwd', a, ctx.node_counts, ctx.counts_kb)
         return d_fused, None, None, None, None, None
 
 
@@ -325,7 +336,10 @@ def triplet_attention(fused, mask3, layout, dropout=(0.0, 0), graph_scale=None, 
     and multiplying by that zero (the incoming gradient of such a graph MUST be zero, as it is behind that multiplication).
     node_counts (B,) int32 on the device (mask_node_counts): ragged batches, N <= 64 -- the columns j >= node_counts[b] of a
     graph are not read or computed: Va[b, :, j] is zeros there and the incoming gradient of those columns is NOT READ and taken as
-    zero (exact when the mask closes every key past the count and the loss ignores the padded columns).  N > 64: ignored.
+    zero (exact when the mask closes every key past the count and the loss ignores the padded columns).  N > 64: ignored unless
+    TGT_TRI_RAGGED_KB=1 (_TRI_RAGGED_KB); then the key-blocked kernels also skip whole 32-row tiles of padded nodes: Va[b, i] is
+    zeros for i >= the count rounded up to 32 as well, the padded rows below it hold other finite values, and the incoming gradient
+    must be zero at the padded ROWS too (include/tgt_hip.h, TGT_TRI_COUNTS_KB).
     Reference arithmetic: lib/tgt/layers/triplet.py:213-246."""
     return _TripletAttention.apply(fused, mask3, layout, dropout, graph_scale, node_counts)
 
@@ -595,7 +609,7 @@ class _ProjectedTripletAttention(torch.autograd.Function):
     def forward(ctx, x, mask3, L, cd, table, dropout, graph_scale, no_backward, node_counts, *wb):
         _dev(x, mask3)
         B, N = x.shape[0], x.shape[1]
-        _check_node_counts(node_counts, B)
+        counts_kb = _counts_kb(_check_node_counts(node_counts, B), N)       # (N > 64 is GEMMs + the plain kernels below)
         weight, bias = wb if table is None else _fuse_params(table, wb, cd)
         out = torch.empty(B, N, N, 2 * L.C, dtype=cd, device=x.device)
         eg = None
@@ -659,16 +673,16 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             else:
                 eg = torch.addmm(be, x2, we.t()).view(B, N, N, L.used - 6 * L.C)
             a = _tri_args(fused, mask3, out, L, dropout=dropout, eg=eg, graph_scale=graph_scale)
-            _call_counts('tgt_triplet_attention_fwd', a, node_counts)
+            _call_counts('tgt_triplet_attention_fwd', a, node_counts, counts_kb)
         else:
             x2, w, fused = _linear_forward(x, weight, bias, cd)
             a = _tri_args(fused, mask3, out, L, dropout=dropout, graph_scale=graph_scale)
-            _call_counts('tgt_triplet_attention_fwd', a, node_counts)
+            _call_counts('tgt_triplet_attention_fwd', a, node_counts, counts_kb)
         ctx.save_for_backward(x2, w, fused, mask3, out, eg if eg is not None else fused.new_empty(0),
                               *(wb if table is not None else ()))
         ctx.L, ctx.table, ctx.dropout = L, table, dropout
         ctx.graph_scale = proj_skip if proj_skip is not None else (graph_scale if _TRI_SKIP_BWD else None)
-        ctx.node_counts = node_counts
+        ctx.node_counts, ctx.counts_kb = node_counts, counts_kb
         ctx.meta = (x.shape, x.dtype, weight.dtype, bias.dtype)
         return out
 
@@ -687,7 +701,7 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         kb = fused.shape[1] > 64
         colsum = None if kb else _colsum_workspace(fused.shape[0], L.width, L.used, fused.device)
         a = _tri_args(fused, mask3, out, L, d_out, d_fused, colsum, dropout=ctx.dropout, eg=eg, graph_scale=ctx.graph_scale)
-        _call_counts('tgt_triplet_attention_bwd', a, ctx.node_counts)
+        _call_counts('tgt_triplet_attention_bwd', a, ctx.node_counts, ctx.counts_kb)
         if _GATE_NODE_BWD == 1:
             _gate_record(d_fused.device)
         need_p = any(ctx.needs_input_grad[9:])
@@ -730,7 +744,8 @@ def projected_triplet_attention(x, weight, bias, mask3, layout, table=None, drop
     projection produced inside the backward kernel.  weight/bias: the fused (layout.width, C)
     projection in kernel order (see TripletLayout) -- or, with a ParamTable, `weight` is the
     tuple of the module's nn.Linear parameters (w0, b0, w1, b1, ...) and bias is None.  node_counts: as triplet_attention; in
-    the projection-fused forward the padded columns are not projected either."""
+    the projection-fused forward the padded columns are not projected either.  N > 64 (library GEMMs + the key-blocked kernels):
+    the counts are used with TGT_TRI_RAGGED_KB=1 only, as in triplet_attention."""
     if not _TRI_COLSUM and table is None:      # A/B knob: separate bias-gradient pass
         return triplet_attention(linear(x, weight, bias), mask3, layout, dropout, graph_scale, node_counts)
     cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
