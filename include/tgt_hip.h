@@ -189,6 +189,20 @@ int tgt_mask_node_counts(const float* mask, int32_t B, int32_t N, int32_t* count
  * writer of those columns.  Supported (tgt_triplet_aggregate_proj_supported, host only,
  * 1 / 0): C = 256, D = 16, H = 16, N <= 32, bf16 / fp16.  Checks before any launch: sizes (TGT_ERR_INVALID), the supported
  * predicate (TGT_ERR_UNSUPPORTED), then null / misaligned x / w / b / eg / mask / out, then e_off / g_off + H outside a row of ld_eg elements (TGT_ERR_INVALID).
+ *
+ * DropPath-dropped graphs: tgt_triplet_aggregate_fwd_skip / _bwd_skip / _proj_fwd_skip are the three entry points above plus
+ * graph_scale: (B) float32 DEVICE memory, the per-graph DropPath factor of the residual branch the call belongs to (see
+ * tgt_triplet_attention_args.graph_scale), or NULL (= the entry point without _skip, which forwards here with NULL and computes
+ * what it always did, bit for bit).  The argument block is unchanged, so the factor travels beside it as node_counts does.
+ * A graph whose factor is exactly 0 is not read or computed:
+ *   forward : the rows out[b] of both directions' column blocks are zeros (projection-fused forward: E/G rows parked inside
+ *             those columns of `out` are overwritten unread);
+ *   backward: d_out[b] is NOT READ; d_v[b] gets zeros in the V columns of both directions and d_eg[b] zeros in the E columns,
+ *             and in the G columns when TGT_TRI_GATED, of both directions.
+ * Every other graph is computed exactly as without the pointer: same strides, same order of every sum, same dropout unit
+ * (b*2 + dir)*H + h.  The factor itself is NOT applied.  Checks: those of the entry point without _skip, in the same order and
+ * words, then a graph_scale that is not 4-byte aligned (TGT_ERR_INVALID).  No entry point reads the factors on the host (no
+ * synchronisation, capturable).
  * ---------------------------------------------------------------------- */
 typedef struct tgt_triplet_aggregate_args {
     int32_t B, N, H, D;
@@ -213,6 +227,10 @@ int tgt_triplet_aggregate_bwd(const tgt_triplet_aggregate_args* a, void* stream)
 int tgt_triplet_aggregate_proj_supported(const tgt_triplet_aggregate_args* a, int32_t C);
 int tgt_triplet_aggregate_proj_fwd(const tgt_triplet_aggregate_args* a, const void* x, int32_t C, const void* w, const void* b,
                                    void* stream);
+int tgt_triplet_aggregate_fwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale, void* stream);
+int tgt_triplet_aggregate_bwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale, void* stream);
+int tgt_triplet_aggregate_proj_fwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale,
+                                        const void* x, int32_t C, const void* w, const void* b, void* stream);
 
 /* ------------------------------------------------------------------------
  * TriangularUpdate core (reference lib/tgt/layers/triplet.py:156-172: the four

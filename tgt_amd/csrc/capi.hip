@@ -25,7 +25,7 @@ int check_launch(const char* what) {
 int triplet_attention_run(const tgt_triplet_attention_args* a, const int32_t* node_counts, bool bwd, hipStream_t st);
 int mask_node_counts_run(const float* mask, int B, int N, int32_t* counts, hipStream_t st);
 int64_t tri_att_kb_workspace_bytes(const tgt_triplet_attention_args* a, int bwd);
-int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, bool bwd, hipStream_t st);
+int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, const float* graph_scale, bool bwd, hipStream_t st);
 int node_attention_run(const tgt_node_attention_args* a, bool bwd, hipStream_t st);
 int node_attention_family(const tgt_node_attention_args* a, bool bwd);
 int layer_norm_parts();
@@ -52,8 +52,8 @@ int triplet_attention_proj_supported(const tgt_triplet_attention_args* a, int C)
 int triplet_attention_proj_run(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x, int C, const void* w,
                                const void* bias, hipStream_t st);
 int triplet_aggregate_proj_supported(const tgt_triplet_aggregate_args* a, int C);
-int triplet_aggregate_proj_run(const tgt_triplet_aggregate_args* a, const void* x, int C, const void* w, const void* bias,
-                               hipStream_t st);
+int triplet_aggregate_proj_run(const tgt_triplet_aggregate_args* a, const float* graph_scale, const void* x, int C, const void* w,
+                               const void* bias, hipStream_t st);
 int fuse_rows_run(const tgt_fuse_rows_args* a, bool scatter, hipStream_t st);
 int permute_cols_run(const void* src, int sd, const int32_t* idx, void* dst, int dd, int rows, int cols, hipStream_t st);
 int sum_planes_run(const float* x, int planes, int64_t n, float* out, hipStream_t st);
@@ -114,11 +114,13 @@ int tgt_mask_node_counts(const float* mask, int32_t B, int32_t N, int32_t* count
     return mask_node_counts_run(mask, B, N, counts, reinterpret_cast<hipStream_t>(stream));
 }
 int64_t tgt_triplet_attention_workspace_bytes(const tgt_triplet_attention_args* a, int32_t bwd) { return tri_att_kb_workspace_bytes(a, bwd); }
-int tgt_triplet_aggregate_fwd(const tgt_triplet_aggregate_args* a, void* stream) {
-    return triplet_aggregate_run(a, false, reinterpret_cast<hipStream_t>(stream));
+int tgt_triplet_aggregate_fwd(const tgt_triplet_aggregate_args* a, void* stream) { return tgt_triplet_aggregate_fwd_skip(a, nullptr, stream); }
+int tgt_triplet_aggregate_bwd(const tgt_triplet_aggregate_args* a, void* stream) { return tgt_triplet_aggregate_bwd_skip(a, nullptr, stream); }
+int tgt_triplet_aggregate_fwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale, void* stream) {
+    return triplet_aggregate_run(a, graph_scale, false, reinterpret_cast<hipStream_t>(stream));
 }
-int tgt_triplet_aggregate_bwd(const tgt_triplet_aggregate_args* a, void* stream) {
-    return triplet_aggregate_run(a, true, reinterpret_cast<hipStream_t>(stream));
+int tgt_triplet_aggregate_bwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale, void* stream) {
+    return triplet_aggregate_run(a, graph_scale, true, reinterpret_cast<hipStream_t>(stream));
 }
 int tgt_node_attention_fwd(const tgt_node_attention_args* a, void* stream) {
     return node_attention_run(a, false, reinterpret_cast<hipStream_t>(stream));
@@ -197,7 +199,11 @@ int tgt_triplet_attention_proj_fwd_counts(const tgt_triplet_attention_args* a, c
 int tgt_triplet_aggregate_proj_supported(const tgt_triplet_aggregate_args* a, int32_t C) { return triplet_aggregate_proj_supported(a, C); }
 int tgt_triplet_aggregate_proj_fwd(const tgt_triplet_aggregate_args* a, const void* x, int32_t C, const void* w, const void* b,
                                    void* stream) {
-    return triplet_aggregate_proj_run(a, x, C, w, b, reinterpret_cast<hipStream_t>(stream));
+    return tgt_triplet_aggregate_proj_fwd_skip(a, nullptr, x, C, w, b, stream);
+}
+int tgt_triplet_aggregate_proj_fwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale, const void* x, int32_t C,
+                                        const void* w, const void* b, void* stream) {
+    return triplet_aggregate_proj_run(a, graph_scale, x, C, w, b, reinterpret_cast<hipStream_t>(stream));
 }
 int tgt_fuse_rows(const tgt_fuse_rows_args* a, void* stream) { return fuse_rows_run(a, false, reinterpret_cast<hipStream_t>(stream)); }
 int tgt_unfuse_rows(const tgt_fuse_rows_args* a, void* stream) { return fuse_rows_run(a, true, reinterpret_cast<hipStream_t>(stream)); }

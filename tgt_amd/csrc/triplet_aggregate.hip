@@ -30,8 +30,8 @@ __device__ __forceinline__ void agg_weights(const AggCtx& c, int N, int wave, in
     tile_softmax<NT>(p);
 }
 
-template <typename T, int D, int HG, int NT>
-__global__ void __launch_bounds__(HG * 64) tri_agg_fwd_kernel(const tgt_triplet_aggregate_args a) {
+template <typename T, int D, int HG, int NT, typename... GS>
+__global__ void __launch_bounds__(HG * 64) tri_agg_fwd_kernel(const tgt_triplet_aggregate_args a, GS... gs) {
     using G = TriGeo<T, D, HG>;
     using F = frag_t<T>;
     constexpr int KR = 32 * NT;
@@ -43,6 +43,12 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_fwd_kernel(const tgt_triplet_
     const int r = lane & 31, hi = lane >> 5;
     const AggCtx c = agg_ctx<HG>(a, wave);
     const int N = c.N;
+    // a graph DropPath dropped (triplet_common.hpp, agg_dead): zeros to this head group's O columns of every (i, j) row
+    if constexpr (sizeof...(GS) > 0) if (agg_dead(c.b, gs...)) {
+        const SlabBuf zO = agg_o_slab<T, D, HG>(a.out, a.ld_out, a.o_off[c.dir], c);
+        for (int i0 = 0; i0 < N; i0 += 32) slab_zero_units<G>(0, N, i0, N, tid, zO);
+        return;
+    }
     F ident_d[G::kDC];
     make_ident_d<T, G::kDC>(ident_d, r, hi);
     const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
@@ -100,8 +106,8 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_fwd_kernel(const tgt_triplet_
     }
 }
 
-template <typename T, int D, int HG, int NT>
-__global__ void __launch_bounds__(HG * 64) tri_agg_bwd_kernel(const tgt_triplet_aggregate_args a) {
+template <typename T, int D, int HG, int NT, typename... GS>
+__global__ void __launch_bounds__(HG * 64) tri_agg_bwd_kernel(const tgt_triplet_aggregate_args a, GS... gs) {
     using G = TriGeo<T, D, HG>;
     using F = frag_t<T>;
     constexpr int KR = 32 * NT;
@@ -111,6 +117,16 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_bwd_kernel(const tgt_triplet_
     const int r = lane & 31, hi = lane >> 5;
     const AggCtx c = agg_ctx<HG>(a, wave);
     const int N = c.N;
+    // a graph DropPath dropped receives an all-zero d_out, which is not read: zeros to this head group's d_v columns of every
+    // (j, k) row and, through the stage (several workgroups can share a 16-byte piece of a narrow E/G row), to its heads' E/G
+    // columns of d_eg
+    if constexpr (sizeof...(GS) > 0) if (agg_dead(c.b, gs...)) {
+        const SlabBuf zV = agg_v_slab<T, D, HG>(a.d_v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);
+        for (int j = 0; j < N; ++j) slab_store_zero<G, KR>(zV, j, 0, N, tid);
+        for (int i0 = 0; i0 < N; i0 += 32)
+            arm_stage_zero_grad<T, HG, NT>(c.ta, a.d_eg[c.dir], c.b, c.dir, c.g, N, i0, smem, wave, tid, r, hi);
+        return;
+    }
 
     F ident_d[G::kDC];
     make_ident_d<T, G::kDC>(ident_d, r, hi);
@@ -244,43 +260,69 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_bwd_kernel(const tgt_triplet_
     }
 }
 
-template <typename T, int D, int HG, int NT>
-static int launch_agg_nt(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) {
+template <typename T, int D, int HG, int NT, typename... GS>
+static int launch_agg_nt(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st, GS... gs) {
     using G = TriGeo<T, D, HG>;
     const int grid = a.B * 2 * (a.H / HG);
     constexpr int kArm = ArmStage<T, HG, NT>::kBytes;
     constexpr int kLds = 2 * (NT + 1) * G::kSlabBytes > kArm ? 2 * (NT + 1) * G::kSlabBytes : kArm;
-    if (!bwd) hipLaunchKernelGGL((tri_agg_fwd_kernel<T, D, HG, NT>), dim3(grid), dim3(G::kThreads), kLds, st, a);
-    else      hipLaunchKernelGGL((tri_agg_bwd_kernel<T, D, HG, NT>), dim3(grid), dim3(G::kThreads), kLds, st, a);
+    if (!bwd) hipLaunchKernelGGL((tri_agg_fwd_kernel<T, D, HG, NT, GS...>), dim3(grid), dim3(G::kThreads), kLds, st, a, gs...);
+    else      hipLaunchKernelGGL((tri_agg_bwd_kernel<T, D, HG, NT, GS...>), dim3(grid), dim3(G::kThreads), kLds, st, a, gs...);
     return check_launch(bwd ? "tri_agg_bwd_kernel" : "tri_agg_fwd_kernel");
 }
-template <typename T, int D, int HG>
-static int launch_agg(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) {
-    if (a.N <= 32) return launch_agg_nt<T, D, HG, 1>(a, bwd, st);
-    return launch_agg_nt<T, D, HG, 2>(a, bwd, st);
+template <typename T, int D, int HG, typename... GS>
+static int launch_agg(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st, GS... gs) {
+    if (a.N <= 32) return launch_agg_nt<T, D, HG, 1>(a, bwd, st, gs...);
+    return launch_agg_nt<T, D, HG, 2>(a, bwd, st, gs...);
 }
-template <typename T, int D>
-static int agg_dispatch_hg(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) {
+template <typename T, int D, typename... GS>
+static int agg_dispatch_hg(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st, GS... gs) {
     if constexpr (D == 16 && sizeof(T) == 2) {
-        if (a.H % 8 == 0 && a.N <= 32) return launch_agg_nt<T, D, 8, 1>(a, bwd, st);     // 256-byte row pieces
+        if (a.H % 8 == 0 && a.N <= 32) return launch_agg_nt<T, D, 8, 1>(a, bwd, st, gs...);     // 256-byte row pieces
     }
-    if (a.H % 4 == 0) return launch_agg<T, D, 4>(a, bwd, st);
-    if constexpr (D * sizeof(T) >= 16) return launch_agg<T, D, 1>(a, bwd, st);
+    if (a.H % 4 == 0) return launch_agg<T, D, 4>(a, bwd, st, gs...);
+    if constexpr (D * sizeof(T) >= 16) return launch_agg<T, D, 1>(a, bwd, st, gs...);
     return set_error(TGT_ERR_UNSUPPORTED, "triplet aggregate: H=%d not a multiple of 4 with D=%d", a.H, D);
 }
-template <typename T>
-static int agg_dispatch_d(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) {
+template <typename T, typename... GS>
+static int agg_dispatch_d(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st, GS... gs) {
     switch (a.D) {
-        case 8: return agg_dispatch_hg<T, 8>(a, bwd, st);
-        case 16: return agg_dispatch_hg<T, 16>(a, bwd, st);
-        case 32: return agg_dispatch_hg<T, 32>(a, bwd, st);
+        case 8: return agg_dispatch_hg<T, 8>(a, bwd, st, gs...);
+        case 16: return agg_dispatch_hg<T, 16>(a, bwd, st, gs...);
+        case 32: return agg_dispatch_hg<T, 32>(a, bwd, st, gs...);
         default: return set_error(TGT_ERR_UNSUPPORTED, "triplet aggregate: D=%d not in {8,16,32}", a.D);
     }
 }
 
-int tri_agg_kb_run(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st);      // triplet_aggregate_kb.hip: 65 <= N <= 128, D = 16
+int tri_agg_kb_run(const tgt_triplet_aggregate_args& a, const float* graph_scale, bool bwd, hipStream_t st);      // triplet_aggregate_kb.hip: 65 <= N <= 128, D = 16
 
-int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, bool bwd, hipStream_t st) {
+template <typename... GS>
+static int agg_dispatch_dtype(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st, GS... gs) {
+    switch (a.dtype) {
+        case TGT_F32: return agg_dispatch_d<float>(a, bwd, st, gs...);
+        case TGT_BF16: return agg_dispatch_d<bf16_t>(a, bwd, st, gs...);
+        case TGT_F16: return agg_dispatch_d<f16_t>(a, bwd, st, gs...);
+        default: return set_error(TGT_ERR_INVALID, "triplet aggregate: bad dtype %d", a.dtype);
+    }
+}
+
+// The kernels with the factors compile in a translation unit of their own (TGT_AGG_INST: bit 0 the kernels without factors and
+// the entry point, bit 1 the kernels with them): co-compiled with their siblings, every tri_agg_bwd_kernel WITHOUT the argument
+// came out of hipcc with another scalar register allocation and more spills than it was measured with.
+#ifndef TGT_AGG_INST
+#define TGT_AGG_INST 3
+#endif
+int triplet_aggregate_skip_run(const tgt_triplet_aggregate_args& a, const float* graph_scale, bool bwd, hipStream_t st);
+#if TGT_AGG_INST & 2
+// N <= 64, arguments already validated by triplet_aggregate_run, graph_scale not NULL
+int triplet_aggregate_skip_run(const tgt_triplet_aggregate_args& a, const float* graph_scale, bool bwd, hipStream_t st) {
+    return agg_dispatch_dtype(a, bwd, st, graph_scale);
+}
+#endif
+
+#if TGT_AGG_INST & 1
+// graph_scale: (B) float32 device memory or NULL (tgt_triplet_aggregate_fwd_skip / _bwd_skip); never read on the host
+int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, const float* graph_scale, bool bwd, hipStream_t st) {
     if (!a) return set_error(TGT_ERR_INVALID, "triplet aggregate: null args");
     if (a->B < 0 || a->N < 0 || a->H <= 0) return set_error(TGT_ERR_INVALID, "triplet aggregate: bad sizes");
     if (a->B == 0 || a->N == 0) return TGT_OK;
@@ -296,13 +338,11 @@ int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, bool bwd, hipStre
         if (bwd && (!a->d_out || !a->d_v[dir] || !a->d_eg[dir] || ((uintptr_t)a->d_v[dir] % 16) || ((uintptr_t)a->d_out % 16)))
             return set_error(TGT_ERR_INVALID, "triplet aggregate bwd: null/misaligned gradient tensor");
     }
-    if (a->N > 64) return tri_agg_kb_run(*a, bwd, st);                             // key-blocked kernels
-    switch (a->dtype) {
-        case TGT_F32: return agg_dispatch_d<float>(*a, bwd, st);
-        case TGT_BF16: return agg_dispatch_d<bf16_t>(*a, bwd, st);
-        case TGT_F16: return agg_dispatch_d<f16_t>(*a, bwd, st);
-        default: return set_error(TGT_ERR_INVALID, "triplet aggregate: bad dtype %d", a->dtype);
-    }
+    if ((uintptr_t)graph_scale % 4) return set_error(TGT_ERR_INVALID, "triplet aggregate: graph_scale must be 4-byte aligned");
+    if (a->N > 64) return tri_agg_kb_run(*a, graph_scale, bwd, st);                // key-blocked kernels
+    // (without factors: the kernels' instantiations without the argument)
+    return graph_scale ? triplet_aggregate_skip_run(*a, graph_scale, bwd, st) : agg_dispatch_dtype(*a, bwd, st);
 }
+#endif
 
 }  // namespace tgt

@@ -57,8 +57,8 @@ __device__ __forceinline__ f32x16 agg_kb_dropped(const float (&p)[16], const flo
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
-template <typename T, int HG>
-__global__ void __launch_bounds__(HG * 64) tri_agg_kb_fwd_kernel(const tgt_triplet_aggregate_args a) {
+template <typename T, int HG, typename... GS>
+__global__ void __launch_bounds__(HG * 64) tri_agg_kb_fwd_kernel(const tgt_triplet_aggregate_args a, GS... gs) {
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
     // two LDS sets {V (128 rows) | O (32)}: set j&1 is computed on while slab j+1 lands in the other one -> ONE barrier per j
@@ -68,6 +68,11 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_fwd_kernel(const tgt_tripl
     const int r = lane & 31, hi = lane >> 5;
     const AggCtx c = agg_ctx<HG, true>(a, wave);
     const int N = c.N, i0 = 32 * c.tile;
+    // a graph DropPath dropped (triplet_common.hpp, agg_dead): zeros to the O rows i0..i0+31 of this head group for every j
+    if constexpr (sizeof...(GS) > 0) if (agg_dead(c.b, gs...)) {
+        slab_zero_units<G>(0, N, i0, N, tid, agg_o_slab<T, 16, HG>(a.out, a.ld_out, a.o_off[c.dir], c));
+        return;
+    }
     F ident_d[1];
     make_ident_d<T, 1>(ident_d, r, hi);
     const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
@@ -117,8 +122,8 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_fwd_kernel(const tgt_tripl
 // ---------------------------------------------------------------------------
 // backward, A sweep: dE / dG of (query tile, all keys)
 // ---------------------------------------------------------------------------
-template <typename T, int HG>
-__global__ void __launch_bounds__(HG * 64) tri_agg_kb_bwd_a_kernel(const tgt_triplet_aggregate_args a) {
+template <typename T, int HG, typename... GS>
+__global__ void __launch_bounds__(HG * 64) tri_agg_kb_bwd_a_kernel(const tgt_triplet_aggregate_args a, GS... gs) {
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -127,6 +132,13 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_bwd_a_kernel(const tgt_tri
     const int r = lane & 31, hi = lane >> 5;
     const AggCtx c = agg_ctx<HG, true>(a, wave);
     const int N = c.N, i0 = 32 * c.tile;
+    // a graph DropPath dropped: d_out is not read, zeros to the d_eg rows of this query tile, key tile by key tile through the
+    // stage as the live store below
+    if constexpr (sizeof...(GS) > 0) if (agg_dead(c.b, gs...)) {
+        for (int kt = 0; 32 * kt < N; ++kt)
+            arm_stage_zero_grad<T, HG, 1>(c.ta, a.d_eg[c.dir], c.b, c.dir, c.g, N, i0, smem, wave, tid, r, hi, 32 * kt);
+        return;
+    }
     const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
     const uint32_t drop_unit = (uint32_t)((c.b * 2 + c.dir) * a.H + c.h);
     const SlabBuf bV = agg_v_slab<T, 16, HG>(a.v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);
@@ -211,8 +223,8 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_bwd_a_kernel(const tgt_tri
 // (blockIdx.y picks which): 4 = all of them for the 16-bit types; fp32 fragments are twice the size and sixteen weight
 // tiles of them spill, so fp32 takes 2 and twice the workgroups.
 // ---------------------------------------------------------------------------
-template <typename T, int HG, int KT>
-__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_agg_kb_bwd_v_kernel(const tgt_triplet_aggregate_args a) {
+template <typename T, int HG, int KT, typename... GS>
+__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_agg_kb_bwd_v_kernel(const tgt_triplet_aggregate_args a, GS... gs) {
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -223,6 +235,12 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     const int N = c.N, j0 = 32 * c.tile, j1 = j0 + 32 < N ? j0 + 32 : N;
     const int kpart = blockIdx.y;                         // owns key tiles [KT*kpart, KT*kpart + KT)
     if (32 * KT * kpart >= N) return;                     // (the whole workgroup, before any barrier)
+    // a graph DropPath dropped: d_out is not read, zeros to the rows the store below owns -- the keys of `kpart` of its 32 j
+    if constexpr (sizeof...(GS) > 0) if (agg_dead(c.b, gs...)) {
+        const SlabBuf zV = agg_v_slab<T, 16, HG>(a.d_v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);
+        for (int j = j0; j < j1; ++j) slab_store_zero<G, 32 * KT>(zV, j, 32 * KT * kpart, N, tid);
+        return;
+    }
     F ident_d[1];
     make_ident_d<T, 1>(ident_d, r, hi);
     const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
@@ -310,23 +328,25 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-template <typename T, int HG>
-static int launch_agg_kb(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) {
+template <typename T, int HG, typename... GS>
+static int launch_agg_kb(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st, GS... gs) {
     using G = TriGeo<T, 16, HG>;
     const int grid = a.B * 2 * (a.H / HG) * ((a.N + 31) / 32);
     constexpr int kArm = ArmStage<T, HG, 1>::kBytes;
     constexpr int kWalkLds = cmax(10 * G::kSlabBytes, kArm), kVLds = cmax(8 * G::kSlabBytes, kArm);
     static_assert(kWalkLds <= 160 * 1024 && kVLds <= 160 * 1024, "LDS of a CU");
-    if (!bwd) return launch_lds<tri_agg_kb_fwd_kernel<T, HG>>("tri_agg_kb_fwd_kernel", dim3(grid), dim3(G::kThreads), kWalkLds, st, a);
+    if (!bwd) return launch_lds<tri_agg_kb_fwd_kernel<T, HG, GS...>>("tri_agg_kb_fwd_kernel", dim3(grid), dim3(G::kThreads), kWalkLds, st, a, gs...);
     constexpr int KT = sizeof(T) == 2 ? 4 : 2;
     // (both reservations before the first launch: a failed one leaves nothing half-written)
-    if (int rc = reserve_lds<tri_agg_kb_bwd_a_kernel<T, HG>>("tri_agg_kb_bwd_a_kernel", kWalkLds)) return rc;
-    if (int rc = reserve_lds<tri_agg_kb_bwd_v_kernel<T, HG, KT>>("tri_agg_kb_bwd_v_kernel", kVLds)) return rc;
-    if (int rc = launch_lds<tri_agg_kb_bwd_a_kernel<T, HG>>("tri_agg_kb_bwd_a_kernel", dim3(grid), dim3(G::kThreads), kWalkLds, st, a)) return rc;
-    return launch_lds<tri_agg_kb_bwd_v_kernel<T, HG, KT>>("tri_agg_kb_bwd_v_kernel", dim3(grid, 4 / KT), dim3(G::kThreads), kVLds, st, a);
+    if (int rc = reserve_lds<tri_agg_kb_bwd_a_kernel<T, HG, GS...>>("tri_agg_kb_bwd_a_kernel", kWalkLds)) return rc;
+    if (int rc = reserve_lds<tri_agg_kb_bwd_v_kernel<T, HG, KT, GS...>>("tri_agg_kb_bwd_v_kernel", kVLds)) return rc;
+    if (int rc = launch_lds<tri_agg_kb_bwd_a_kernel<T, HG, GS...>>("tri_agg_kb_bwd_a_kernel", dim3(grid), dim3(G::kThreads), kWalkLds, st, a, gs...)) return rc;
+    return launch_lds<tri_agg_kb_bwd_v_kernel<T, HG, KT, GS...>>("tri_agg_kb_bwd_v_kernel", dim3(grid, 4 / KT), dim3(G::kThreads), kVLds, st, a, gs...);
 }
+// graph_scale NULL: the kernels' instantiations without the argument (triplet_common.hpp, agg_dead)
 template <typename T>
-static int dispatch_agg_kb(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) {
+static int dispatch_agg_kb(const tgt_triplet_aggregate_args& a, const float* graph_scale, bool bwd, hipStream_t st) {
+    if (graph_scale) return a.H % 4 == 0 ? launch_agg_kb<T, 4>(a, bwd, st, graph_scale) : launch_agg_kb<T, 1>(a, bwd, st, graph_scale);
     if (a.H % 4 == 0) return launch_agg_kb<T, 4>(a, bwd, st);
     return launch_agg_kb<T, 1>(a, bwd, st);
 }
@@ -336,26 +356,26 @@ static int dispatch_agg_kb(const tgt_triplet_aggregate_args& a, bool bwd, hipStr
 #ifndef TGT_AGGKB_INST
 #define TGT_AGGKB_INST 15
 #endif
-int tri_agg_kb_run_f32(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st);
-int tri_agg_kb_run_bf16(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st);
-int tri_agg_kb_run_f16(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st);
+int tri_agg_kb_run_f32(const tgt_triplet_aggregate_args& a, const float* graph_scale, bool bwd, hipStream_t st);
+int tri_agg_kb_run_bf16(const tgt_triplet_aggregate_args& a, const float* graph_scale, bool bwd, hipStream_t st);
+int tri_agg_kb_run_f16(const tgt_triplet_aggregate_args& a, const float* graph_scale, bool bwd, hipStream_t st);
 #if TGT_AGGKB_INST & 1
-int tri_agg_kb_run_f32(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) { return dispatch_agg_kb<float>(a, bwd, st); }
+int tri_agg_kb_run_f32(const tgt_triplet_aggregate_args& a, const float* graph_scale, bool bwd, hipStream_t st) { return dispatch_agg_kb<float>(a, graph_scale, bwd, st); }
 #endif
 #if TGT_AGGKB_INST & 2
-int tri_agg_kb_run_bf16(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) { return dispatch_agg_kb<bf16_t>(a, bwd, st); }
+int tri_agg_kb_run_bf16(const tgt_triplet_aggregate_args& a, const float* graph_scale, bool bwd, hipStream_t st) { return dispatch_agg_kb<bf16_t>(a, graph_scale, bwd, st); }
 #endif
 #if TGT_AGGKB_INST & 4
-int tri_agg_kb_run_f16(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) { return dispatch_agg_kb<f16_t>(a, bwd, st); }
+int tri_agg_kb_run_f16(const tgt_triplet_aggregate_args& a, const float* graph_scale, bool bwd, hipStream_t st) { return dispatch_agg_kb<f16_t>(a, graph_scale, bwd, st); }
 #endif
 
 #if TGT_AGGKB_INST & 8
 // 65 <= N <= 128, D = 16, arguments already validated by triplet_aggregate_run
-int tri_agg_kb_run(const tgt_triplet_aggregate_args& a, bool bwd, hipStream_t st) {
+int tri_agg_kb_run(const tgt_triplet_aggregate_args& a, const float* graph_scale, bool bwd, hipStream_t st) {
     switch (a.dtype) {
-        case TGT_F32: return tri_agg_kb_run_f32(a, bwd, st);
-        case TGT_BF16: return tri_agg_kb_run_bf16(a, bwd, st);
-        case TGT_F16: return tri_agg_kb_run_f16(a, bwd, st);
+        case TGT_F32: return tri_agg_kb_run_f32(a, graph_scale, bwd, st);
+        case TGT_BF16: return tri_agg_kb_run_bf16(a, graph_scale, bwd, st);
+        case TGT_F16: return tri_agg_kb_run_f16(a, graph_scale, bwd, st);
         default: return set_error(TGT_ERR_INVALID, "triplet aggregate: bad dtype %d", a.dtype);
     }
 }

@@ -37,9 +37,9 @@ struct Geo : TriGeo<T, kD, kH> {
 };
 }  // namespace aggproj
 
-template <typename T>
+template <typename T, typename... GS>
 __global__ void __launch_bounds__(aggproj::kThreads, 4) tri_agg_proj_fwd_kernel(const tgt_triplet_aggregate_args a, const T* x, const T* w,
-                                                                             const T* bias) {
+                                                                             const T* bias, GS... gs) {
     using namespace aggproj;
     using G = Geo<T>;
     using F = frag_t<T>;
@@ -48,6 +48,12 @@ __global__ void __launch_bounds__(aggproj::kThreads, 4) tri_agg_proj_fwd_kernel(
     const int r = lane & 31, hi = lane >> 5;
     const AggCtx c = agg_ctx<kH>(a, 0);                      // one head group: blockIdx.x = b*2 + dir
     const int N = c.N, dir = c.dir;
+    // a graph DropPath dropped (triplet_common.hpp, agg_dead): zeros to this direction's C columns of every row of the graph.  Its
+    // E/G, where they wait inside those columns, are overwritten unread: only this workgroup would have read them.
+    if constexpr (sizeof...(GS) > 0) if (agg_dead(c.b, gs...)) {
+        slab_zero_units<G>(0, N, 0, N, tid, agg_o_slab<T, kD, kH>(a.out, a.ld_out, a.o_off[dir], c));
+        return;
+    }
     const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
 
     // ---- the weights A[i,k] of the two heads, once (the stage aliases the walk's buffers).
@@ -164,15 +170,16 @@ int triplet_aggregate_proj_supported(const tgt_triplet_aggregate_args* a, int C)
            C == aggproj::kC;
 }
 
-template <typename T>
-static int launch_agg_proj(const tgt_triplet_aggregate_args& a, const void* x, const void* w, const void* bias, hipStream_t st) {
+template <typename T, typename... GS>
+static int launch_agg_proj(const tgt_triplet_aggregate_args& a, const void* x, const void* w, const void* bias, hipStream_t st, GS... gs) {
     constexpr int kArm = ArmStage<T, aggproj::kH, 1>::kBytes;
     constexpr int kLds = cmax(aggproj::kWalk, kArm);
-    return launch_lds<tri_agg_proj_fwd_kernel<T>>("tri_agg_proj_fwd_kernel", dim3(a.B * 2), dim3(aggproj::kThreads), kLds, st, a,
-                                                  reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias));
+    return launch_lds<tri_agg_proj_fwd_kernel<T, GS...>>("tri_agg_proj_fwd_kernel", dim3(a.B * 2), dim3(aggproj::kThreads), kLds, st, a,
+                                                         reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias), gs...);
 }
 
-int triplet_aggregate_proj_run(const tgt_triplet_aggregate_args* a, const void* x, int C, const void* w, const void* bias, hipStream_t st) {
+int triplet_aggregate_proj_run(const tgt_triplet_aggregate_args* a, const float* graph_scale, const void* x, int C, const void* w, const void* bias,
+                               hipStream_t st) {
     if (!a) return set_error(TGT_ERR_INVALID, "projected triplet aggregate: null args");
     if (a->B < 0 || a->N < 0 || a->H <= 0 || C <= 0) return set_error(TGT_ERR_INVALID, "projected triplet aggregate: bad sizes");
     if (!triplet_aggregate_proj_supported(a, C))
@@ -190,6 +197,9 @@ int triplet_aggregate_proj_run(const tgt_triplet_aggregate_args* a, const void* 
         if (a->ld_eg[dir] < aggproj::kH || a->e_off[dir] < 0 || a->e_off[dir] + aggproj::kH > a->ld_eg[dir] ||
             (gated && (a->g_off[dir] < 0 || a->g_off[dir] + aggproj::kH > a->ld_eg[dir])))
             return set_error(TGT_ERR_INVALID, "projected triplet aggregate: e_off / g_off + H outside the E/G row (ld_eg=%lld)", (long long)a->ld_eg[dir]);
+    if ((uintptr_t)graph_scale % 4) return set_error(TGT_ERR_INVALID, "projected triplet aggregate: graph_scale must be 4-byte aligned");
+    // (without factors: the kernel's instantiation without the argument -- triplet_common.hpp, agg_dead)
+    if (graph_scale) return a->dtype == TGT_BF16 ? launch_agg_proj<bf16_t>(*a, x, w, bias, st, graph_scale) : launch_agg_proj<f16_t>(*a, x, w, bias, st, graph_scale);
     return a->dtype == TGT_BF16 ? launch_agg_proj<bf16_t>(*a, x, w, bias, st) : launch_agg_proj<f16_t>(*a, x, w, bias, st);
 }
 

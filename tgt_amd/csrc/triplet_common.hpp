@@ -594,6 +594,29 @@ __device__ __forceinline__ AggCtx agg_ctx(const tgt_triplet_aggregate_args& a, i
                     true, (a.flags & TGT_TRI_GATED) != 0};
     return c;
 }
+// A graph DropPath dropped (tgt_hip.h, tgt_triplet_aggregate_*_skip: graph_scale[b] == 0): its workgroups read and compute
+// nothing and write zeros to what they own.  Workgroup-uniform (b comes from blockIdx): one scalar load, tested before the first
+// barrier.  The factors are a trailing parameter pack `GS... gs` of every aggregate kernel, as the attention kernels' counts
+// (`NC... nc` above): a call without factors launches the instantiation with the empty pack, whose argument list and
+// instruction stream are the ones the kernel had before the factors existed; with them the pack is one `const float*`, never null.
+// The test sits behind `if constexpr (sizeof...(GS) > 0)`: the dead branch is not even instantiated without factors (merely
+// folded away as dead code, it still moved the register allocation of every tri_agg_bwd_kernel).
+__device__ __forceinline__ bool agg_dead(int b, const float* graph_scale) { return graph_scale[b] == 0.f; }
+// zeros to the E/G gradient columns of this head group for the staged pair region of pass (i0, k0): the staged path of the live
+// kernels (arm_stage_put_grad / arm_stage_store_grad) with a zero tile per head, so the ownership map of the store is theirs.
+// Two barriers; `lds` is the stage.
+template <typename T, int HG, int NT>
+__device__ __forceinline__ void arm_stage_zero_grad(const ThirdArm& ta, void* d_eg, int b, int dir, int g, int N, int i0, char* lds,
+                                                    int wave, int tid, int r, int hi, int k0 = 0) {
+    float z[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) z[q] = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt) arm_stage_put_grad<T, HG, NT>(lds, dir, wave, r, hi, kt, z, z);
+    __syncthreads();
+    arm_stage_store_grad<T, HG, NT>(ta, d_eg, b, dir, g, N, i0, lds, tid, k0);
+    __syncthreads();
+}
 // buffer-addressed slabs: rows k of V[j,k] (inward) / V[k,j] (outward) of this head group
 template <typename T, int D, int HG>
 __device__ __forceinline__ SlabBuf agg_v_slab(const void* tensor, int64_t ld, int off, const AggCtx& c) {

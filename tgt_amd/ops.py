@@ -802,18 +802,36 @@ def _agg_args(fused, mask3, out, L, d_out=None, d_fused=None, dropout=(0.0, 0)):
     return a
 
 
+def _check_agg_graph_scale(graph_scale, B):
+    """per-graph DropPath factor of the triplet aggregate kernels (tgt_hip.h, tgt_triplet_aggregate_fwd_skip): checked as _tri_args
+    checks the attention's; the values stay on the device"""
+    if graph_scale is not None and (graph_scale.dtype != torch.float32 or graph_scale.numel() != B or not graph_scale.is_contiguous() or
+                                    not graph_scale.is_cuda):
+        raise RuntimeError('triplet aggregate: graph_scale must be a contiguous float32 device tensor with one value per graph')
+    return graph_scale
+
+
+def _call_skip(name, args, graph_scale):
+    """tgt_triplet_aggregate_fwd / _bwd (`name`), through the _skip entry point when DropPath factors are given"""
+    if graph_scale is None:
+        return _call(name, getattr(_lib.lib(), name), args)
+    fn = getattr(_lib.lib(), name + '_skip')
+    _call(name, lambda a, st: fn(a, _ptr(graph_scale), st), args)
+
+
 class _TripletAggregate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, fused, mask3, L, dropout=(0.0, 0)):
+    def forward(ctx, fused, mask3, L, dropout=(0.0, 0), graph_scale=None):
         _dev(fused, mask3)
         fused = fused.contiguous()
         B, N = fused.shape[0], fused.shape[1]
         assert fused.shape == (B, N, N, L.width), (fused.shape, L.width)
         out = torch.empty(B, N, N, 2 * L.C, dtype=fused.dtype, device=fused.device)
         a = _agg_args(fused, mask3, out, L, dropout=dropout)
-        _call('tgt_triplet_aggregate_fwd', _lib.lib().tgt_triplet_aggregate_fwd, a)
+        _call_skip('tgt_triplet_aggregate_fwd', a, _check_agg_graph_scale(graph_scale, B))
         ctx.save_for_backward(fused, mask3, out)
         ctx.L, ctx.dropout = L, dropout
+        ctx.graph_scale = graph_scale if _TRI_SKIP_BWD else None       # (as _TripletAttention: the backward skips with TGT_TRI_SKIP=2)
         return out
 
     @staticmethod
@@ -824,13 +842,16 @@ class _TripletAggregate(torch.autograd.Function):
         if ctx.L.width > ctx.L.used:
             d_fused[..., ctx.L.used:] = 0
         a = _agg_args(fused, mask3, out, ctx.L, d_out, d_fused, dropout=ctx.dropout)
-        _call('tgt_triplet_aggregate_bwd', _lib.lib().tgt_triplet_aggregate_bwd, a)
-        return d_fused, None, None, None
+        _call_skip('tgt_triplet_aggregate_bwd', a, ctx.graph_scale)
+        return d_fused, None, None, None, None
 
 
-def triplet_aggregate(fused, mask3, layout, dropout=(0.0, 0)):
-    """Reference arithmetic: lib/tgt/layers/triplet.py:56-70 / :107-123; dropout as triplet_attention."""
-    return _TripletAggregate.apply(fused, mask3, layout, dropout)
+def triplet_aggregate(fused, mask3, layout, dropout=(0.0, 0), graph_scale=None):
+    """Reference arithmetic: lib/tgt/layers/triplet.py:56-70 / :107-123; dropout as triplet_attention.
+    graph_scale (B,) float32 as triplet_attention's: the DropPath factor of the residual branch the result feeds (drawn and
+    applied by the caller).  Graphs whose factor is exactly 0 are skipped by the forward -- zeros out -- and, with TGT_TRI_SKIP=2,
+    by the backward -- zero gradients, their incoming gradient is not read (it MUST be zero, as it is behind that multiplication)."""
+    return _TripletAggregate.apply(fused, mask3, layout, dropout, graph_scale)
 
 
 def _agg_proj_ok(x, N, L, cd):
@@ -864,21 +885,24 @@ def _agg_proj_args(eg, mask3, out, L, dropout=(0.0, 0)):
     return a
 
 
-def projected_triplet_aggregate(x, params, mask3, layout, table, dropout=(0.0, 0)):
-    """triplet_aggregate(fused_linear(x, table, params), mask3, layout, dropout).  params: the module's nn.Linear parameters
+def projected_triplet_aggregate(x, params, mask3, layout, table, dropout=(0.0, 0), graph_scale=None):
+    """triplet_aggregate(fused_linear(x, table, params), mask3, layout, dropout, graph_scale).  params: the module's nn.Linear parameters
     (lin_V.weight, lin_V.bias, lin_E(G).weight, lin_E(G).bias).  A call that no backward can follow (torch.no_grad(), or nothing
     requires grad) projects V inside the aggregate kernel where _agg_proj_ok holds: only the narrow E/G rows are projected
-    beforehand, into columns of the result itself, and no fused row is allocated (TGT_AGG_PROJ_INFER is the A/B knob)."""
+    beforehand, into columns of the result itself, and no fused row is allocated (TGT_AGG_PROJ_INFER is the A/B knob).
+    graph_scale: see triplet_aggregate; both paths skip the dropped graphs in the aggregate kernel (the projections that run as
+    library GEMMs still cover every graph)."""
     L = layout
     cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
     # (whether a backward can follow is decided as in projected_triplet_attention)
     no_backward = not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, *params)))
     N = x.shape[1]
     if not (no_backward and _AGG_PROJ_INFER and _agg_proj_ok(x, N, L, cd)):
-        return triplet_aggregate(fused_linear(x, table, params), mask3, L, dropout)
+        return triplet_aggregate(fused_linear(x, table, params), mask3, L, dropout, graph_scale)
     with torch.no_grad():
         _dev(x, mask3)
         B = x.shape[0]
+        _check_agg_graph_scale(graph_scale, B)
         w, b = _fuse_params(table, params, cd)
         x2 = x.reshape(-1, L.C)
         x2 = (x2 if x2.dtype == cd else x2.to(cd)).contiguous()
@@ -891,8 +915,11 @@ def projected_triplet_aggregate(x, params, mask3, layout, table, dropout=(0.0, 0
             torch.addmm(be, x2, we.t(), out=egv)
         a = _agg_proj_args(out, mask3, out, L, dropout)
         s0, s1 = _prof_begin('tgt_triplet_aggregate_proj_fwd')
-        _lib.check(_lib.lib().tgt_triplet_aggregate_proj_fwd(C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), _stream()),
-                   'tgt_triplet_aggregate_proj_fwd')
+        if graph_scale is None:
+            rc = _lib.lib().tgt_triplet_aggregate_proj_fwd(C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), _stream())
+        else:
+            rc = _lib.lib().tgt_triplet_aggregate_proj_fwd_skip(C.byref(a), _ptr(graph_scale), _ptr(x2), L.C, _ptr(w), _ptr(b), _stream())
+        _lib.check(rc, 'tgt_triplet_aggregate_proj_fwd')
         _prof_end('tgt_triplet_aggregate_proj_fwd', s0, s1)
     return out
 

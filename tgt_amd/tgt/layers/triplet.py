@@ -176,16 +176,21 @@ class TripletAggregate(_TripletBase):
     def forward(self, e, mask):
         return self.forward_normed(self.tri_ln_e(e), mask)
 
-    def forward_normed(self, x, mask):
-        return self._out_proj(self.attend(x, mask))
+    takes_graph_scale = True          # forward_normed(..., graph_scale=): DropPath-dropped graphs are not computed
+
+    def forward_normed(self, x, mask, graph_scale=None):
+        """the block after tri_ln_e; graph_scale as TripletAttention.forward_normed"""
+        return self._out_proj(self.attend(x, mask, graph_scale))
 
     def attend(self, x, mask, graph_scale=None):
-        """forward_normed without lin_O (see TripletAttention.attend; the aggregate kernels compute every graph)"""
+        """forward_normed without lin_O (see TripletAttention.attend).  graph_scale (B,) float32: the DropPath factor the CALLER
+        multiplies the block's result with at the residual add; graphs whose factor is 0 are skipped by the aggregate kernels
+        (ops.triplet_aggregate)"""
         B, N = x.shape[0], x.shape[1]
         lin_b = self.lin_EG if self.gated else self.lin_E
         return ops.projected_triplet_aggregate(x, (self.lin_V.weight, self.lin_V.bias, lin_b.weight, lin_b.bias),
                                                ops.as_mask3(mask, B, N), self._layout, self._table,
-                                               ops.draw_dropout(self.attention_dropout, self.training))
+                                               ops.draw_dropout(self.attention_dropout, self.training), graph_scale=graph_scale)
 
 
 class TripletAggregateUngated(TripletAggregate):
