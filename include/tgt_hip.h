@@ -22,6 +22,9 @@
  *    the node-attention ops take the reference's HEAD-MINOR channels
  *    (c = d*H + h).  The Python mirror permutes the projection weights, not
  *    the activations, to get head-major triplet operands.
+ *  - ragged batches: what a padded node or a padded edge row would compute may be left out on request -- per-graph node
+ *    counts beside the argument block (tgt_triplet_attention_*_counts), a live tile list beside it (tgt_edge_linear_live);
+ *    both are permissions to skip, never obligations, and a NULL pointer is the plain entry point.
  */
 #ifndef TGT_HIP_H
 #define TGT_HIP_H
@@ -440,6 +443,29 @@ int tgt_edge_linear_supported(const tgt_edge_linear_args* a);
 int tgt_edge_linear_parts(int64_t M, int32_t N);
 int tgt_edge_linear(const tgt_edge_linear_args* a, void* stream);
 void tgt_edge_linear_set_grid_cap(int32_t cap);
+
+/* Ragged batches: the padded rows of the edge tensors are not computed (csrc/edge_live.hip; no reference counterpart -- the
+ * reference computes every padded position).  Row r of a (B*N*N, C) edge tensor is the pair (b, i, j) = (r / N^2, (r % N^2) / N,
+ * r % N); it is DEAD when i >= n_b or j >= n_b, n_b = clamp(node_counts[b], 0, N) (clamped in the kernel).  The 32-row tile t =
+ * rows [32 t, 32 t + 32) is dead when every one of its rows is dead or at / past M = B*N*N.
+ * tgt_edge_live_tiles: tiles = int32 DEVICE memory, 1 + ceil(M / 32) entries: tiles[0] = number of live tiles, then the live tile
+ *   indices ascending, then the dead ones ascending.  One small launch, deterministic, nothing read on the host (capturable).
+ * tgt_edge_linear_live: tgt_edge_linear on the live tiles only.  The grid is the one tgt_edge_linear uses (colsum_rows,
+ *   tgt_edge_linear_parts and the grid-cap hook keep their meaning); workgroup w walks tiles[1 + w + s * grid] while that index
+ *   is below tiles[0], so the live tiles are dealt round-robin; the dead tiles are dealt the same way from the tail of the list
+ *   and get ZEROS in every output the epilogue defines (out, out2, y, mean, rstd) -- no operand of a dead tile is read.  A
+ *   workgroup without live tiles still writes its colsum_partial row (zeros).  tiles == NULL: tgt_edge_linear.
+ *   Contract: rows of live tiles are bit-identical to tgt_edge_linear (dropout draws by absolute element); colsum_partial
+ *   regroups rows over workgroups, so its totals equal tgt_edge_linear's up to fp32 summation order (bit-reproducible run to run).
+ *   The caller vouches that the dead rows do not matter: forward, a padded row reaches a real one only through keys the mask
+ *   closes; backward, its cotangent out of a masked loss is exactly zero -- and zero is what its outputs get here.
+ * tgt_edge_linear_live_supported: the launches that take a list -- the 32-row-tile kernels: N = 256 with a whole-row epilogue
+ *   (GELU, RESID [+ LayerNorm], GELU_BWD, LN_BWD; K in {64,128,256}), K = 512 -> 256 (RESID), 256 -> 512 plain, TGT_EPI_GLU.
+ *   Not with dw_partial, not the shapes of the 64 / 128-row slice kernel: tgt_edge_linear_live answers those with
+ *   TGT_ERR_UNSUPPORTED before any launch. */
+int tgt_edge_live_tiles(const int32_t* node_counts, int32_t B, int32_t N, int32_t* tiles, void* stream);
+int tgt_edge_linear_live_supported(const tgt_edge_linear_args* a);
+int tgt_edge_linear_live(const tgt_edge_linear_args* a, const int32_t* tiles, void* stream);
 
 /* ------------------------------------------------------------------------
  * LayerNorm over the last axis (the five per-layer norms of the TGT layer:

@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, 'libtgt_hip.so')
 LIB_OVERRIDE = os.environ.get('TGT_HIP_LIB')
 CSRC = os.path.join(_HERE, 'csrc')
 # (source, extra flags, object suffix): the triplet attention kernels compile one dtype per translation unit
-SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_wgrad.hip', 'params.hip', 'loss.hip', 'predict.hip', 'gaussian.hip', 'triplet_attention_proj.hip',
+SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_live.hip', 'edge_wgrad.hip', 'params.hip', 'loss.hip', 'predict.hip', 'gaussian.hip', 'triplet_attention_proj.hip',
            ('triplet_attention.hip', ['-DTGT_TRI_INST=9'], '.f32'), ('triplet_attention.hip', ['-DTGT_TRI_INST=2'], '.bf16'),
            ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip', 'triplet_attention_bwd2.hip',
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=9'], '.f32'), ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=2'], '.bf16'),
@@ -166,6 +166,9 @@ SYMBOLS = {
     'tgt_edge_linear_parts': (C.c_int, [_i64, _i32]),
     'tgt_edge_linear': (C.c_int, [C.POINTER(EdgeLinearArgs), _vp]),
     'tgt_edge_linear_set_grid_cap': (None, [_i32]),
+    'tgt_edge_live_tiles': (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    'tgt_edge_linear_live_supported': (C.c_int, [C.POINTER(EdgeLinearArgs)]),
+    'tgt_edge_linear_live': (C.c_int, [C.POINTER(EdgeLinearArgs), _vp, _vp]),
     'tgt_adam_step': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _vp, _vp, _i32, _vp]),
     'tgt_grad_stats_parts': (C.c_int, []),
     'tgt_grad_scaler_step': (C.c_int, [_vp, _i64, _vp, _vp, _i32, _f32, _f32, _i32, _f32, _f32, _i32, _vp]),

@@ -63,7 +63,9 @@ int xent_run(const void* x, int dtype, const int64_t* target, const float* lse_i
              float* lse, float* xent, void* dx, hipStream_t st);
 int edge_linear_supported(const tgt_edge_linear_args* a);
 int edge_linear_parts(int64_t M, int N);
-int edge_linear_run(const tgt_edge_linear_args* a, hipStream_t st);
+int edge_linear_run(const tgt_edge_linear_args* a, hipStream_t st, const int32_t* tiles);
+int edge_linear_live_supported(const tgt_edge_linear_args* a);
+int edge_live_tiles_run(const int32_t* node_counts, int B, int N, int32_t* tiles, hipStream_t st);
 void edge_linear_set_grid_cap(int cap);
 int layer_norm_fwd_run(const void* x, int x_dtype, const float* gamma, const float* beta, void* y, int y_dtype,
                        float* mean, float* rstd, int64_t rows, int C, float eps, hipStream_t st);
@@ -285,7 +287,14 @@ int tgt_gaussian_basis_bwd(const float* x, const float* mul, const float* bias, 
 
 int tgt_edge_linear_supported(const tgt_edge_linear_args* a) { return edge_linear_supported(a); }
 int tgt_edge_linear_parts(int64_t M, int32_t N) { return edge_linear_parts(M, N); }
-int tgt_edge_linear(const tgt_edge_linear_args* a, void* stream) { return edge_linear_run(a, reinterpret_cast<hipStream_t>(stream)); }
+int tgt_edge_linear(const tgt_edge_linear_args* a, void* stream) { return edge_linear_run(a, reinterpret_cast<hipStream_t>(stream), nullptr); }
+int tgt_edge_linear_live_supported(const tgt_edge_linear_args* a) { return edge_linear_live_supported(a); }
+int tgt_edge_linear_live(const tgt_edge_linear_args* a, const int32_t* tiles, void* stream) {
+    return edge_linear_run(a, reinterpret_cast<hipStream_t>(stream), tiles);
+}
+int tgt_edge_live_tiles(const int32_t* node_counts, int32_t B, int32_t N, int32_t* tiles, void* stream) {
+    return edge_live_tiles_run(node_counts, B, N, tiles, reinterpret_cast<hipStream_t>(stream));
+}
 void tgt_edge_linear_set_grid_cap(int32_t cap) { edge_linear_set_grid_cap(cap); }
 
 }  // extern "C"

@@ -232,5 +232,46 @@ __device__ __forceinline__ void rp_st_f32(__amdgpu_buffer_rsrc_t r, uint32_t off
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)off, 0, 0);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Live tile lists (tgt_edge_linear_live; built by tgt_edge_live_tiles, edge_live.hip): list[0] = number of live 32-row tiles, then
+// the live tile indices ascending, then the dead ones ascending.  A tile is dead when every row (b, i, j) of it is padding of a
+// ragged batch (i or j at or past the node count of graph b) -- the persistent row kernels then neither load nor compute it: the
+// LIVE tiles are dealt round-robin over the workgroups (workgroup w walks list[1 + w + s * gridDim]), the dead ones the same way
+// from the tail of the list, and those only get zeros in every output the epilogue defines.
+// The list is a COMPILE-TIME choice, as the node counts are in the triplet kernels (triplet_common.hpp): a trailing parameter pack
+// `TL... tl` of the kernel, empty without a list -- that instantiation has the argument list and the instruction stream it always had.
+// Entries are clamped where they are read: whatever the list holds, no access leaves the tensors.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ const int32_t* edge_live_ptr() { return nullptr; }
+__device__ __forceinline__ const int32_t* edge_live_ptr(const int32_t* p) { return p; }
+__device__ __forceinline__ int edge_live_count(const int32_t* list, int64_t row_tiles) {
+    const int n = list[0];
+    return n < 0 ? 0 : (n > row_tiles ? (int)row_tiles : n);
+}
+// entry `idx` (0-based, behind the count) of the list as a tile; at or past `end`: row_tiles = a tile past the last row, whose
+// buffer resources are all empty (loads return 0, stores are dropped)
+__device__ __forceinline__ int64_t edge_live_tile(const int32_t* list, int64_t idx, int64_t end, int64_t row_tiles) {
+    if (idx >= end) return row_tiles;
+    const int t = list[1 + idx];
+    return t < 0 ? row_tiles : (t > row_tiles ? row_tiles : (int64_t)t);
+}
+// zeros into rows [32 tile, 32 tile + 32) of an (M, ld) tensor whose rows hold `row_bytes` (a multiple of 512), by the 1024
+// threads of a workgroup: thread = (row tid / 32, 16-byte chunk tid % 32), 32 whole rows of 512 bytes per store instruction
+__device__ __forceinline__ void edge_zero_rows(void* base, int64_t ld_bytes, int row_bytes, int64_t tile, int64_t M, int tid) {
+    const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, ld_bytes, row_bytes, tile * 32, M);
+    const uint32_t off = (uint32_t)(tid >> 5) * (uint32_t)ld_bytes + (uint32_t)(tid & 31) * 16u;
+    for (int c = 0; c < row_bytes; c += 512) rp_st16(rs, off + (uint32_t)c, make_uint4(0, 0, 0, 0));
+}
+// ... and into the 32 floats of a per-row statistic (mean, rstd)
+__device__ __forceinline__ void edge_zero_stat(float* base, int64_t tile, int64_t M, int tid) {
+    const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, 4, 4, tile * 32, M);
+    rp_st_f32(rs, tid < 32 ? (uint32_t)tid * 4u : 0xffffffffu, 0.f);
+}
+// the dead tiles of this workgroup: zero(tile) for each
+template <typename Z>
+__device__ __forceinline__ void edge_dead_tiles(const int32_t* list, int n_live, int64_t row_tiles, Z&& zero) {
+    for (int64_t d = blockIdx.x; d < row_tiles - n_live; d += gridDim.x) zero(edge_live_tile(list, n_live + d, row_tiles, row_tiles));
+}
+
 
 }  // namespace tgt

@@ -416,8 +416,9 @@ __global__ void __launch_bounds__(512, 2) edge_slice_kernel(const tgt_edge_linea
 // per-thread accumulators across ALL tiles of the persistent workgroup, folded once at the end.
 // Weight slice (32 columns x K per wave) resident in registers, A tiles by LDS-DMA into two buffers, as above.
 // ---------------------------------------------------------------------------------------------------------------
-template <typename T, int KS, int EPI>
-__global__ void __launch_bounds__(1024, 4) edge_rows_kernel(const tgt_edge_linear_args a, const uint64_t* seed_ctr) {
+template <typename T, int KS, int EPI, typename... TL>
+__global__ void __launch_bounds__(1024, 4) edge_rows_kernel(const tgt_edge_linear_args a, const uint64_t* seed_ctr, TL... tl) {
+    constexpr bool LV = sizeof...(TL) > 0;                // launched with a live tile list as a trailing argument (edge_common.hpp)
     using F = frag_t<T>;
     constexpr int K = KS * 16, N = 256, kBM = 32, kABytes = kBM * K * 2, kSBytes = kBM * N * 2, kPass = 2;
     constexpr bool kOperand = EPI == EPI_RESID || EPI == EPI_GELU_BWD || EPI == EPI_LN_BWD;
@@ -430,8 +431,29 @@ __global__ void __launch_bounds__(1024, 4) edge_rows_kernel(const tgt_edge_linea
     const int64_t row_tiles = (a.M + kBM - 1) / kBM;
     float* gb = reinterpret_cast<float*>(smem + kOffGB);
     if (blockIdx.x >= row_tiles) return;
-    const int n_tiles = (int)((row_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x);       // tiles of this workgroup
-    auto tile_of = [&](int s) { return (int64_t)blockIdx.x + (int64_t)s * gridDim.x; };    // (s >= n_tiles: past the last row -> empty buffers)
+    const int32_t* live = edge_live_ptr(tl...);
+    int n_live = 0;
+    if constexpr (LV) {
+        n_live = edge_live_count(live, row_tiles);
+        edge_dead_tiles(live, n_live, row_tiles, [&](int64_t t) {      // all 16 waves, before the roles part: zeros, no operand read
+            edge_zero_rows(a.out, a.ldo * 2, N * 2, t, a.M, tid);
+            if constexpr (EPI == EPI_GELU || EPI == EPI_LN_BWD) edge_zero_rows(a.out2, a.ldo2 * 2, N * 2, t, a.M, tid);
+            if constexpr (EPI == EPI_RESID) {
+                if (a.gamma) {
+                    edge_zero_rows(a.y, a.ldy * 2, N * 2, t, a.M, tid);
+                    edge_zero_stat(a.mean, t, a.M, tid);
+                    edge_zero_stat(a.rstd, t, a.M, tid);
+                }
+            }
+        });
+    }
+    // tiles of this workgroup; with a list: its share of the LIVE tiles (none: both roles run their barriers, the column sums are zeros)
+    const int n_tiles = LV ? (int)(((int64_t)n_live - blockIdx.x + gridDim.x - 1) / gridDim.x)
+                           : (int)((row_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
+    auto tile_of = [&](int s) {                            // (s >= n_tiles: past the last row -> empty buffers)
+        if constexpr (LV) return edge_live_tile(live, (int64_t)blockIdx.x + (int64_t)s * gridDim.x, n_live, row_tiles);
+        else return (int64_t)blockIdx.x + (int64_t)s * gridDim.x;
+    };
     // (static wave priority for either role -- what gave the projection-fused triplet forward 8 % -- measured neutral here:
     // profiles/r05o_ab_prio.txt)
 
@@ -742,8 +764,9 @@ __global__ void __launch_bounds__(1024, 4) edge_rows_kernel(const tgt_edge_linea
 // stores drain under the next stage -- and the two phases together (~5500 cycles per 32-row tile) stay under the tile's HBM time
 // (80 KB per tile and CU: ~9800 cycles at 5 TB/s).
 // ---------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(1024, 4) edge_rows512_kernel(const tgt_edge_linear_args a) {
+template <typename T, typename... TL>
+__global__ void __launch_bounds__(1024, 4) edge_rows512_kernel(const tgt_edge_linear_args a, TL... tl) {
+    constexpr bool LV = sizeof...(TL) > 0;                // launched with a live tile list (edge_common.hpp)
     using F = frag_t<T>;
     constexpr int K = 512, KS = 16, N = 256, kBM = 32;
     constexpr int kABytes = kBM * K * 2, kPBytes = kBM * N * 4;
@@ -757,8 +780,25 @@ __global__ void __launch_bounds__(1024, 4) edge_rows512_kernel(const tgt_edge_li
     const int64_t row_tiles = (a.M + kBM - 1) / kBM;
     float* gb = reinterpret_cast<float*>(smem + kOffGB);
     if (blockIdx.x >= row_tiles) return;
-    const int n_tiles = (int)((row_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
-    auto tile_of = [&](int s) { return (int64_t)blockIdx.x + (int64_t)s * gridDim.x; };
+    const int32_t* live = edge_live_ptr(tl...);
+    int n_live = 0;
+    if constexpr (LV) {
+        n_live = edge_live_count(live, row_tiles);
+        edge_dead_tiles(live, n_live, row_tiles, [&](int64_t t) {
+            edge_zero_rows(a.out, a.ldo * 2, N * 2, t, a.M, tid);
+            if (a.gamma) {
+                edge_zero_rows(a.y, a.ldy * 2, N * 2, t, a.M, tid);
+                edge_zero_stat(a.mean, t, a.M, tid);
+                edge_zero_stat(a.rstd, t, a.M, tid);
+            }
+        });
+    }
+    const int n_tiles = LV ? (int)(((int64_t)n_live - blockIdx.x + gridDim.x - 1) / gridDim.x)
+                           : (int)((row_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
+    auto tile_of = [&](int s) {
+        if constexpr (LV) return edge_live_tile(live, (int64_t)blockIdx.x + (int64_t)s * gridDim.x, n_live, row_tiles);
+        else return (int64_t)blockIdx.x + (int64_t)s * gridDim.x;
+    };
     const bool pres = (a.flags & TGT_EDGE_BIAS_SCALED) != 0;                  // a arrived pre-scaled: res + a W^T + scale * bias
     if (tid < N) {
         gb[tid] = a.gamma ? a.gamma[tid] : 1.f;
@@ -907,8 +947,9 @@ __global__ void __launch_bounds__(1024, 4) edge_rows512_kernel(const tgt_edge_li
 // (32 rows x 1 KB, 16-byte slots XOR-swizzled by the row) and leave as whole 1 KB rows, 16 bytes per thread and store.
 // Straight-line stages on tile-based buffer resources, exact wait counts (see edge_rows_kernel).
 // ---------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(1024, 4) edge_wide512_kernel(const tgt_edge_linear_args a) {
+template <typename T, typename... TL>
+__global__ void __launch_bounds__(1024, 4) edge_wide512_kernel(const tgt_edge_linear_args a, TL... tl) {
+    constexpr bool LV = sizeof...(TL) > 0;                // launched with a live tile list (edge_common.hpp)
     using F = frag_t<T>;
     constexpr int K = 256, KS = 16, N = 512, kBM = 32;
     constexpr int kABytes = kBM * K * 2, kOBytes = kBM * N * 2;
@@ -921,8 +962,18 @@ __global__ void __launch_bounds__(1024, 4) edge_wide512_kernel(const tgt_edge_li
     const int64_t row_tiles = (a.M + kBM - 1) / kBM;
     float* bs = reinterpret_cast<float*>(smem + kOffB);
     if (blockIdx.x >= row_tiles) return;
-    const int n_tiles = (int)((row_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
-    auto tile_of = [&](int s) { return (int64_t)blockIdx.x + (int64_t)s * gridDim.x; };
+    const int32_t* live = edge_live_ptr(tl...);
+    int n_live = 0;
+    if constexpr (LV) {
+        n_live = edge_live_count(live, row_tiles);
+        edge_dead_tiles(live, n_live, row_tiles, [&](int64_t t) { edge_zero_rows(a.out, a.ldo * 2, N * 2, t, a.M, tid); });
+    }
+    const int n_tiles = LV ? (int)(((int64_t)n_live - blockIdx.x + gridDim.x - 1) / gridDim.x)
+                           : (int)((row_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
+    auto tile_of = [&](int s) {
+        if constexpr (LV) return edge_live_tile(live, (int64_t)blockIdx.x + (int64_t)s * gridDim.x, n_live, row_tiles);
+        else return (int64_t)blockIdx.x + (int64_t)s * gridDim.x;
+    };
     if (tid < N) bs[tid] = a.bias ? to_f32(reinterpret_cast<const T*>(a.bias)[tid]) : 0.f;
     const T* W = reinterpret_cast<const T*>(a.w);
     F wr[KS];
@@ -983,7 +1034,7 @@ __global__ void __launch_bounds__(1024, 4) edge_wide512_kernel(const tgt_edge_li
 bool edge_wgrad_eligible(const tgt_edge_linear_args& a);                       // edge_wgrad.hip
 int edge_wgrad_run(const tgt_edge_linear_args& a, int grid, hipStream_t st);
 bool edge_glu_eligible(const tgt_edge_linear_args& a);                         // edge_glu.hip (TGT_EPI_GLU: 256 -> 512 + gated activation)
-int edge_glu_run(const tgt_edge_linear_args& a, int grid, hipStream_t st);
+int edge_glu_run(const tgt_edge_linear_args& a, int grid, hipStream_t st, const int32_t* tiles);
 
 // test hook (tgt_edge_linear_set_grid_cap): at most this many persistent workgroups / row groups per launch, so that a small
 // problem walks several tiles per workgroup -- the stage hand-over the BASELINE-size launches (32 tiles each) depend on
@@ -1005,37 +1056,38 @@ static int er_grid(const tgt_edge_linear_args& a) {
 }
 
 
-template <typename T, int KS, int EPI>
-static int er_launch(const tgt_edge_linear_args& a, hipStream_t st) {
+// (TL: empty, or the live tile list of tgt_edge_linear_live -- the kernels' trailing parameter pack)
+template <typename T, int KS, int EPI, typename... TL>
+static int er_launch(const tgt_edge_linear_args& a, hipStream_t st, TL... tl) {
     constexpr int K = KS * 16;
     constexpr int lds0 = 2 * 32 * K * 2 + 2 * 32 * 256 * 2 + 2 * 256 * 4;
     constexpr int lds = lds0 < 49152 ? 49152 : lds0;                        // the final column-sum fold of LN_BWD needs 48 KB
-    return launch_lds<edge_rows_kernel<T, KS, EPI>>("edge_rows_kernel", dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a, seed_counter());
+    return launch_lds<edge_rows_kernel<T, KS, EPI, TL...>>("edge_rows_kernel", dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a, seed_counter(), tl...);
 }
 
-template <typename T>
-static int er512_launch(const tgt_edge_linear_args& a, hipStream_t st) {
+template <typename T, typename... TL>
+static int er512_launch(const tgt_edge_linear_args& a, hipStream_t st, TL... tl) {
     constexpr int lds = 2 * 32 * 512 * 2 + 2 * 32 * 256 * 4 + 3 * 256 * 4;
-    return launch_lds<edge_rows512_kernel<T>>("edge_rows512_kernel", dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a);
+    return launch_lds<edge_rows512_kernel<T, TL...>>("edge_rows512_kernel", dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a, tl...);
 }
 
-template <typename T>
-static int ew512_launch(const tgt_edge_linear_args& a, hipStream_t st) {
+template <typename T, typename... TL>
+static int ew512_launch(const tgt_edge_linear_args& a, hipStream_t st, TL... tl) {
     constexpr int lds = 2 * 32 * 256 * 2 + 32 * 512 * 2 + 512 * 4;
-    return launch_lds<edge_wide512_kernel<T>>("edge_wide512_kernel", dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a);
+    return launch_lds<edge_wide512_kernel<T, TL...>>("edge_wide512_kernel", dim3((unsigned)er_grid(a)), dim3(1024), lds, st, a, tl...);
 }
 // K = 256 -> N = 512 with the plain epilogue and nothing else attached
 static bool ew512_eligible(const tgt_edge_linear_args& a) {
     return a.K == 256 && a.N == 512 && a.epilogue == EPI_BIAS && !a.gamma && !a.row_scale && !a.out_scale;
 }
 
-template <typename T, int KS>
-static int er_dispatch(const tgt_edge_linear_args& a, hipStream_t st) {
+template <typename T, int KS, typename... TL>
+static int er_dispatch(const tgt_edge_linear_args& a, hipStream_t st, TL... tl) {
     switch (a.epilogue) {
-        case EPI_GELU: return er_launch<T, KS, EPI_GELU>(a, st);
-        case EPI_RESID: return er_launch<T, KS, EPI_RESID>(a, st);
-        case EPI_GELU_BWD: return er_launch<T, KS, EPI_GELU_BWD>(a, st);
-        case EPI_LN_BWD: return er_launch<T, KS, EPI_LN_BWD>(a, st);
+        case EPI_GELU: return er_launch<T, KS, EPI_GELU>(a, st, tl...);
+        case EPI_RESID: return er_launch<T, KS, EPI_RESID>(a, st, tl...);
+        case EPI_GELU_BWD: return er_launch<T, KS, EPI_GELU_BWD>(a, st, tl...);
+        case EPI_LN_BWD: return er_launch<T, KS, EPI_LN_BWD>(a, st, tl...);
         default: return set_error(TGT_ERR_INVALID, "edge linear (row-phase kernel): bad epilogue %d", a.epilogue);
     }
 }
@@ -1048,12 +1100,12 @@ static bool er_eligible(const tgt_edge_linear_args& a) {
     return true;
 }
 
-template <typename T>
-static int er_run(const tgt_edge_linear_args& a, hipStream_t st) {
+template <typename T, typename... TL>
+static int er_run(const tgt_edge_linear_args& a, hipStream_t st, TL... tl) {
     switch (a.K) {
-        case 64: return er_dispatch<T, 4>(a, st);
-        case 128: return er_dispatch<T, 8>(a, st);
-        default: return er_dispatch<T, 16>(a, st);
+        case 64: return er_dispatch<T, 4>(a, st, tl...);
+        case 128: return er_dispatch<T, 8>(a, st, tl...);
+        default: return er_dispatch<T, 16>(a, st, tl...);
     }
 }
 
@@ -1143,13 +1195,28 @@ int edge_linear_supported(const tgt_edge_linear_args* a) {
     return 1;
 }
 
-int edge_linear_run(const tgt_edge_linear_args* a, hipStream_t st) {
+// the launches that walk a live tile list (tgt_edge_linear_live): the three persistent 32-row-tile kernels of this file and the GLU
+// form of the 256 -> 512 one (edge_glu.hip).  Not the slice kernel (64 / 128-row tiles), not the fused weight gradient (its
+// dW planes sum A rows the list says are never read)
+int edge_linear_live_supported(const tgt_edge_linear_args* a) {
+    if (!edge_linear_supported(a) || a->dw_partial) return 0;
+    if (a->epilogue == EPI_GLU || a->K == 512) return 1;
+    return (ew512_eligible(*a) || er_eligible(*a)) ? 1 : 0;
+}
+
+// tiles: NULL, or the live tile list (1 + ceil(M / 32) entries) of tgt_edge_live_tiles
+int edge_linear_run(const tgt_edge_linear_args* a, hipStream_t st, const int32_t* tiles) {
     if (!a || !a->a || !a->w || !a->out) return set_error(TGT_ERR_INVALID, "edge linear: null argument");
     if (a->M < 0 || a->K <= 0 || a->N <= 0) return set_error(TGT_ERR_INVALID, "edge linear: bad sizes");
     if (!edge_linear_supported(a))
         return set_error(TGT_ERR_UNSUPPORTED, "edge linear: unsupported shape/dtype (K=%d N=%d dtype=%d epilogue=%d): needs a 16-bit "
                          "dtype, N %% 8 == 0, K in {64,128,256} (K = 512: residual epilogue, N = 256); row-wise epilogues N <= 256; TGT_EPI_GLU K = 256, N = 512",
                          a->K, a->N, a->dtype, a->epilogue);
+    if (tiles && !edge_linear_live_supported(a))
+        return set_error(TGT_ERR_UNSUPPORTED, "edge linear: a live tile list goes with the 32-row-tile kernels only (N = 256 whole-row epilogues, "
+                         "K = 512 -> 256, 256 -> 512 plain or TGT_EPI_GLU) and not with dw_partial (K=%d N=%d epilogue=%d dw_partial=%s)",
+                         a->K, a->N, a->epilogue, a->dw_partial ? "given" : "NULL");
+    if (tiles && (a->M + 31) / 32 > 0x7ffffffeLL) return set_error(TGT_ERR_INVALID, "edge linear: too many rows for a live tile list");
     if (a->M == 0) return TGT_OK;
     const uintptr_t al = (uintptr_t)a->a | (uintptr_t)a->w | (uintptr_t)a->out | (uintptr_t)a->out2 | (uintptr_t)a->res |
                          (uintptr_t)a->y | (uintptr_t)a->ds_in;
@@ -1174,7 +1241,12 @@ int edge_linear_run(const tgt_edge_linear_args* a, hipStream_t st) {
         if (((uintptr_t)a->dw_partial) % 16) return set_error(TGT_ERR_INVALID, "edge linear: dw_partial must be 16-byte aligned");
         return edge_wgrad_run(*a, er_grid(*a), st);
     }
-    if (a->epilogue == EPI_GLU) return edge_glu_run(*a, er_grid(*a), st);
+    if (a->epilogue == EPI_GLU) return edge_glu_run(*a, er_grid(*a), st, tiles);
+    if (tiles) {
+        if (a->K == 512) return a->dtype == TGT_BF16 ? er512_launch<bf16_t>(*a, st, tiles) : er512_launch<f16_t>(*a, st, tiles);
+        if (ew512_eligible(*a)) return a->dtype == TGT_BF16 ? ew512_launch<bf16_t>(*a, st, tiles) : ew512_launch<f16_t>(*a, st, tiles);
+        return a->dtype == TGT_BF16 ? er_run<bf16_t>(*a, st, tiles) : er_run<f16_t>(*a, st, tiles);      // (er_eligible: checked above)
+    }
     if (a->K == 512) return a->dtype == TGT_BF16 ? er512_launch<bf16_t>(*a, st) : er512_launch<f16_t>(*a, st);
     if (ew512_eligible(*a)) return a->dtype == TGT_BF16 ? ew512_launch<bf16_t>(*a, st) : ew512_launch<f16_t>(*a, st);
     if (er_eligible(*a)) return a->dtype == TGT_BF16 ? er_run<bf16_t>(*a, st) : er_run<f16_t>(*a, st);

@@ -13,8 +13,9 @@
 
 namespace tgt {
 
-template <typename T, int KIND>
-__global__ void __launch_bounds__(1024, 4) edge_glu512_kernel(const tgt_edge_linear_args a, const uint64_t* __restrict__ seed_ctr) {
+template <typename T, int KIND, typename... TL>
+__global__ void __launch_bounds__(1024, 4) edge_glu512_kernel(const tgt_edge_linear_args a, const uint64_t* __restrict__ seed_ctr, TL... tl) {
+    constexpr bool LV = sizeof...(TL) > 0;                // launched with a live tile list (edge_common.hpp), as edge_wide512_kernel
     using F = frag_t<T>;
     constexpr int K = 256, KS = 16, N = 512, NO = 256, kBM = 32;
     constexpr int kABytes = kBM * K * 2, kOBytes = kBM * N * 2;
@@ -27,8 +28,21 @@ __global__ void __launch_bounds__(1024, 4) edge_glu512_kernel(const tgt_edge_lin
     const int64_t row_tiles = (a.M + kBM - 1) / kBM;
     float* bs = reinterpret_cast<float*>(smem + kOffB);
     if (blockIdx.x >= row_tiles) return;
-    const int n_tiles = (int)((row_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
-    auto tile_of = [&](int s) { return (int64_t)blockIdx.x + (int64_t)s * gridDim.x; };
+    const int32_t* live = edge_live_ptr(tl...);
+    int n_live = 0;
+    if constexpr (LV) {
+        n_live = edge_live_count(live, row_tiles);
+        edge_dead_tiles(live, n_live, row_tiles, [&](int64_t t) {
+            edge_zero_rows(a.out2, a.ldo2 * 2, N * 2, t, a.M, tid);
+            edge_zero_rows(a.out, a.ldo * 2, NO * 2, t, a.M, tid);
+        });
+    }
+    const int n_tiles = LV ? (int)(((int64_t)n_live - blockIdx.x + gridDim.x - 1) / gridDim.x)
+                           : (int)((row_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x);
+    auto tile_of = [&](int s) {
+        if constexpr (LV) return edge_live_tile(live, (int64_t)blockIdx.x + (int64_t)s * gridDim.x, n_live, row_tiles);
+        else return (int64_t)blockIdx.x + (int64_t)s * gridDim.x;
+    };
     if (tid < N) bs[tid] = a.bias ? to_f32(reinterpret_cast<const T*>(a.bias)[tid]) : 0.f;
     const T* W = reinterpret_cast<const T*>(a.w);
     F wr[KS];
@@ -112,18 +126,18 @@ __global__ void __launch_bounds__(1024, 4) edge_glu512_kernel(const tgt_edge_lin
     }
 }
 
-template <typename T, int KIND>
-static int eglu_launch(const tgt_edge_linear_args& a, int grid, hipStream_t st) {
+template <typename T, int KIND, typename... TL>
+static int eglu_launch(const tgt_edge_linear_args& a, int grid, hipStream_t st, TL... tl) {
     constexpr int lds = 2 * 32 * 256 * 2 + 32 * 512 * 2 + 512 * 4;
-    return launch_lds<edge_glu512_kernel<T, KIND>>("edge_glu512_kernel", dim3((unsigned)grid), dim3(1024), lds, st, a, seed_counter());
+    return launch_lds<edge_glu512_kernel<T, KIND, TL...>>("edge_glu512_kernel", dim3((unsigned)grid), dim3(1024), lds, st, a, seed_counter(), tl...);
 }
 
-template <typename T>
-static int eglu_kind(const tgt_edge_linear_args& a, int grid, hipStream_t st) {
+template <typename T, typename... TL>
+static int eglu_kind(const tgt_edge_linear_args& a, int grid, hipStream_t st, TL... tl) {
     switch ((a.flags & TGT_EDGE_GLU_KIND_MASK) >> TGT_EDGE_GLU_KIND_SHIFT) {
-        case TGT_GLU_GEGLU: return eglu_launch<T, TGT_GLU_GEGLU>(a, grid, st);
-        case TGT_GLU_GLU: return eglu_launch<T, TGT_GLU_GLU>(a, grid, st);
-        case TGT_GLU_SWIGLU: return eglu_launch<T, TGT_GLU_SWIGLU>(a, grid, st);
+        case TGT_GLU_GEGLU: return eglu_launch<T, TGT_GLU_GEGLU>(a, grid, st, tl...);
+        case TGT_GLU_GLU: return eglu_launch<T, TGT_GLU_GLU>(a, grid, st, tl...);
+        case TGT_GLU_SWIGLU: return eglu_launch<T, TGT_GLU_SWIGLU>(a, grid, st, tl...);
         default: return set_error(TGT_ERR_INVALID, "edge linear (TGT_EPI_GLU): bad kind in flags 0x%x", a.flags);
     }
 }
@@ -135,7 +149,9 @@ bool edge_glu_eligible(const tgt_edge_linear_args& a) {
            ((a.flags & TGT_EDGE_GLU_KIND_MASK) >> TGT_EDGE_GLU_KIND_SHIFT) <= TGT_GLU_SWIGLU;
 }
 
-int edge_glu_run(const tgt_edge_linear_args& a, int grid, hipStream_t st) {
+// tiles: NULL, or the live tile list of tgt_edge_linear_live
+int edge_glu_run(const tgt_edge_linear_args& a, int grid, hipStream_t st, const int32_t* tiles) {
+    if (tiles) return a.dtype == TGT_BF16 ? eglu_kind<bf16_t>(a, grid, st, tiles) : eglu_kind<f16_t>(a, grid, st, tiles);
     return a.dtype == TGT_BF16 ? eglu_kind<bf16_t>(a, grid, st) : eglu_kind<f16_t>(a, grid, st);
 }
 

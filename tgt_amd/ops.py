@@ -144,6 +144,45 @@ def mask_node_counts(mask3):
     return counts
 
 
+class EdgeLiveTiles:
+    """The live tile list of a ragged batch (edge_live_tiles): `tiles` for tgt_edge_linear_live, `rows` = B*N*N, the only row
+    count it describes."""
+    __slots__ = ('tiles', 'rows')
+
+    def __init__(self, tiles, rows):
+        self.tiles, self.rows = tiles, rows
+
+
+def edge_live_tiles(node_counts, N):
+    """(B,) int32 node counts on the device -> EdgeLiveTiles: which 32-row tiles of the (B*N*N, C) edge rows hold a real row
+    (tgt_hip.h, tgt_edge_live_tiles; the counts are clamped to [0, N] in the kernel).  One launch, no host synchronisation."""
+    B = node_counts.numel()
+    _check_node_counts(node_counts, B)
+    if not node_counts.is_cuda:
+        _dev(node_counts)
+    rows = B * int(N) * int(N)
+    tiles = torch.empty(1 + (rows + 31) // 32, dtype=torch.int32, device=node_counts.device)
+    _lib.check(_lib.lib().tgt_edge_live_tiles(_ptr(node_counts), B, int(N), _ptr(tiles), _stream()), 'tgt_edge_live_tiles')
+    return EdgeLiveTiles(tiles, rows)
+
+
+# The list of the forward in progress (TGT_EDGE_RAGGED: TGT_Encoder.forward sets it around its layer loop).  Every autograd
+# Function that launches a row kernel reads it in its forward, keeps it in ctx and hands THAT to its backward launches -- the
+# backward skips what its forward skipped, whatever the context holds by then.
+_edge_live = None
+
+
+@contextlib.contextmanager
+def edge_live(live):
+    """within: edge_linear_raw launches of the autograd Functions on live.rows rows skip the dead tiles (live None: nothing changes)"""
+    global _edge_live
+    prev, _edge_live = _edge_live, live
+    try:
+        yield live
+    finally:
+        _edge_live = prev
+
+
 def _pair(cls, a, b):
     return (cls * 2)(a, b)
 
@@ -1613,7 +1652,7 @@ def _materialize_dgrad(dy):
     return dy if lazy is None else (lazy[0] @ lazy[1]).view(dy.shape)
 
 
-def _ln_backward(dy, s, g, mean, rstd, ds, scale, rps, want_dz):
+def _ln_backward(dy, s, g, mean, rstd, ds, scale, rps, want_dz, live=None):
     """(d_res, d_z, dgamma, dbeta, colsum of d_z) of the residual entry  s = res + scale z, y = LayerNorm(s; g):
     d_res = ds + LN_bwd(dy), d_z = scale * d_res (a separate tensor only when want_dz; else d_res stands for it and only the
     column sums carry the factor).  dy a lazy token of a K <= 256 data gradient: one fused launch; else tgt_add_layer_norm_bwd."""
@@ -1630,7 +1669,7 @@ def _ln_backward(dy, s, g, mean, rstd, ds, scale, rps, want_dz):
         edge_linear_raw(dz2, weight_t(w), None, _lib.EPI_LN_BWD, ln=(g, None, 1e-5), stats=(mean, rstd), res=s.view(rows, N),
                         ds_in=None if ds is None else ds.view(rows, N), out=d_res.view(rows, N),
                         out2=None if d_z is None else d_z.view(rows, N), row_scale=scale, rows_per_sample=rps if scale is not None else 0,
-                        colsum_partial=partial)
+                        colsum_partial=partial, live=live)
         with _on_stream(_terminal_fork(rows, partial)):
             tot = sum_planes(partial, torch.empty(3 * N, dtype=torch.float32, device=s.device))
         _lazy_dgrads[1] += 1
@@ -1918,7 +1957,8 @@ def _linear_forward(x, weight, bias, cd):
     return x2, w, y
 
 
-def _linear_backward(x2, w, dy2, xs, xdt, wdt, bdt, need_dx, need_dw, need_db, lazy_dx=False, dw_post=None, fork=True, dw_ptr=None):
+def _linear_backward(x2, w, dy2, xs, xdt, wdt, bdt, need_dx, need_dw, need_db, lazy_dx=False, dw_post=None, fork=True, dw_ptr=None,
+                     live=None):
     """(dx, dW, db) of y = x W^T + b.  dW = dY^T X contracts over M = B*N*N = 262144 rows into a
     tiny (out,in) result; as one GEMM the library runs it on a handful of workgroups
     (0.4-0.8 ms), as 64-128 independent chunk products + an fp32 sum it is HBM-bound (57 us for
@@ -1937,7 +1977,7 @@ def _linear_backward(x2, w, dy2, xs, xdt, wdt, bdt, need_dx, need_dw, need_db, l
                 ((w.shape[0] == 256 and w.shape[1] == 512) or w.shape[1] <= 128):
             # data gradients the weight-resident kernels win: lin_O's (256 -> 512 channels: 3 E at ~5 TB/s, library 3.5) on
             # edge_wide512_kernel, narrow ones (lin_O_e: 256 -> 64) on the slice kernel
-            dx = edge_linear_raw(dy2.contiguous(), weight_t(w)).view(xs).to(xdt)
+            dx = edge_linear_raw(dy2.contiguous(), weight_t(w), live=live).view(xs).to(xdt)
         else:
             dx = _gemm.matmul_nn(dy2, w).view(xs).to(xdt)
     if need_dw:
@@ -1976,6 +2016,7 @@ class _Linear(torch.autograd.Function):
         ctx.meta = (x.shape, x.dtype, weight.dtype, None if bias is None else bias.dtype)
         ctx.lazy = lazy
         ctx.wptr = weight.data_ptr()
+        ctx.live = _edge_live
         return y
 
     @staticmethod
@@ -1986,7 +2027,7 @@ class _Linear(torch.autograd.Function):
         cs = _take_colsum(dy, dy.shape[-1]) if need_db else None
         dx, dw, db = _linear_backward(x2, w, dy.reshape(-1, dy.shape[-1]), xs, xdt, wdt, bdt,
                                       ctx.needs_input_grad[0], ctx.needs_input_grad[1], need_db and cs is None, ctx.lazy,
-                                      dw_ptr=ctx.wptr)
+                                      dw_ptr=ctx.wptr, live=ctx.live)
         if cs is not None:
             db = _param_grad(cs, bdt)
         return dx, dw, db, None, None
@@ -2019,6 +2060,7 @@ class _LinearPermutedCols(torch.autograd.Function):
         x2, w, y = _linear_forward(x, w, bias, cd)
         ctx.save_for_backward(x2, w, inv)
         ctx.meta = (x.shape, x.dtype, weight.dtype, None if bias is None else bias.dtype)
+        ctx.live = _edge_live
         return y
 
     @staticmethod
@@ -2029,7 +2071,7 @@ class _LinearPermutedCols(torch.autograd.Function):
         cs = _take_colsum(dy, dy.shape[-1]) if need_db else None
         dx, dw, db = _linear_backward(x2, w, dy.reshape(-1, dy.shape[-1]), xs, xdt, torch.float32, bdt,
                                       ctx.needs_input_grad[0], ctx.needs_input_grad[1], need_db and cs is None,
-                                      dw_post=lambda t: _permute_cols(t.contiguous(), inv, wdt, after_sums=True))
+                                      dw_post=lambda t: _permute_cols(t.contiguous(), inv, wdt, after_sums=True), live=ctx.live)
         if cs is not None:
             db = _param_grad(cs, bdt)
         return dx, dw, db, None, None, None
@@ -2052,6 +2094,7 @@ class _FusedLinear(torch.autograd.Function):
         x2, w, y = _linear_forward(x, weight, bias, cd)
         ctx.save_for_backward(x2, w, *params)
         ctx.table, ctx.meta = table, (x.shape, x.dtype)
+        ctx.live = _edge_live
         return y
 
     @staticmethod
@@ -2061,7 +2104,7 @@ class _FusedLinear(torch.autograd.Function):
         xs, xdt = ctx.meta
         need_p = any(ctx.needs_input_grad[3:])
         dx, dw, db = _linear_backward(x2, w, dy.reshape(-1, dy.shape[-1]), xs, xdt, torch.float32, torch.float32,
-                                      ctx.needs_input_grad[0], need_p, need_p, fork=False)
+                                      ctx.needs_input_grad[0], need_p, need_p, fork=False, live=ctx.live)
         grads = _unfuse_grads(ctx.table, params, dw, db) if need_p else (None,) * len(params)
         return (dx, None, None, *grads)
 
@@ -2084,10 +2127,13 @@ def linear(x, weight, bias=None):
 # ---------------------------------------------------------------------------
 def edge_linear_raw(a, w, bias=None, epilogue=_lib.EPI_BIAS, *, ln=None, y=None, out=None, out2=None, res=None, ds_in=None,
                     row_scale=None, out_scale=None, rows_per_sample=0, dropout=(0.0, 0), stats=None, colsum_partial=None,
-                    flags=0, dw_partial=None):
+                    flags=0, dw_partial=None, live=None):
     """One launch of tgt_edge_linear on 2-D operands (rows may be strided views with a contiguous last axis).
     a (M,K), w (N,K), bias (N) in one 16-bit dtype; ln = (gamma, beta, eps) float32 for the LayerNorm prologue /
     the LN_BWD epilogue; stats = (mean, rstd) float32 (M) (written by the prologue, read by LN_BWD).
+    live: an EdgeLiveTiles (edge_live_tiles) -- a PERMISSION to skip the dead tiles, never an obligation: used when it describes
+    exactly these M rows and the launch is one tgt_edge_linear_live takes (the dead rows of every output are then zeros);
+    otherwise this is the plain call.
     Returns out (allocated when not given).  No fallback: an unsupported shape raises."""
     _dev(a, w, bias, out, out2, res, ds_in, y)
     M, K = a.shape
@@ -2144,8 +2190,17 @@ def edge_linear_raw(a, w, bias=None, epilogue=_lib.EPI_BIAS, *, ln=None, y=None,
             raise RuntimeError(f'edge_linear: dw_partial must be contiguous float32 (parts, {N}, {K}) with as many planes as colsum_partial has rows')
         g.dw_partial = dw_partial.data_ptr()
         g.colsum_rows = dw_partial.shape[0]
-    _call('tgt_edge_linear', _lib.lib().tgt_edge_linear, g)
+    if live is not None and M == live.rows and live.tiles.device == a.device and _live_supported(g):
+        tiles = live.tiles
+        _call('tgt_edge_linear', lambda args, st: _lib.lib().tgt_edge_linear_live(args, _ptr(tiles), st), g)
+    else:
+        _call('tgt_edge_linear', _lib.lib().tgt_edge_linear, g)
     return out
+
+
+def _live_supported(g):
+    """does tgt_edge_linear_live take this argument block?  (the 32-row-tile kernels, no fused weight gradient)"""
+    return bool(_lib.lib().tgt_edge_linear_live_supported(C.byref(g)))
 
 
 def edge_linear_supported(K, N, dtype, epilogue=_lib.EPI_BIAS, ln=False, row_scale=False):
@@ -2193,8 +2248,9 @@ class _LinearGeluDropout(torch.autograd.Function):
         pre = torch.empty(*xs[:-1], N, dtype=cd, device=x.device)
         act = torch.empty_like(pre)
         rps = (x2.shape[0] // sample_scale.numel()) if sample_scale is not None else 0
+        ctx.live = _edge_live
         edge_linear_raw(x2, w, b, _lib.EPI_GELU, out=act.view(-1, N), out2=pre.view(-1, N), dropout=(p, seed),
-                        row_scale=sample_scale, rows_per_sample=rps)
+                        row_scale=sample_scale, rows_per_sample=rps, live=ctx.live)
         ctx.save_for_backward(x2, w, pre, sample_scale)
         ctx.meta = (xs, x.dtype, weight.dtype, None if bias is None else bias.dtype, float(p), seed, rps * N)
         ctx.wptr = weight.data_ptr()
@@ -2237,7 +2293,7 @@ class _LinearGeluDropout(torch.autograd.Function):
         if d_pre is None:
             return None, None, None, None, None, None, None, None
         dx, dw, db = _linear_backward(x2, w, d_pre.view(-1, d_pre.shape[-1]), xs, xdt, wdt, bdt, ctx.needs_input_grad[0],
-                                      ctx.needs_input_grad[1], need_db and cs is None, ctx.lazy, dw_ptr=ctx.wptr)
+                                      ctx.needs_input_grad[1], need_db and cs is None, ctx.lazy, dw_ptr=ctx.wptr, live=ctx.live)
         if need_db and cs is not None:
             db = _param_grad(cs, bdt)
         return dx, dw, db, None, None, None, None, None
@@ -2285,8 +2341,9 @@ class _LinearGluDropout(torch.autograd.Function):
         pre = torch.empty(*xs[:-1], N2, dtype=cd, device=x.device)
         act = torch.empty(*xs[:-1], N2 // 2, dtype=cd, device=x.device)
         rps = (x2.shape[0] // sample_scale.numel()) if sample_scale is not None else 0
+        ctx.live = _edge_live
         edge_linear_raw(x2, w, b, _lib.EPI_GLU, out=act.view(-1, N2 // 2), out2=pre.view(-1, N2), dropout=(p, seed),
-                        row_scale=sample_scale, rows_per_sample=rps, flags=kind << _lib.EDGE_GLU_KIND_SHIFT)
+                        row_scale=sample_scale, rows_per_sample=rps, flags=kind << _lib.EDGE_GLU_KIND_SHIFT, live=ctx.live)
         ctx.save_for_backward(x2, w, pre, sample_scale)
         ctx.meta = (xs, x.dtype, weight.dtype, None if bias is None else bias.dtype, kind, float(p), seed, rps * (N2 // 2))
         ctx.wptr = weight.data_ptr()
@@ -2298,7 +2355,7 @@ class _LinearGluDropout(torch.autograd.Function):
         xs, xdt, wdt, bdt, kind, p, seed, eps_ = ctx.meta
         d_pre = _glu_backward(pre, d_act, kind, p, seed, sample_scale, eps_)
         dx, dw, db = _linear_backward(x2, w, d_pre.view(-1, d_pre.shape[-1]), xs, xdt, wdt, bdt, ctx.needs_input_grad[0],
-                                      ctx.needs_input_grad[1], bdt is not None and ctx.needs_input_grad[2], dw_ptr=ctx.wptr)
+                                      ctx.needs_input_grad[1], bdt is not None and ctx.needs_input_grad[2], dw_ptr=ctx.wptr, live=ctx.live)
         return dx, dw, db, None, None, None, None, None
 
 
@@ -2348,6 +2405,7 @@ class _AddLayerNorm(torch.autograd.Function):
         _prof_end('tgt_add_layer_norm_fwd', p0, p1)
         ctx.save_for_backward(s, w, mean, rstd, scale)
         ctx.meta = (weight.dtype, res.dtype, rps)
+        ctx.live = _edge_live             # (the backward may run a Linear's data gradient fused with its own: a row kernel, _ln_backward)
         return s, y
 
     @staticmethod
@@ -2363,7 +2421,7 @@ class _AddLayerNorm(torch.autograd.Function):
             return d_x, d_res.to(rdt), None, None, None, None, None
         # (column sums of d_x: the bias gradient of the Linear that produced x (lin_O / lin_W2 / lin_O_e), handed over on the
         # gradient tensor, see _hand_colsum)
-        d_res, d_x, dg, dbeta, cs = _ln_backward(dy, s, w, mean, rstd, ds, scale, rps, scale is not None)
+        d_res, d_x, dg, dbeta, cs = _ln_backward(dy, s, w, mean, rstd, ds, scale, rps, scale is not None, live=ctx.live)
         if d_x is None:
             d_x = d_res
         _hand_colsum(d_x, cs)
@@ -2403,9 +2461,10 @@ class _LinearResidualLN(torch.autograd.Function):
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         rps = rows // xs[0]
+        ctx.live = _edge_live
         edge_linear_raw(x2, w, b, _lib.EPI_RESID, out=s.view(rows, N), res=res2, row_scale=scale, rows_per_sample=rps,
                         ln=(g, be, eps), stats=(mean, rstd), y=y.view(rows, N),
-                        flags=_lib.EDGE_BIAS_SCALED if (prescaled and scale is not None) else 0)
+                        flags=_lib.EDGE_BIAS_SCALED if (prescaled and scale is not None) else 0, live=ctx.live)
         ctx.gelu = None
         if pre is not None:
             ctx.gelu = (float(gelu[0]), gelu[1], gelu[2] is not None)
@@ -2433,7 +2492,7 @@ class _LinearResidualLN(torch.autograd.Function):
             if pres and bdt is not None and ctx.needs_input_grad[2]:
                 cs = (ds.reshape(scale.numel(), -1, N).float().sum(1) * scale.view(-1, 1)).sum(0)
         else:
-            d_res, d_z, dg, dbeta, cs = _ln_backward(dy, s, g, mean, rstd, ds, scale, rps, scale is not None and not pres)
+            d_res, d_z, dg, dbeta, cs = _ln_backward(dy, s, g, mean, rstd, ds, scale, rps, scale is not None and not pres, live=ctx.live)
             if d_z is None:
                 d_z = d_res
 
@@ -2461,7 +2520,7 @@ class _LinearResidualLN(torch.autograd.Function):
                 dw_part = torch.empty(parts, 256, 256, dtype=torch.float32, device=pre.device) if fuse_dw else None
                 edge_linear_raw(d_z.reshape(rows, N), weight_t(w), None, _lib.EPI_GELU_BWD, out=d_pre.view(rows, -1),
                                 res=pre.view(rows, -1), out_scale=g_scale, rows_per_sample=rps, dropout=(ctx.gelu[0], ctx.gelu[1]),
-                                colsum_partial=part, dw_partial=dw_part)
+                                colsum_partial=part, dw_partial=dw_part, live=ctx.live)
                 if part is not None:
                     with _on_stream(_terminal_fork(rows, part)):
                         _hand_colsum(d_pre, sum_rows(part))
@@ -2472,7 +2531,7 @@ class _LinearResidualLN(torch.autograd.Function):
         dx, dw, db = _linear_backward(x2, w, d_z.reshape(rows, N), xs, xdt, torch.float32 if ctx.col_inv is not None else wdt, bdt,
                                       need_dx, ctx.needs_input_grad[1] and fused_dw is None, need_db and cs is None,
                                       dw_post=None if ctx.col_inv is None else (lambda t: _permute_cols(t.contiguous(), ctx.col_inv, wdt, after_sums=True)),
-                                      dw_ptr=ctx.wptr)
+                                      dw_ptr=ctx.wptr, live=ctx.live)
         if need_db and cs is not None:
             db = _param_grad(cs, bdt)
         if fused_dw is not None:

@@ -11,6 +11,7 @@ from .layers.blocks import PendingResidual
 
 _DEFER_EDGE = K.defer_edge      # A/B knob (tgt_amd/knobs.py)
 _TRI_RAGGED = K.tri_ragged      # triplet attention skips the padded nodes of every graph (default off)
+_EDGE_RAGGED = K.edge_ragged    # the edge row kernels skip the tiles of padded rows (default off; needs _TRI_RAGGED)
 
 
 class Graph(dict):
@@ -68,6 +69,16 @@ class TGT_Encoder(nn.Module):
             graph = self.TGT_layers[layer_idx](graph, defer_edge=defer_edge)
         return graph
 
+    def _edge_ragged_ok(self):
+        """may the edge row kernels leave the padded rows out?  Only when no layer lets a padded row reach a real one: a triplet
+        module must take the node counts (the attention family: every key of a padded node is masked).  The aggregate family's
+        gated outward direction is unmasked (quirk Q2), so its padded rows DO reach real outputs: such a model computes everything."""
+        ok = all(getattr(layer.tria, 'takes_node_counts', False) for layer in self.TGT_layers if hasattr(layer, 'tria'))
+        if not ok:
+            ops._slow_path_notice('edge_ragged', 'TGT_EDGE_RAGGED has no effect on this model: a triplet module that does not take '
+                                  'node counts (the aggregate family) reads padded rows; every edge row is computed')
+        return ok
+
     def forward(self, inputs):
         graph = Graph(inputs)
         # ragged batches: the per-graph node counts the triplet attention kernels skip behind, once per forward from the mask
@@ -75,11 +86,17 @@ class TGT_Encoder(nn.Module):
         own_counts = _TRI_RAGGED and graph.get('node_counts') is None and graph.mask.is_cuda
         if own_counts:
             graph['node_counts'] = ops.mask_node_counts(ops.as_mask3(graph.mask, graph.e.shape[0], graph.e.shape[1]))
-        for idx in range(self.model_height):
-            # between layers the closing edge residual travels un-added (layers.PendingResidual)
-            graph = self.apply_layer(idx, graph, defer_edge=_DEFER_EDGE)
-        if isinstance(graph.e, PendingResidual):
-            graph.e = graph.e.materialize()
+        # ... and the live tile list the persistent edge row kernels walk (TGT_EDGE_RAGGED): one more launch per forward, carried
+        # by an ops context around the layer loop; the padded rows of the edge stream are then zeros in whole dead tiles
+        live = None
+        if _EDGE_RAGGED and _TRI_RAGGED and graph.get('node_counts') is not None and graph.e.is_cuda and self._edge_ragged_ok():
+            live = ops.edge_live_tiles(graph['node_counts'], graph.e.shape[1])
+        with ops.edge_live(live):
+            for idx in range(self.model_height):
+                # between layers the closing edge residual travels un-added (layers.PendingResidual)
+                graph = self.apply_layer(idx, graph, defer_edge=_DEFER_EDGE)
+            if isinstance(graph.e, PendingResidual):
+                graph.e = graph.e.materialize()
         side = graph.pop('node_side', None)
         if side is not None:
             side.join(graph.h)
