@@ -251,18 +251,20 @@ def _step(model, batch, autocast):
 def test_training_step_is_bit_identical_with_both_switches_on(autocast, monkeypatch):
     """TGT_TRI_RAGGED (the model computes and hands down the counts) + TGT_TRI_RAGGED_KB (the kernels for N > 64 use them) against
     both off: the loss, every parameter gradient and the outputs on real nodes and edges"""
-    from tgt_amd import ops
+    from tgt_amd import ops, _lib
     from tgt_amd.pcqm import TGT_Multi
     from tgt_amd.tgt import stack
     model = gu.fill_params(TGT_Multi(**CFG), seed=31).cuda().train()
     batch = {k: v.cuda() for k, v in gu.model_batch(GEOM, seed=32).items()}
     flags = []
-    real_call = ops._call_counts
+    real_launch = ops._launch
 
-    def spy(name, args, node_counts, counts_kb=False):
-        flags.append((name, node_counts is not None, counts_kb))
-        return real_call(name, args, node_counts, counts_kb)
-    monkeypatch.setattr(ops, '_call_counts', spy)
+    def spy(entry, *args, prof=None):
+        # (the triplet attention launches: counts given = the _counts entry, the flag = TRI_COUNTS_KB on the argument block)
+        if entry.startswith(('tgt_triplet_attention_fwd', 'tgt_triplet_attention_bwd')):
+            flags.append((entry, entry.endswith('_counts'), bool(args[0]._obj.flags & _lib.TRI_COUNTS_KB)))
+        return real_launch(entry, *args, prof=prof)
+    monkeypatch.setattr(ops, '_launch', spy)
     monkeypatch.setattr(stack, '_TRI_RAGGED', False)
     monkeypatch.setattr(ops, '_TRI_RAGGED_KB', False)
     loss0, out0, grads0 = _step(model, batch, autocast)

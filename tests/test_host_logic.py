@@ -250,3 +250,158 @@ def test_slow_kernel_family_is_announced_once():
         ops._slow_path_notice(('x', 'y'), 'first')
         ops._slow_path_notice(('x', 'y'), 'second')
     assert len(w) == 1 and 'first' in str(w[0].message) and issubclass(w[0].category, RuntimeWarning)
+
+
+# ---- ops._launch, the one way a kernel is enqueued, and the skip record of the triplet ops.  As in the binding tests nothing is
+# launched and no pointer is dereferenced: the argument blocks are refused, or done (an empty batch), before memory is touched
+def _aggregate_block(B=2, N=20):
+    from tgt_amd import _lib
+    a = _lib.TripletAggregateArgs()
+    a.B, a.N, a.H, a.D, a.dtype, a.flags = B, N, 16, 16, _lib.TGT_BF16, _lib.TRI_BIASED | _lib.TRI_GATED
+    return a
+
+
+def test_launcher_labels_an_error_with_the_entry_it_called(monkeypatch):
+    import ctypes as C
+    from tgt_amd import ops
+    monkeypatch.setattr(ops, '_stream', lambda: None)
+    a = _aggregate_block(N=-1)
+    for entry in ('tgt_triplet_aggregate_fwd', 'tgt_triplet_aggregate_bwd'):
+        with pytest.raises(RuntimeError, match=entry + r' failed \(code 1\).*bad sizes'):
+            ops._launch(entry, C.byref(a), prof='tgt_triplet_aggregate_fwd')
+    with pytest.raises(RuntimeError, match=r'tgt_triplet_aggregate_fwd_skip failed \(code 1\).*bad sizes'):
+        ops._launch('tgt_triplet_aggregate_fwd_skip', C.byref(a), None, prof='tgt_triplet_aggregate_fwd')
+    assert ops._launch('tgt_triplet_aggregate_fwd', C.byref(_aggregate_block(B=0))) is None      # an empty batch: done, cleanly
+    with pytest.raises(AttributeError):
+        ops._launch('tgt_no_such_entry')
+
+
+def test_launcher_samples_counts_and_records_under_the_one_name_it_is_given(monkeypatch):
+    import ctypes as C
+    from tgt_amd import ops
+    recorded = []
+
+    class FakeEvent:
+        def __init__(self, enable_timing=False):
+            assert enable_timing
+
+        def record(self):
+            recorded.append(self)
+    monkeypatch.setattr(torch.cuda, 'Event', FakeEvent)
+    monkeypatch.setattr(ops, '_stream', lambda: None)
+    empty = _aggregate_block(B=0)
+
+    def launch(prof):
+        ops._launch('tgt_triplet_aggregate_fwd', C.byref(empty), prof=prof)
+    try:
+        prof = ops.profile_kernels(True, only={'tgt_layer_norm_bwd'}, stride=2)
+        for name in ['tgt_layer_norm_bwd', 'tgt_colsum', None] * 3 + ['tgt_layer_norm_bwd'] * 2:
+            launch(name)
+        assert list(prof) == ['tgt_layer_norm_bwd'] and len(prof['tgt_layer_norm_bwd']) == 3         # launches 0, 2 and 4 of five
+        assert all(isinstance(ev, FakeEvent) for pair in prof['tgt_layer_norm_bwd'] for ev in pair) and len(recorded) == 6
+        assert ops.profile_launch_counts() == {'tgt_layer_norm_bwd': 5}                               # (no None key, no other name)
+        # every name, one launch in two: counted and sampled per name; prof=None stays out of both
+        prof = ops.profile_kernels(True, stride=2)
+        for name in ('tgt_colsum', None, 'tgt_colsum', 'tgt_colsum', 'tgt_layer_norm_fwd', None):
+            launch(name)
+        assert {k: len(v) for k, v in prof.items()} == {'tgt_colsum': 2, 'tgt_layer_norm_fwd': 1}
+        assert ops.profile_launch_counts() == {'tgt_colsum': 3, 'tgt_layer_norm_fwd': 1}
+        # stride 1: everything named is recorded, nothing is counted
+        prof = ops.profile_kernels(True)
+        for name in ('tgt_colsum', None, 'tgt_colsum'):
+            launch(name)
+        assert {k: len(v) for k, v in prof.items()} == {'tgt_colsum': 2} and ops.profile_launch_counts() == {}
+    finally:
+        ops.profile_kernels(False)
+    n = len(recorded)
+    launch('tgt_colsum')
+    assert len(recorded) == n and ops._PROFILE is None
+
+
+class _PerGraph:
+    """stands in for a per-graph device tensor: only what the check asks"""
+
+    def __init__(self, dtype, n, contiguous=True, is_cuda=True):
+        self.dtype, self.n, self.contiguous, self.is_cuda = dtype, n, contiguous, is_cuda
+
+    def numel(self):
+        return self.n
+
+    def is_contiguous(self):
+        return self.contiguous
+
+
+def test_per_graph_vectors_of_the_triplet_ops_are_checked_in_one_place():
+    from tgt_amd import ops
+    B = 3
+    counts, scale = _PerGraph(torch.int32, B), _PerGraph(torch.float32, B)
+    assert ops._check_per_graph(None, B, torch.int32, 'x') is None and ops._check_per_graph(counts, B, torch.int32, 'x') is counts
+    bad_counts = [_PerGraph(torch.int64, B), _PerGraph(torch.int32, B + 1), _PerGraph(torch.int32, B, contiguous=False),
+                  _PerGraph(torch.int32, B, is_cuda=False), torch.zeros(B, dtype=torch.int32)]
+    bad_scale = [_PerGraph(torch.float16, B), _PerGraph(torch.float32, B - 1), _PerGraph(torch.float32, B, contiguous=False),
+                 _PerGraph(torch.float32, B, is_cuda=False), torch.ones(B)]
+    for t in bad_counts:
+        with pytest.raises(RuntimeError) as err:
+            ops._TriSkip.of('triplet attention', B, 20, node_counts=t)
+        assert str(err.value) == 'triplet attention: node_counts must be a contiguous int32 device tensor with one value per graph'
+        if t.numel() == B:                  # (edge_live_tiles takes the batch size FROM the counts)
+            with pytest.raises(RuntimeError, match='triplet attention: node_counts must be a contiguous int32 device tensor'):
+                ops.edge_live_tiles(t, 20)
+    for op in ('triplet attention', 'triplet aggregate'):
+        for t in bad_scale:
+            with pytest.raises(RuntimeError) as err:
+                ops._TriSkip.of(op, B, 20, graph_scale=t)
+            assert str(err.value) == op + ': graph_scale must be a contiguous float32 device tensor with one value per graph'
+    assert ops._TriSkip.of('triplet attention', B, 20, counts, scale) == (counts, False, scale)
+
+
+def test_skip_record_decides_what_a_triplet_backward_skips(monkeypatch):
+    from tgt_amd import ops
+    B = 3
+    counts, scale = _PerGraph(torch.int32, B), _PerGraph(torch.float32, B)
+    # counts_kb: N > 64, counts given, the switch on -- all three
+    for ragged_kb in (False, True):
+        monkeypatch.setattr(ops, '_TRI_RAGGED_KB', ragged_kb)
+        for N in (64, 65, 128):
+            for nc in (None, counts):
+                skip = ops._TriSkip.of('triplet attention', B, N, nc, scale)
+                assert skip.counts_kb is (ragged_kb and N > 64 and nc is not None), (ragged_kb, N, nc)
+                assert skip.node_counts is nc and skip.graph_scale is scale
+    # the backward's factors: with TGT_TRI_SKIP=2, or behind a projection-fused forward; its counts and flag: always the forward's
+    skip = ops._TriSkip.of('triplet attention', B, 72, counts, scale)
+    assert skip.counts_kb
+    for skip_bwd in (False, True):
+        monkeypatch.setattr(ops, '_TRI_SKIP_BWD', skip_bwd)
+        for fused in (False, True):
+            bwd = skip.for_backward(projection_fused=fused)
+            assert bwd.graph_scale is (scale if (skip_bwd or fused) else None), (skip_bwd, fused)
+            assert bwd.node_counts is counts and bwd.counts_kb is True
+        assert skip.for_backward().graph_scale is (scale if skip_bwd else None)
+        assert ops._TriSkip.of('triplet aggregate', B, 20).for_backward(True) == (None, False, None)
+    # decided once: what the forward stored does not move with the switches
+    monkeypatch.setattr(ops, '_TRI_SKIP_BWD', False)
+    monkeypatch.setattr(ops, '_TRI_RAGGED_KB', False)
+    assert bwd.graph_scale is scale and bwd.counts_kb is True
+    with pytest.raises(AttributeError):
+        skip.graph_scale = None
+    assert not hasattr(skip, '__dict__')
+
+
+def test_compute_dtype_keeps_both_spellings_of_its_call_sites(monkeypatch):
+    from tgt_amd import ops
+    x = torch.zeros(2, dtype=torch.float32)                    # a CPU tensor: where the two spellings differ
+    assert ops._compute_dtype(x) is torch.float32 and ops._compute_dtype(x, on_cpu=True) is torch.float32
+    assert ops._compute_dtype(x, otherwise=torch.float64) is torch.float64
+    # CUDA autocast on (torch switches it off by itself where there is no GPU: its state is stood in for)
+    monkeypatch.setattr(torch, 'is_autocast_enabled', lambda device: device == 'cuda')
+    monkeypatch.setattr(torch, 'get_autocast_dtype', lambda device: torch.bfloat16)
+    assert ops._compute_dtype(x) is torch.float32
+    assert ops._compute_dtype(x, otherwise=torch.float64) is torch.float64
+    assert ops._compute_dtype(x, on_cpu=True) is torch.bfloat16
+    assert ops._compute_dtype(_PerGraph(torch.float32, 2)) is torch.bfloat16
+    assert ops._compute_dtype(_PerGraph(torch.float32, 2), otherwise=torch.float64) is torch.bfloat16
+    monkeypatch.undo()
+    p = torch.zeros(2, requires_grad=True)
+    assert ops._no_backward(x, None) and not ops._no_backward(x, None, p)
+    with torch.no_grad():
+        assert ops._no_backward(x, p)

@@ -78,15 +78,20 @@ def kernel_times_ms(prof):
     return {k: [s.elapsed_time(e) for s, e in v] for k, v in prof.items()}
 
 
-def _call(name, fn, args):
-    if _PROFILE is None or not _timed(name):
-        _lib.check(fn(C.byref(args), _stream()), name)
+def _launch(entry, *args, prof=None):
+    """THE way work is enqueued: libtgt_hip's `entry`(*args, current stream), its return code checked under that name.
+    prof: the name this launch offers itself to a running profile under (None: never timed) -- _timed() samples and counts it,
+    and the events are recorded, under that one name.  Several entries may share a name (the _counts / _skip / _live forms report
+    as the plain kernel)."""
+    fn = getattr(_lib.lib(), entry)
+    if prof is None or _PROFILE is None or not _timed(prof):
+        _lib.check(fn(*args, _stream()), entry)
         return
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
-    _lib.check(fn(C.byref(args), _stream()), name)
+    _lib.check(fn(*args, _stream()), entry)
     e.record()
-    _PROFILE.setdefault(name, []).append((s, e))
+    _PROFILE.setdefault(prof, []).append((s, e))
 
 
 def _dev(*tensors):
@@ -94,6 +99,20 @@ def _dev(*tensors):
         if t is not None and not t.is_cuda:
             raise RuntimeError('tgt_amd ops run on the MI355X only: got a CPU tensor '
                                '(there is no CPU fallback; the CPU restatement lives in oracle/ and is test-only)')
+
+
+def _compute_dtype(x, on_cpu=False, otherwise=None):
+    """the dtype an op computes in: CUDA autocast's while that is on, else `otherwise` (default: x.dtype).  on_cpu: also for a CPU
+    tensor x (the entries that take only the autocast state into account; the others leave a CPU tensor its dtype)"""
+    if torch.is_autocast_enabled('cuda') and (on_cpu or x.is_cuda):
+        return torch.get_autocast_dtype('cuda')
+    return x.dtype if otherwise is None else otherwise
+
+
+def _no_backward(*tensors):
+    """can NO backward follow this call (torch.no_grad(), or nothing requires grad)?  Grad mode is always off INSIDE
+    Function.forward and ctx.needs_input_grad ignores torch.no_grad(): asked before .apply"""
+    return not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors))
 
 
 def _stream():
@@ -107,29 +126,54 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def _check_node_counts(node_counts, B):
-    """per-graph node counts of the triplet attention kernels (tgt_hip.h, tgt_triplet_attention_fwd_counts): checked like
-    graph_scale; the values stay on the device (the kernels clamp them)"""
-    if node_counts is not None and (node_counts.dtype != torch.int32 or node_counts.numel() != B or not node_counts.is_contiguous() or
-                                    not node_counts.is_cuda):
-        raise RuntimeError('triplet attention: node_counts must be a contiguous int32 device tensor with one value per graph')
-    return node_counts
+def _check_per_graph(t, B, dtype, noun):
+    """a per-graph vector the triplet kernels read (node counts, DropPath factors; tgt_hip.h, the _counts / _skip entries): None, or
+    a contiguous device tensor of `dtype` with one value per graph.  The values stay on the device (the kernels clamp the counts)."""
+    if t is not None and (t.dtype != dtype or t.numel() != B or not t.is_contiguous() or not t.is_cuda):
+        word = str(dtype).removeprefix('torch.')            # 'int32' / 'float32'
+        raise RuntimeError(f'{noun} must be a contiguous {word} device tensor with one value per graph')
+    return t
 
 
-def _counts_kb(node_counts, N):
-    """does this forward hand its node counts to the key-blocked kernels?  (its backward takes the answer from ctx)"""
-    return bool(_TRI_RAGGED_KB and node_counts is not None and N > 64)
+class _TriSkip(collections.namedtuple('_TriSkip', 'node_counts counts_kb graph_scale')):
+    """What ONE triplet launch skips: the per-graph node counts (attention only), whether the key-blocked kernels (N > 64) get
+    them too -- the flag bit TRI_COUNTS_KB -- and the DropPath factors whose zeros are dropped graphs.  A forward builds it once
+    (of), launches with it, and keeps what for_backward() answers as ctx.skip: its backward launches with THAT, so it skips
+    what the forward skipped whatever the switches say by then."""
+    __slots__ = ()
 
+    @classmethod
+    def of(cls, op, B, N, node_counts=None, graph_scale=None):
+        """checked; op: 'triplet attention' / 'triplet aggregate' (words the error)"""
+        _check_per_graph(node_counts, B, torch.int32, op + ': node_counts')
+        _check_per_graph(graph_scale, B, torch.float32, op + ': graph_scale')
+        return cls(node_counts, bool(_TRI_RAGGED_KB and node_counts is not None and N > 64), graph_scale)
 
-def _call_counts(name, args, node_counts, counts_kb=False):
-    """tgt_triplet_attention_fwd / _bwd (`name`), through the _counts entry point when node counts are given; counts_kb: with
-    TRI_COUNTS_KB on the argument block (N > 64)"""
-    if counts_kb:
-        args.flags |= _lib.TRI_COUNTS_KB
-    if node_counts is None:
-        return _call(name, getattr(_lib.lib(), name), args)
-    fn = getattr(_lib.lib(), name + '_counts')
-    _call(name, lambda a, st: fn(a, _ptr(node_counts), st), args)
+    def for_backward(self, projection_fused=False):
+        """same counts, same flag; the factors only with TGT_TRI_SKIP=2 (_TRI_SKIP_BWD, see above) -- except behind a
+        projection-fused forward, which wrote NO Q/K/V rows for the dropped graphs: that backward must skip them"""
+        return self if (projection_fused or _TRI_SKIP_BWD) else self._replace(graph_scale=None)
+
+    def launch_attention(self, a, bwd=False):
+        """tgt_triplet_attention_fwd / _bwd on argument block a (the factors are on it: _tri_args), through the _counts entry
+        when there are node counts"""
+        if self.counts_kb:
+            a.flags |= _lib.TRI_COUNTS_KB
+        name = 'tgt_triplet_attention_bwd' if bwd else 'tgt_triplet_attention_fwd'
+        if self.node_counts is None:
+            _launch(name, C.byref(a), prof=name)
+        else:
+            _launch('tgt_triplet_attention_bwd_counts' if bwd else 'tgt_triplet_attention_fwd_counts', C.byref(a), _ptr(self.node_counts),
+                    prof=name)
+
+    def launch_aggregate(self, a, bwd=False):
+        """tgt_triplet_aggregate_fwd / _bwd on argument block a, through the _skip entry when there are DropPath factors"""
+        name = 'tgt_triplet_aggregate_bwd' if bwd else 'tgt_triplet_aggregate_fwd'
+        if self.graph_scale is None:
+            _launch(name, C.byref(a), prof=name)
+        else:
+            _launch('tgt_triplet_aggregate_bwd_skip' if bwd else 'tgt_triplet_aggregate_fwd_skip', C.byref(a), _ptr(self.graph_scale),
+                    prof=name)
 
 
 def mask_node_counts(mask3):
@@ -140,7 +184,7 @@ def mask_node_counts(mask3):
     if mask3.dim() != 3 or mask3.shape[1] != mask3.shape[2] or mask3.dtype != torch.float32 or not mask3.is_contiguous():
         raise RuntimeError('mask_node_counts: expects a contiguous float32 (B,N,N) mask')
     counts = torch.empty(mask3.shape[0], dtype=torch.int32, device=mask3.device)
-    _lib.check(_lib.lib().tgt_mask_node_counts(_ptr(mask3), mask3.shape[0], mask3.shape[1], _ptr(counts), _stream()), 'tgt_mask_node_counts')
+    _launch('tgt_mask_node_counts', _ptr(mask3), mask3.shape[0], mask3.shape[1], _ptr(counts))
     return counts
 
 
@@ -157,12 +201,10 @@ def edge_live_tiles(node_counts, N):
     """(B,) int32 node counts on the device -> EdgeLiveTiles: which 32-row tiles of the (B*N*N, C) edge rows hold a real row
     (tgt_hip.h, tgt_edge_live_tiles; the counts are clamped to [0, N] in the kernel).  One launch, no host synchronisation."""
     B = node_counts.numel()
-    _check_node_counts(node_counts, B)
-    if not node_counts.is_cuda:
-        _dev(node_counts)
+    _check_per_graph(node_counts, B, torch.int32, 'triplet attention: node_counts')
     rows = B * int(N) * int(N)
     tiles = torch.empty(1 + (rows + 31) // 32, dtype=torch.int32, device=node_counts.device)
-    _lib.check(_lib.lib().tgt_edge_live_tiles(_ptr(node_counts), B, int(N), _ptr(tiles), _stream()), 'tgt_edge_live_tiles')
+    _launch('tgt_edge_live_tiles', _ptr(node_counts), B, int(N), _ptr(tiles))
     return EdgeLiveTiles(tiles, rows)
 
 
@@ -252,9 +294,7 @@ def _tri_args(fused, mask3, out, L, d_out=None, d_fused=None, colsum=None, dropo
     a.out, a.ld_out = out.data_ptr(), 2 * L.C
     a.o_off = _pair(C.c_int32, 0, L.C)
     a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFFFFFFFFFF
-    if graph_scale is not None:           # per-graph DropPath factor of the branch: graphs at exactly 0 are not computed
-        if graph_scale.dtype != torch.float32 or graph_scale.numel() != B or not graph_scale.is_contiguous() or not graph_scale.is_cuda:
-            raise RuntimeError('triplet attention: graph_scale must be a contiguous float32 device tensor with one value per graph')
+    if graph_scale is not None:           # per-graph DropPath factor of the branch (checked by _TriSkip.of): graphs at exactly 0 are not computed
         a.graph_scale = graph_scale.data_ptr()
     if d_out is not None:
         a.d_out = d_out.data_ptr()
@@ -346,12 +386,10 @@ class _TripletAttention(torch.autograd.Function):
         B, N = fused.shape[0], fused.shape[1]
         assert fused.shape == (B, N, N, L.width), (fused.shape, L.width)
         out = torch.empty(B, N, N, 2 * L.C, dtype=fused.dtype, device=fused.device)
-        a = _tri_args(fused, mask3, out, L, dropout=dropout, graph_scale=graph_scale)
-        ctx.counts_kb = _counts_kb(_check_node_counts(node_counts, B), N)
-        _call_counts('tgt_triplet_attention_fwd', a, node_counts, ctx.counts_kb)
+        skip = _TriSkip.of('triplet attention', B, N, node_counts, graph_scale)
+        skip.launch_attention(_tri_args(fused, mask3, out, L, dropout=dropout, graph_scale=graph_scale))
         ctx.save_for_backward(fused, mask3, out)
-        ctx.L, ctx.dropout, ctx.graph_scale = L, dropout, (graph_scale if _TRI_SKIP_BWD else None)
-        ctx.node_counts = node_counts          # (the backward must skip what the forward skipped: same counts, same flag)
+        ctx.L, ctx.dropout, ctx.skip = L, dropout, skip.for_backward()
         return out
 
     @staticmethod
@@ -361,8 +399,8 @@ class _TripletAttention(torch.autograd.Function):
         d_fused = torch.empty_like(fused)          # every used column is written by the kernel
         if ctx.L.width > ctx.L.used:
             d_fused[..., ctx.L.used:] = 0
-        a = _tri_args(fused, mask3, out, ctx.L, d_out, d_fused, dropout=ctx.dropout, graph_scale=ctx.graph_scale)
-        _call_counts('tgt_triplet_attention_bwd', a, ctx.node_counts, ctx.counts_kb)
+        a = _tri_args(fused, mask3, out, ctx.L, d_out, d_fused, dropout=ctx.dropout, graph_scale=ctx.skip.graph_scale)
+        ctx.skip.launch_attention(a, bwd=True)
         return d_fused, None, None, None, None, None
 
 
@@ -437,13 +475,12 @@ def _queue():
 
 
 def _run_sums(pairs):
-    L = _lib.lib()
     for i in range(0, len(pairs), _lib.SUM_MANY_MAX):
         chunk = pairs[i:i + _lib.SUM_MANY_MAX]
         items = (_lib.SumItem * len(chunk))()
         for it, (part, out) in zip(items, chunk):
             it.src, it.dst, it.planes, it.n = part.data_ptr(), out.data_ptr(), part.shape[0], out.numel()
-        _lib.check(L.tgt_sum_many(items, len(chunk), _stream()), 'tgt_sum_many')
+        _launch('tgt_sum_many', items, len(chunk))
         _deferred_stats[1] += 1
 
 
@@ -505,7 +542,7 @@ def sum_planes(part, out, defer=True):
         if len(q[0]) >= _DEFER_MAX:
             _flush_queue(q)
         return out
-    _lib.check(_lib.lib().tgt_sum_planes(_ptr(part), part.shape[0], out.numel(), _ptr(out), _stream()), 'tgt_sum_planes')
+    _launch('tgt_sum_planes', _ptr(part), part.shape[0], out.numel(), _ptr(out))
     return out
 
 
@@ -556,7 +593,7 @@ def _fuse_params(table, params, cd):
     w = torch.empty(table.n_rows, table.n_cols, dtype=cd, device=params[0].device)
     b = torch.empty(table.n_rows, dtype=cd, device=params[0].device)
     a = _fuse_args(table, srcs[0::2], srcs[1::2], w, b)
-    _lib.check(_lib.lib().tgt_fuse_rows(C.byref(a), _stream()), 'tgt_fuse_rows')
+    _launch('tgt_fuse_rows', C.byref(a))
     return w, b
 
 
@@ -574,7 +611,7 @@ def _unfuse_grads(table, params, dW, db):
     keep = [t.detach() for t in (dW, db, *grads)]       # aliases: the memory stays, the gradient objects keep ONE owner (see sum_planes)
 
     def run():
-        _lib.check(_lib.lib().tgt_unfuse_rows(C.byref(a), _stream()), 'tgt_unfuse_rows')
+        _launch('tgt_unfuse_rows', C.byref(a))
         keep.clear()
     _after_sums(run)
     return grads
@@ -648,11 +685,11 @@ class _ProjectedTripletAttention(torch.autograd.Function):
     def forward(ctx, x, mask3, L, cd, table, dropout, graph_scale, no_backward, node_counts, *wb):
         _dev(x, mask3)
         B, N = x.shape[0], x.shape[1]
-        counts_kb = _counts_kb(_check_node_counts(node_counts, B), N)       # (N > 64 is GEMMs + the plain kernels below)
+        skip = _TriSkip.of('triplet attention', B, N, node_counts, graph_scale)      # (N > 64 is GEMMs + the plain kernels below)
         weight, bias = wb if table is None else _fuse_params(table, wb, cd)
         out = torch.empty(B, N, N, 2 * L.C, dtype=cd, device=x.device)
         eg = None
-        proj_skip = None
+        projection_fused = False
         if x.numel() // L.C >= _SPLIT_MIN_ROWS and not (dropout[0] == 0 and _proj_fused_ok(x, N, L, cd)) and _TRI_PROJ:
             why = ('N > 64' if N > 64 else 'N > 32' if N > 32 else 'attention dropout > 0' if dropout[0] else 'head dim != 16' if L.D != 16 else
                    'heads not a multiple of 8' if L.H % 8 else 'edge width != 256' if L.C != 256 else
@@ -678,25 +715,17 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             # TGT_TRI_PROJ_INFER=0 is the A/B knob
             infer = _TRI_PROJ_INFER and no_backward
             fused = None if infer else torch.empty(B, N, N, 6 * L.C, dtype=cd, device=x.device)
-            we, be = w[6 * L.C:L.used], b[6 * L.C:L.used]
-            if not L.biased:
-                eg = None                      # (axial: no third arm)
-            elif we.shape[0] <= 128 and _edge_kernel_ok(x2, we.shape[0], cd):
-                eg = edge_linear_raw(x2, we, be.contiguous()).view(B, N, N, L.used - 6 * L.C)
-            else:
-                eg = torch.addmm(be, x2, we.t()).view(B, N, N, L.used - 6 * L.C)
+            if L.biased:                       # (axial: no third arm)
+                eg = _narrow_linear(x2, w[6 * L.C:L.used], b[6 * L.C:L.used], cd).view(B, N, N, L.used - 6 * L.C)
             a = _tri_args(fused, mask3, out, L, eg=eg, graph_scale=graph_scale)
-            s0, s1 = _prof_begin('tgt_triplet_attention_proj_fwd')
             if node_counts is None:
-                _lib.check(_lib.lib().tgt_triplet_attention_proj_fwd(C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), _stream()),
-                           'tgt_triplet_attention_proj_fwd')
+                _launch('tgt_triplet_attention_proj_fwd', C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), prof='tgt_triplet_attention_proj_fwd')
             else:              # (padded units: no Q/K/V rows either -- the backward below gets the same counts)
-                _lib.check(_lib.lib().tgt_triplet_attention_proj_fwd_counts(C.byref(a), _ptr(node_counts), _ptr(x2), L.C, _ptr(w), _ptr(b),
-                                                                            _stream()), 'tgt_triplet_attention_proj_fwd_counts')
-            _prof_end('tgt_triplet_attention_proj_fwd', s0, s1)
+                _launch('tgt_triplet_attention_proj_fwd_counts', C.byref(a), _ptr(node_counts), _ptr(x2), L.C, _ptr(w), _ptr(b),
+                        prof='tgt_triplet_attention_proj_fwd')
             if infer:
                 return out                 # (nothing to save: no backward exists)
-            proj_skip = graph_scale        # (dropped graphs have NO Q/K/V rows: the backward must skip them too)
+            projection_fused = True        # (dropped graphs have NO Q/K/V rows: the backward must skip them too)
         elif _split_projection_ok(x, L):
             # two GEMMs: Q/K/V (6C = 1536 channels: six full 256-wide tile columns, 294 us) and the
             # narrow E/G (39 us) instead of one ragged 1600-wide GEMM (376 us; tools/gemm_probe.py);
@@ -705,23 +734,14 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             x2 = x2 if x2.dtype == cd else x2.to(cd)
             w, b = _as_dtype(weight, cd), _as_dtype(bias, cd)
             fused = torch.addmm(b[:6 * L.C], x2, w[:6 * L.C].t()).view(B, N, N, 6 * L.C)
-            we, be = w[6 * L.C:L.used], b[6 * L.C:L.used]
-            if we.shape[0] <= 128 and we.is_contiguous() and _edge_kernel_ok(x2, we.shape[0], cd):
-                # the narrow third-arm projection on the weight-resident slice kernel (29 vs 37 us against the tuned library GEMM)
-                eg = edge_linear_raw(x2, we, be.contiguous()).view(B, N, N, L.used - 6 * L.C)
-            else:
-                eg = torch.addmm(be, x2, we.t()).view(B, N, N, L.used - 6 * L.C)
-            a = _tri_args(fused, mask3, out, L, dropout=dropout, eg=eg, graph_scale=graph_scale)
-            _call_counts('tgt_triplet_attention_fwd', a, node_counts, counts_kb)
+            eg = _narrow_linear(x2, w[6 * L.C:L.used], b[6 * L.C:L.used], cd).view(B, N, N, L.used - 6 * L.C)
+            skip.launch_attention(_tri_args(fused, mask3, out, L, dropout=dropout, eg=eg, graph_scale=graph_scale))
         else:
             x2, w, fused = _linear_forward(x, weight, bias, cd)
-            a = _tri_args(fused, mask3, out, L, dropout=dropout, graph_scale=graph_scale)
-            _call_counts('tgt_triplet_attention_fwd', a, node_counts, counts_kb)
+            skip.launch_attention(_tri_args(fused, mask3, out, L, dropout=dropout, graph_scale=graph_scale))
         ctx.save_for_backward(x2, w, fused, mask3, out, eg if eg is not None else fused.new_empty(0),
                               *(wb if table is not None else ()))
-        ctx.L, ctx.table, ctx.dropout = L, table, dropout
-        ctx.graph_scale = proj_skip if proj_skip is not None else (graph_scale if _TRI_SKIP_BWD else None)
-        ctx.node_counts, ctx.counts_kb = node_counts, counts_kb
+        ctx.L, ctx.table, ctx.dropout, ctx.skip = L, table, dropout, skip.for_backward(projection_fused)
         ctx.meta = (x.shape, x.dtype, weight.dtype, bias.dtype)
         return out
 
@@ -739,8 +759,8 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         # (N > 64: the key-blocked kernels produce no column sums; the bias gradient is a column-sum pass over d_fused)
         kb = fused.shape[1] > 64
         colsum = None if kb else _colsum_workspace(fused.shape[0], L.width, L.used, fused.device)
-        a = _tri_args(fused, mask3, out, L, d_out, d_fused, colsum, dropout=ctx.dropout, eg=eg, graph_scale=ctx.graph_scale)
-        _call_counts('tgt_triplet_attention_bwd', a, ctx.node_counts, ctx.counts_kb)
+        a = _tri_args(fused, mask3, out, L, d_out, d_fused, colsum, dropout=ctx.dropout, eg=eg, graph_scale=ctx.skip.graph_scale)
+        ctx.skip.launch_attention(a, bwd=True)
         if _GATE_NODE_BWD == 1:
             _gate_record(d_fused.device)
         need_p = any(ctx.needs_input_grad[9:])
@@ -787,12 +807,9 @@ def projected_triplet_attention(x, weight, bias, mask3, layout, table=None, drop
     the counts are used with TGT_TRI_RAGGED_KB=1 only, as in triplet_attention."""
     if not _TRI_COLSUM and table is None:      # A/B knob: separate bias-gradient pass
         return triplet_attention(linear(x, weight, bias), mask3, layout, dropout, graph_scale, node_counts)
-    cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
     wb = (weight, bias) if table is None else tuple(weight)
-    # (grad mode is always off INSIDE Function.forward and ctx.needs_input_grad ignores torch.no_grad(): whether a backward can
-    # follow is decided here)
-    no_backward = not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, *wb)))
-    return _ProjectedTripletAttention.apply(x, mask3, layout, cd, table, dropout, graph_scale, no_backward, node_counts, *wb)
+    return _ProjectedTripletAttention.apply(x, mask3, layout, _compute_dtype(x), table, dropout, graph_scale, _no_backward(x, *wb),
+                                            node_counts, *wb)
 
 
 # ---------------------------------------------------------------------------
@@ -841,23 +858,6 @@ def _agg_args(fused, mask3, out, L, d_out=None, d_fused=None, dropout=(0.0, 0)):
     return a
 
 
-def _check_agg_graph_scale(graph_scale, B):
-    """per-graph DropPath factor of the triplet aggregate kernels (tgt_hip.h, tgt_triplet_aggregate_fwd_skip): checked as _tri_args
-    checks the attention's; the values stay on the device"""
-    if graph_scale is not None and (graph_scale.dtype != torch.float32 or graph_scale.numel() != B or not graph_scale.is_contiguous() or
-                                    not graph_scale.is_cuda):
-        raise RuntimeError('triplet aggregate: graph_scale must be a contiguous float32 device tensor with one value per graph')
-    return graph_scale
-
-
-def _call_skip(name, args, graph_scale):
-    """tgt_triplet_aggregate_fwd / _bwd (`name`), through the _skip entry point when DropPath factors are given"""
-    if graph_scale is None:
-        return _call(name, getattr(_lib.lib(), name), args)
-    fn = getattr(_lib.lib(), name + '_skip')
-    _call(name, lambda a, st: fn(a, _ptr(graph_scale), st), args)
-
-
 class _TripletAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, fused, mask3, L, dropout=(0.0, 0), graph_scale=None):
@@ -866,11 +866,10 @@ class _TripletAggregate(torch.autograd.Function):
         B, N = fused.shape[0], fused.shape[1]
         assert fused.shape == (B, N, N, L.width), (fused.shape, L.width)
         out = torch.empty(B, N, N, 2 * L.C, dtype=fused.dtype, device=fused.device)
-        a = _agg_args(fused, mask3, out, L, dropout=dropout)
-        _call_skip('tgt_triplet_aggregate_fwd', a, _check_agg_graph_scale(graph_scale, B))
+        skip = _TriSkip.of('triplet aggregate', B, N, graph_scale=graph_scale)
+        skip.launch_aggregate(_agg_args(fused, mask3, out, L, dropout=dropout))
         ctx.save_for_backward(fused, mask3, out)
-        ctx.L, ctx.dropout = L, dropout
-        ctx.graph_scale = graph_scale if _TRI_SKIP_BWD else None       # (as _TripletAttention: the backward skips with TGT_TRI_SKIP=2)
+        ctx.L, ctx.dropout, ctx.skip = L, dropout, skip.for_backward()
         return out
 
     @staticmethod
@@ -880,8 +879,7 @@ class _TripletAggregate(torch.autograd.Function):
         d_fused = torch.empty_like(fused)
         if ctx.L.width > ctx.L.used:
             d_fused[..., ctx.L.used:] = 0
-        a = _agg_args(fused, mask3, out, ctx.L, d_out, d_fused, dropout=ctx.dropout)
-        _call_skip('tgt_triplet_aggregate_bwd', a, ctx.graph_scale)
+        ctx.skip.launch_aggregate(_agg_args(fused, mask3, out, ctx.L, d_out, d_fused, dropout=ctx.dropout), bwd=True)
         return d_fused, None, None, None, None
 
 
@@ -932,34 +930,26 @@ def projected_triplet_aggregate(x, params, mask3, layout, table, dropout=(0.0, 0
     graph_scale: see triplet_aggregate; both paths skip the dropped graphs in the aggregate kernel (the projections that run as
     library GEMMs still cover every graph)."""
     L = layout
-    cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
-    # (whether a backward can follow is decided as in projected_triplet_attention)
-    no_backward = not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, *params)))
+    cd = _compute_dtype(x)
     N = x.shape[1]
-    if not (no_backward and _AGG_PROJ_INFER and _agg_proj_ok(x, N, L, cd)):
+    if not (_no_backward(x, *params) and _AGG_PROJ_INFER and _agg_proj_ok(x, N, L, cd)):
         return triplet_aggregate(fused_linear(x, table, params), mask3, L, dropout, graph_scale)
     with torch.no_grad():
         _dev(x, mask3)
         B = x.shape[0]
-        _check_agg_graph_scale(graph_scale, B)
+        _check_per_graph(graph_scale, B, torch.float32, 'triplet aggregate: graph_scale')
         w, b = _fuse_params(table, params, cd)
         x2 = x.reshape(-1, L.C)
         x2 = (x2 if x2.dtype == cd else x2.to(cd)).contiguous()
-        we, be = w[2 * L.C:L.used], b[2 * L.C:L.used]
         out = torch.empty(B, N, N, 2 * L.C, dtype=cd, device=x.device)
         egv, _ = _agg_proj_eg_view(out, L)                   # (the E/G rows wait inside `out` for the kernel: no tensor of their own)
-        if we.shape[0] <= 128 and _edge_kernel_ok(x2, we.shape[0], cd):
-            edge_linear_raw(x2, we, be.contiguous(), out=egv)
-        else:
-            torch.addmm(be, x2, we.t(), out=egv)
+        _narrow_linear(x2, w[2 * L.C:L.used], b[2 * L.C:L.used], cd, out=egv)
         a = _agg_proj_args(out, mask3, out, L, dropout)
-        s0, s1 = _prof_begin('tgt_triplet_aggregate_proj_fwd')
         if graph_scale is None:
-            rc = _lib.lib().tgt_triplet_aggregate_proj_fwd(C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), _stream())
+            _launch('tgt_triplet_aggregate_proj_fwd', C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), prof='tgt_triplet_aggregate_proj_fwd')
         else:
-            rc = _lib.lib().tgt_triplet_aggregate_proj_fwd_skip(C.byref(a), _ptr(graph_scale), _ptr(x2), L.C, _ptr(w), _ptr(b), _stream())
-        _lib.check(rc, 'tgt_triplet_aggregate_proj_fwd')
-        _prof_end('tgt_triplet_aggregate_proj_fwd', s0, s1)
+            _launch('tgt_triplet_aggregate_proj_fwd_skip', C.byref(a), _ptr(graph_scale), _ptr(x2), L.C, _ptr(w), _ptr(b),
+                    prof='tgt_triplet_aggregate_proj_fwd')
     return out
 
 
@@ -973,8 +963,7 @@ class _TriangularUpdate(torch.autograd.Function):
         e4, v4 = e4.contiguous(), v4.contiguous()
         B, N = e4.shape[0], e4.shape[1]
         out = torch.empty(B, N, N, 2 * H, dtype=e4.dtype, device=e4.device)
-        _lib.check(_lib.lib().tgt_triangular_update_fwd(_ptr(e4), _ptr(v4), _ptr(mask3), _ptr(out), B, N, H,
-                                                        _DT[e4.dtype], _stream()), 'tgt_triangular_update_fwd')
+        _launch('tgt_triangular_update_fwd', _ptr(e4), _ptr(v4), _ptr(mask3), _ptr(out), B, N, H, _DT[e4.dtype])
         ctx.save_for_backward(e4, v4, mask3)
         ctx.H = H
         return out
@@ -985,9 +974,8 @@ class _TriangularUpdate(torch.autograd.Function):
         d_out = d_out.contiguous()
         B, N = e4.shape[0], e4.shape[1]
         d_e4, d_v4 = torch.empty_like(e4), torch.empty_like(v4)
-        _lib.check(_lib.lib().tgt_triangular_update_bwd(_ptr(e4), _ptr(v4), _ptr(mask3), _ptr(d_out), _ptr(d_e4),
-                                                        _ptr(d_v4), B, N, ctx.H, _DT[e4.dtype], _stream()),
-                   'tgt_triangular_update_bwd')
+        _launch('tgt_triangular_update_bwd', _ptr(e4), _ptr(v4), _ptr(mask3), _ptr(d_out), _ptr(d_e4), _ptr(d_v4), B, N, ctx.H,
+                _DT[e4.dtype])
         return d_e4, d_v4, None, None
 
 
@@ -1047,7 +1035,7 @@ class _NodeAttention(torch.autograd.Function):
         gsum = torch.empty(B, N, H, dtype=torch.float32, device=qkv.device)
         a.vatt, a.hhat, a.lse, a.gsum = vatt.data_ptr(), _ptr(hhat), lse.data_ptr(), gsum.data_ptr()
         a.hhat_scale = _ptr(hhat_scale)
-        _call('tgt_node_attention_fwd', _lib.lib().tgt_node_attention_fwd, a)
+        _launch('tgt_node_attention_fwd', C.byref(a), prof='tgt_node_attention_fwd')
         ctx.save_for_backward(qkv, eg, mask3, lse, gsum, vatt, hhat_scale)
         ctx.cfg = (H, scale_degree, want_edges)
         if want_edges:
@@ -1066,7 +1054,7 @@ class _NodeAttention(torch.autograd.Function):
         a.lse, a.gsum, a.vatt = lse.data_ptr(), gsum.data_ptr(), vatt.data_ptr()
         a.d_vatt, a.d_hhat, a.d_qkv, a.d_eg = d_vatt.data_ptr(), _ptr(d_hhat), d_qkv.data_ptr(), d_eg.data_ptr()
         a.hhat_scale = _ptr(hhat_scale)
-        _call('tgt_node_attention_bwd', _lib.lib().tgt_node_attention_bwd, a)
+        _launch('tgt_node_attention_bwd', C.byref(a), prof='tgt_node_attention_bwd')
         return d_qkv, d_eg, None, None, None, None, None
 
 
@@ -1090,7 +1078,7 @@ class _EdgeLogits(torch.autograd.Function):
         a, W = _node_args(qk, e_bias, None, H, False, True)
         hhat = torch.empty(B, N, N, H, dtype=qk.dtype, device=qk.device)
         a.hhat = hhat.data_ptr()
-        _call('tgt_node_attention_fwd(logits)', _lib.lib().tgt_node_attention_fwd, a)
+        _launch('tgt_node_attention_fwd', C.byref(a), prof='tgt_node_attention_fwd(logits)')
         ctx.save_for_backward(qk, e_bias)
         ctx.H = H
         return hhat
@@ -1102,7 +1090,7 @@ class _EdgeLogits(torch.autograd.Function):
         d_hhat = d_hhat.contiguous()
         d_qk, d_e = torch.empty_like(qk), torch.empty_like(e_bias)
         a.d_hhat, a.d_qkv, a.d_eg = d_hhat.data_ptr(), d_qk.data_ptr(), d_e.data_ptr()
-        _call('tgt_node_attention_bwd(logits)', _lib.lib().tgt_node_attention_bwd, a)
+        _launch('tgt_node_attention_bwd', C.byref(a), prof='tgt_node_attention_bwd(logits)')
         return d_qk, d_e, None
 
 
@@ -1127,10 +1115,9 @@ def adam_step_(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), e
         assert shadow.is_cuda and shadow.numel() == param.numel() and shadow.dtype in (torch.bfloat16, torch.float16)
     if ctl is not None:
         assert ctl.dtype == torch.float32 and ctl.is_contiguous() and ctl.numel() >= CTL_SIZE
-    _lib.check(_lib.lib().tgt_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
-                                        param.numel(), lr, betas[0], betas[1], eps, weight_decay,
-                                        int(step), grad_scale, float(clip_value or 0.0), _ptr(ctl), _ptr(shadow),
-                                        0 if shadow is None else _DT[shadow.dtype], _stream()), 'tgt_adam_step')
+    _launch('tgt_adam_step', _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), lr, betas[0], betas[1], eps,
+            weight_decay, int(step), grad_scale, float(clip_value or 0.0), _ptr(ctl), _ptr(shadow),
+            0 if shadow is None else _DT[shadow.dtype])
 
 
 # layout of the optimizer control block (include/tgt_hip.h TGT_CTL_*)
@@ -1145,11 +1132,9 @@ def grad_scaler_step_(grad, ctl, world=1, clip_value=0.0, clip_norm=0.0, dynamic
     device in `ctl` for adam_step_ (reference training.py:451-469 does this with a host sync)."""
     _dev(grad, ctl)
     assert grad.dtype == torch.float32 and grad.is_contiguous() and ctl.dtype == torch.float32 and ctl.numel() >= CTL_SIZE
-    L = _lib.lib()
-    partial = torch.empty(L.tgt_grad_stats_parts(), dtype=torch.float32, device=grad.device)
-    _lib.check(L.tgt_grad_scaler_step(_ptr(grad), grad.numel(), _ptr(ctl), _ptr(partial), int(world), float(clip_value or 0.0),
-                                      float(clip_norm or 0.0), int(bool(dynamic)), float(growth_factor), float(backoff_factor),
-                                      int(growth_interval), _stream()), 'tgt_grad_scaler_step')
+    partial = torch.empty(_lib.lib().tgt_grad_stats_parts(), dtype=torch.float32, device=grad.device)
+    _launch('tgt_grad_scaler_step', _ptr(grad), grad.numel(), _ptr(ctl), _ptr(partial), int(world), float(clip_value or 0.0),
+            float(clip_norm or 0.0), int(bool(dynamic)), float(growth_factor), float(backoff_factor), int(growth_interval))
 
 
 def loss_accumulate_(loss, samples, ctl, mixed, mode=3):
@@ -1159,8 +1144,8 @@ def loss_accumulate_(loss, samples, ctl, mixed, mode=3):
     _dev(ctl, loss)
     if loss is not None:
         assert loss.numel() == 1 and loss.dtype in (torch.float32, torch.float64)
-    _lib.check(_lib.lib().tgt_loss_accumulate(_ptr(loss), int(loss is not None and loss.dtype == torch.float64), float(samples),
-                                              _ptr(ctl), int(bool(mixed)), int(mode), _stream()), 'tgt_loss_accumulate')
+    _launch('tgt_loss_accumulate', _ptr(loss), int(loss is not None and loss.dtype == torch.float64), float(samples), _ptr(ctl),
+            int(bool(mixed)), int(mode))
 
 
 # ---------------------------------------------------------------------------
@@ -1178,11 +1163,8 @@ class _LayerNorm(torch.autograd.Function):
         y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        L = _lib.lib()
-        s, e = _prof_begin()
-        _lib.check(L.tgt_layer_norm_fwd(_ptr(x), _DT[x.dtype], _ptr(w), _ptr(b), _ptr(y), _DT[out_dtype],
-                                        _ptr(mean), _ptr(rstd), rows, C_, float(eps), _stream()), 'tgt_layer_norm_fwd')
-        _prof_end('tgt_layer_norm_fwd', s, e)
+        _launch('tgt_layer_norm_fwd', _ptr(x), _DT[x.dtype], _ptr(w), _ptr(b), _ptr(y), _DT[out_dtype], _ptr(mean), _ptr(rstd), rows, C_,
+                float(eps), prof='tgt_layer_norm_fwd')
         ctx.save_for_backward(x, w, mean, rstd)
         ctx.wdtype = weight.dtype
         return y
@@ -1193,39 +1175,19 @@ class _LayerNorm(torch.autograd.Function):
         dy = dy.contiguous()
         C_ = x.shape[-1]
         rows = x.numel() // C_
-        L = _lib.lib()
         dx = torch.empty_like(x)
         # separate tensors (not two views of one): autograd can then adopt them as .grad without a copy
         dgb = (torch.empty(C_, dtype=torch.float32, device=x.device), torch.empty(C_, dtype=torch.float32, device=x.device))
-        partial = torch.empty(L.tgt_layer_norm_parts() * 2 * C_, dtype=torch.float32, device=x.device)
-        s, e = _prof_begin()
-        _lib.check(L.tgt_layer_norm_bwd(_ptr(dy), _DT[dy.dtype], _ptr(x), _DT[x.dtype], _ptr(w), _ptr(mean), _ptr(rstd),
-                                        _ptr(dx), _DT[dx.dtype], _ptr(dgb[0]), _ptr(dgb[1]), _ptr(partial),
-                                        rows, C_, _stream()), 'tgt_layer_norm_bwd')
-        _prof_end('tgt_layer_norm_bwd', s, e)
+        partial = torch.empty(_lib.lib().tgt_layer_norm_parts() * 2 * C_, dtype=torch.float32, device=x.device)
+        _launch('tgt_layer_norm_bwd', _ptr(dy), _DT[dy.dtype], _ptr(x), _DT[x.dtype], _ptr(w), _ptr(mean), _ptr(rstd), _ptr(dx),
+                _DT[dx.dtype], _ptr(dgb[0]), _ptr(dgb[1]), _ptr(partial), rows, C_, prof='tgt_layer_norm_bwd')
         return dx, dgb[0].to(ctx.wdtype), dgb[1].to(ctx.wdtype), None, None
-
-
-def _prof_begin(name=None):
-    if _PROFILE is None or not _timed(name):
-        return None, None
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    return s, e
-
-
-def _prof_end(name, s, e):
-    if s is not None:
-        e.record()
-        _PROFILE.setdefault(name, []).append((s, e))
 
 
 def layer_norm(x, weight, bias, eps=1e-5, out_dtype=None):
     """LayerNorm over the last axis.  out_dtype defaults to the autocast dtype when
     autocast is on (what the consuming GEMM would cast to anyway), else x.dtype."""
-    if out_dtype is None:
-        out_dtype = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else x.dtype
-    return _LayerNorm.apply(x, weight, bias, eps, out_dtype)
+    return _LayerNorm.apply(x, weight, bias, eps, _compute_dtype(x, on_cpu=True) if out_dtype is None else out_dtype)
 
 
 # ---------------------------------------------------------------------------
@@ -1340,10 +1302,8 @@ class _GeluDropout(torch.autograd.Function):
         x = x.contiguous()
         y = torch.empty_like(x)
         eps_ = x.numel() // x.shape[0] if sample_scale is not None else 0
-        s, e = _prof_begin()
-        _lib.check(_lib.lib().tgt_gelu_dropout_scaled_fwd(_ptr(x), _ptr(y), x.numel(), _DT[x.dtype], float(p), seed,
-                                                          _ptr(sample_scale), eps_, _stream()), 'tgt_gelu_dropout_fwd')
-        _prof_end('tgt_gelu_dropout_fwd', s, e)
+        _launch('tgt_gelu_dropout_scaled_fwd', _ptr(x), _ptr(y), x.numel(), _DT[x.dtype], float(p), seed, _ptr(sample_scale), eps_,
+                prof='tgt_gelu_dropout_fwd')
         ctx.save_for_backward(x, sample_scale)
         ctx.p, ctx.seed, ctx.eps_ = float(p), seed, eps_
         return y
@@ -1353,10 +1313,8 @@ class _GeluDropout(torch.autograd.Function):
         x, sample_scale = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(x)
-        s, e = _prof_begin()
-        _lib.check(_lib.lib().tgt_gelu_dropout_scaled_bwd(_ptr(x), _ptr(dy), _ptr(dx), x.numel(), _DT[x.dtype], ctx.p, ctx.seed,
-                                                          _ptr(sample_scale), ctx.eps_, _stream()), 'tgt_gelu_dropout_bwd')
-        _prof_end('tgt_gelu_dropout_bwd', s, e)
+        _launch('tgt_gelu_dropout_scaled_bwd', _ptr(x), _ptr(dy), _ptr(dx), x.numel(), _DT[x.dtype], ctx.p, ctx.seed, _ptr(sample_scale),
+                ctx.eps_, prof='tgt_gelu_dropout_bwd')
         return dx, None, None, None
 
 
@@ -1390,10 +1348,8 @@ def _glu_backward(pre, d_act, kind, p, seed, sample_scale, eps_):
     if d_act.dtype != pre.dtype:
         d_act = d_act.to(pre.dtype)
     d_pre = torch.empty_like(pre)
-    s, e = _prof_begin('tgt_glu_dropout_bwd')
-    _lib.check(_lib.lib().tgt_glu_dropout_bwd(_ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel() // (2 * cols), cols, kind, _DT[pre.dtype],
-                                              p, seed, _ptr(sample_scale), eps_, _stream()), 'tgt_glu_dropout_bwd')
-    _prof_end('tgt_glu_dropout_bwd', s, e)
+    _launch('tgt_glu_dropout_bwd', _ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel() // (2 * cols), cols, kind, _DT[pre.dtype], p, seed,
+            _ptr(sample_scale), eps_, prof='tgt_glu_dropout_bwd')
     return d_pre
 
 
@@ -1405,10 +1361,8 @@ class _GluDropout(torch.autograd.Function):
         cols = x.shape[-1] // 2
         y = torch.empty(*x.shape[:-1], cols, dtype=x.dtype, device=x.device)
         eps_ = y.numel() // sample_scale.numel() if sample_scale is not None else 0
-        s, e = _prof_begin('tgt_glu_dropout_fwd')
-        _lib.check(_lib.lib().tgt_glu_dropout_fwd(_ptr(x), _ptr(y), y.numel() // cols, cols, kind, _DT[x.dtype], float(p), seed,
-                                                  _ptr(sample_scale), eps_, _stream()), 'tgt_glu_dropout_fwd')
-        _prof_end('tgt_glu_dropout_fwd', s, e)
+        _launch('tgt_glu_dropout_fwd', _ptr(x), _ptr(y), y.numel() // cols, cols, kind, _DT[x.dtype], float(p), seed, _ptr(sample_scale),
+                eps_, prof='tgt_glu_dropout_fwd')
         ctx.save_for_backward(x, sample_scale)
         ctx.meta = (kind, float(p), seed, eps_)
         return y
@@ -1528,12 +1482,9 @@ def column_sum(x2):
     rows, C_ = x2.shape
     if not (x2.is_cuda and x2.is_contiguous() and C_ % 8 == 0 and C_ <= 4096 and x2.dtype in _DT and rows >= 1024):
         return x2.sum(0, dtype=torch.float32)
-    L = _lib.lib()
     out = torch.empty(C_, dtype=torch.float32, device=x2.device)
-    partial = torch.empty(L.tgt_layer_norm_parts() * C_, dtype=torch.float32, device=x2.device)
-    s, e = _prof_begin()
-    _lib.check(L.tgt_colsum(_ptr(x2), _DT[x2.dtype], rows, C_, _ptr(out), _ptr(partial), _stream()), 'tgt_colsum')
-    _prof_end('tgt_colsum', s, e)
+    partial = torch.empty(_lib.lib().tgt_layer_norm_parts() * C_, dtype=torch.float32, device=x2.device)
+    _launch('tgt_colsum', _ptr(x2), _DT[x2.dtype], rows, C_, _ptr(out), _ptr(partial), prof='tgt_colsum')
     return out
 
 
@@ -1678,13 +1629,9 @@ def _ln_backward(dy, s, g, mean, rstd, ds, scale, rps, want_dz, live=None):
     dg = torch.empty(N, dtype=torch.float32, device=s.device)
     db_cs = torch.empty(2 * N, dtype=torch.float32, device=s.device)
     partial = torch.empty(L.tgt_layer_norm_parts() * 3 * N, dtype=torch.float32, device=s.device)
-    p0, p1 = _prof_begin()
-    _lib.check(L.tgt_add_layer_norm_bwd(_ptr(dy), _DT[dy.dtype], _ptr(s), _DT[s.dtype], _ptr(ds),
-                                        0 if ds is None else _DT[ds.dtype], _ptr(scale), rps, _ptr(g), _ptr(mean),
-                                        _ptr(rstd), _ptr(d_res), _ptr(d_z), _DT[s.dtype], _ptr(dg), _ptr(db_cs),
-                                        db_cs.data_ptr() + 4 * N, _ptr(partial), rows, N, _stream()),
-               'tgt_add_layer_norm_bwd')
-    _prof_end('tgt_add_layer_norm_bwd', p0, p1)
+    _launch('tgt_add_layer_norm_bwd', _ptr(dy), _DT[dy.dtype], _ptr(s), _DT[s.dtype], _ptr(ds), 0 if ds is None else _DT[ds.dtype],
+            _ptr(scale), rps, _ptr(g), _ptr(mean), _ptr(rstd), _ptr(d_res), _ptr(d_z), _DT[s.dtype], _ptr(dg), _ptr(db_cs),
+            db_cs.data_ptr() + 4 * N, _ptr(partial), rows, N, prof='tgt_add_layer_norm_bwd')
     return d_res, d_z, dg, db_cs[:N], db_cs[N:]
 
 
@@ -1911,7 +1858,7 @@ class WeightTransposes:
             for ptr, (t, shape) in self.entries.items():
                 rows += [ptr, t.data_ptr(), shape[0] | (shape[1] << 32)]        # {src, dst, int32 rows, int32 cols}
             self.table = torch.tensor(rows, dtype=torch.int64).to(self.shadow.device)
-        _lib.check(_lib.lib().tgt_transpose_many(_ptr(self.table), len(self.entries), 16, _stream()), 'tgt_transpose_many')
+        _launch('tgt_transpose_many', _ptr(self.table), len(self.entries), 16)
 
 
 _WT_CACHE = K.wt_cache          # A/B knob
@@ -1938,6 +1885,19 @@ def _edge_kernel_ok(x2, N, cd, ks=(64, 128, 256)):
             N % 8 == 0 and x2.shape[0] >= _EDGE_MIN_ROWS and x2.stride(-1) == 1 and (x2.stride(0) * 2) % 16 == 0)
 
 
+def _addmm_tn(x2, w, b, out=None):
+    return torch.addmm(b, x2, w.t(), out=out)
+
+
+def _narrow_linear(x2, w, b, cd, out=None, gemm=_addmm_tn):
+    """x2 w^T + b (into `out`, which may be a strided view) where w has at most 128 rows -- lin_EG (128), or a row slice of a fused
+    projection: the third-arm E/G (64) -- on the weight-resident slice kernel: 41 vs 47 us and 29 vs 37 us against the tuned
+    library GEMM.  Any other weight, a non-contiguous one, or rows the edge kernels do not take: gemm(x2, w, b, out=out)."""
+    if w.shape[0] <= 128 and w.is_contiguous() and _edge_kernel_ok(x2, w.shape[0], cd):
+        return edge_linear_raw(x2, w, None if b is None else b.contiguous(), out=out)
+    return gemm(x2, w, b, out=out)
+
+
 def _linear_forward(x, weight, bias, cd):
     """(x2, w, y): the operands saved for the backward and y = x W^T + b in dtype cd"""
     xs = x.shape
@@ -1948,12 +1908,7 @@ def _linear_forward(x, weight, bias, cd):
     b = None if bias is None else _as_dtype(bias, cd)
     # the result must own its storage (not be a view): the layer adds the residual in place
     y = torch.empty(*xs[:-1], weight.shape[0], dtype=cd, device=x.device)
-    y2 = y.view(-1, weight.shape[0])
-    if weight.shape[0] <= 128 and w.is_contiguous() and _edge_kernel_ok(x2, weight.shape[0], cd):
-        # narrow outputs (lin_EG: 128, third-arm E/G: 64): 41 vs 47 us and 29 vs 37 us against the tuned library GEMM
-        edge_linear_raw(x2, w, b, out=y2)
-        return x2, w, y
-    _gemm.linear_tn(x2, w, b, out=y2)                      # (torch.mm / torch.addmm(out=) from a cached plan)
+    _narrow_linear(x2, w, b, cd, out=y.view(-1, weight.shape[0]), gemm=_gemm.linear_tn)    # (torch.mm / torch.addmm(out=) from a cached plan)
     return x2, w, y
 
 
@@ -2040,7 +1995,7 @@ def _permute_cols(src, idx, dtype, after_sums=False):
     args = (_ptr(src), _DT[src.dtype], _ptr(idx), _ptr(out), _DT[dtype], src.shape[0], src.shape[1])
 
     def run():
-        _lib.check(_lib.lib().tgt_permute_cols(*args, _stream()), 'tgt_permute_cols')
+        _launch('tgt_permute_cols', *args)
         keep.clear()
     if after_sums:
         _after_sums(run)
@@ -2079,8 +2034,7 @@ class _LinearPermutedCols(torch.autograd.Function):
 
 def linear_permuted_cols(x, weight, bias, idx, inv):
     """linear(x, weight[:, idx], bias); idx / inv: int32 device tensors (a permutation and its inverse)"""
-    cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
-    return _LinearPermutedCols.apply(x, weight, bias, cd, idx, inv)
+    return _LinearPermutedCols.apply(x, weight, bias, _compute_dtype(x), idx, inv)
 
 
 class _FusedLinear(torch.autograd.Function):
@@ -2111,14 +2065,13 @@ class _FusedLinear(torch.autograd.Function):
 
 def fused_linear(x, table, params):
     """linear(x, W, b) with (W, b) assembled from `params` = (w0, b0, w1, b1, ...) by `table`"""
-    cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
-    return _FusedLinear.apply(x, cd, table, *params)
+    return _FusedLinear.apply(x, _compute_dtype(x), table, *params)
 
 
 def linear(x, weight, bias=None):
     """F.linear replacement for the TGT modules (autocast-aware: computes in the autocast
     dtype when autocast is on, else in x.dtype)."""
-    cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
+    cd = _compute_dtype(x)
     return _Linear.apply(x, weight, bias, cd, _lazy_ok(x, weight, cd))
 
 
@@ -2191,10 +2144,9 @@ def edge_linear_raw(a, w, bias=None, epilogue=_lib.EPI_BIAS, *, ln=None, y=None,
         g.dw_partial = dw_partial.data_ptr()
         g.colsum_rows = dw_partial.shape[0]
     if live is not None and M == live.rows and live.tiles.device == a.device and _live_supported(g):
-        tiles = live.tiles
-        _call('tgt_edge_linear', lambda args, st: _lib.lib().tgt_edge_linear_live(args, _ptr(tiles), st), g)
+        _launch('tgt_edge_linear_live', C.byref(g), _ptr(live.tiles), prof='tgt_edge_linear')
     else:
-        _call('tgt_edge_linear', _lib.lib().tgt_edge_linear, g)
+        _launch('tgt_edge_linear', C.byref(g), prof='tgt_edge_linear')
     return out
 
 
@@ -2270,22 +2222,18 @@ class _LinearGeluDropout(torch.autograd.Function):
         if d_act is not None:
             d_act = d_act.contiguous()
             d_pre = torch.empty_like(pre)
-            L = _lib.lib()
             N = pre.shape[-1]
             vec = 16 // pre.element_size()
-            s, e = _prof_begin()
             if _GELU_BWD_COLSUM and need_db and d_pre_in is None and N % vec == 0 and (256 * vec) % N == 0:
                 # the bias gradient of lin_W1 (column sums of d_pre) rides on the activation's backward pass: no separate
                 # reduction pass over the 134 MB gradient
                 cs = torch.empty(N, dtype=torch.float32, device=pre.device)
-                partial = torch.empty(L.tgt_gelu_colsum_parts() * N, dtype=torch.float32, device=pre.device)
-                _lib.check(L.tgt_gelu_dropout_bwd_colsum(_ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel(), _DT[pre.dtype], p, seed,
-                                                         _ptr(sample_scale), eps_, N, _ptr(partial), _ptr(cs), _stream()),
-                           'tgt_gelu_dropout_bwd_colsum')
+                partial = torch.empty(_lib.lib().tgt_gelu_colsum_parts() * N, dtype=torch.float32, device=pre.device)
+                _launch('tgt_gelu_dropout_bwd_colsum', _ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel(), _DT[pre.dtype], p, seed,
+                        _ptr(sample_scale), eps_, N, _ptr(partial), _ptr(cs), prof='tgt_gelu_dropout_bwd')
             else:
-                _lib.check(L.tgt_gelu_dropout_scaled_bwd(_ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel(), _DT[pre.dtype], p, seed,
-                                                         _ptr(sample_scale), eps_, _stream()), 'tgt_gelu_dropout_bwd')
-            _prof_end('tgt_gelu_dropout_bwd', s, e)
+                _launch('tgt_gelu_dropout_scaled_bwd', _ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel(), _DT[pre.dtype], p, seed,
+                        _ptr(sample_scale), eps_, prof='tgt_gelu_dropout_bwd')
         if d_pre_in is not None:
             if d_pre is None and need_db:
                 cs = _take_colsum(d_pre_in, d_pre_in.shape[-1])        # (the GELU_BWD epilogue that wrote it summed its columns)
@@ -2303,7 +2251,7 @@ def linear_gelu_dropout_ok(x, weight, sample_scale=None):
     """whether linear_gelu_dropout takes this call: edge rows (many of them), 16-bit compute dtype, 256 outputs, K in {64,128,256}"""
     if not (_FFN_GELU_EPI and x.is_cuda):
         return False
-    cd = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else x.dtype
+    cd = _compute_dtype(x, on_cpu=True)
     rows = x.numel() // x.shape[-1]
     if sample_scale is not None and (rows % sample_scale.numel() or sample_scale.dtype != torch.float32):
         return False
@@ -2313,7 +2261,7 @@ def linear_gelu_dropout_ok(x, weight, sample_scale=None):
 
 def linear_gelu_dropout(x, weight, bias, p, training, sample_scale=None):
     """dropout(gelu(linear(x, weight, bias)), p) [* sample_scale per graph] in one launch; see linear_gelu_dropout_ok"""
-    cd = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else x.dtype
+    cd = _compute_dtype(x, on_cpu=True)
     p = float(p) if training else 0.0
     seed = _host_seed() if p > 0 else 0
     act, pre = _LinearGeluDropout.apply(x, weight, bias, cd, p, seed, sample_scale, _lazy_ok(x, weight, cd))
@@ -2363,7 +2311,7 @@ def linear_glu_dropout_ok(x, weight, sample_scale=None):
     """whether linear_glu_dropout takes this call: edge rows (many of them), a 16-bit compute dtype, a (512, 256) weight"""
     if not x.is_cuda:
         return False
-    cd = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else x.dtype
+    cd = _compute_dtype(x, on_cpu=True)
     rows = x.numel() // x.shape[-1]
     if sample_scale is not None and (rows % sample_scale.numel() or sample_scale.dtype != torch.float32):
         return False
@@ -2375,7 +2323,7 @@ def linear_glu_dropout(x, weight, bias, kind, p, training, sample_scale=None):
     """dropout(e * act(g), p) [* sample_scale per graph] with [g | e] = linear(x, weight, bias) in one launch; kind as in
     glu_dropout; see linear_glu_dropout_ok"""
     kind = _glu_kind(kind)
-    cd = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else x.dtype
+    cd = _compute_dtype(x, on_cpu=True)
     p = float(p) if training else 0.0
     seed = _host_seed() if p > 0 else 0
     return _LinearGluDropout.apply(x, weight, bias, cd, kind, p, seed, sample_scale)
@@ -2397,12 +2345,8 @@ class _AddLayerNorm(torch.autograd.Function):
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         rps = rows // x.shape[0]
-        L = _lib.lib()
-        p0, p1 = _prof_begin()
-        _lib.check(L.tgt_add_layer_norm_fwd(_ptr(x), _DT[x.dtype], _ptr(res), _DT[res.dtype], _ptr(scale), rps, _ptr(s),
-                                            _ptr(w), _ptr(b), _ptr(y), _DT[out_dtype], _ptr(mean), _ptr(rstd),
-                                            rows, C_, float(eps), _stream()), 'tgt_add_layer_norm_fwd')
-        _prof_end('tgt_add_layer_norm_fwd', p0, p1)
+        _launch('tgt_add_layer_norm_fwd', _ptr(x), _DT[x.dtype], _ptr(res), _DT[res.dtype], _ptr(scale), rps, _ptr(s), _ptr(w), _ptr(b),
+                _ptr(y), _DT[out_dtype], _ptr(mean), _ptr(rstd), rows, C_, float(eps), prof='tgt_add_layer_norm_fwd')
         ctx.save_for_backward(s, w, mean, rstd, scale)
         ctx.meta = (weight.dtype, res.dtype, rps)
         ctx.live = _edge_live             # (the backward may run a Linear's data gradient fused with its own: a row kernel, _ln_backward)
@@ -2414,7 +2358,6 @@ class _AddLayerNorm(torch.autograd.Function):
         wdt, rdt, rps = ctx.meta
         C_ = s.shape[-1]
         rows = s.numel() // C_
-        L = _lib.lib()
         if dy is None:                                  # the LN branch was not used
             d_res = ds
             d_x = ds if scale is None else ds * scale.view(-1, *([1] * (ds.ndim - 1))).to(ds.dtype)
@@ -2482,7 +2425,6 @@ class _LinearResidualLN(torch.autograd.Function):
         xs, xdt, wdt, bdt, lndt, rdt, rps = ctx.meta
         N = s.shape[-1]
         rows = s.numel() // N
-        L = _lib.lib()
         pres = ctx.prescaled       # x arrived pre-scaled: the gradient of x W^T IS the stream gradient, only the bias carries the factor
         if dy is None:                                  # the LayerNorm branch was not used
             d_res = ds
@@ -2573,7 +2515,7 @@ def linear_residual_layer_norm(x, weight, bias, res, scale, ln_weight, ln_bias, 
     prescaled: x already carries the factor (its producer folded it in: gelu_dropout(sample_scale=), node_attention(
     hhat_scale=)), so s = res + x W^T + scale[graph] * bias -- the same value, and the backward hands the stream gradient
     itself to the Linear's gradient GEMMs instead of writing a scaled copy of it (one pass over the rows less)."""
-    cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else x.dtype
+    cd = _compute_dtype(x)
     # x = the FFN's activation out of linear_gelu_dropout: take over its backward when the data gradient runs on the row-phase kernel
     gelu = getattr(x, '_tgt_gelu', None) if _FFN_GELU_BWD_EPI else None
     if gelu is not None and not (weight.shape[0] == 256 and weight.shape[1] == 256 and gelu[0].dtype == cd and
@@ -2725,7 +2667,7 @@ def drop_path_scale(x, drop_prob, training):
 def add_layer_norm(x, res, scale, weight, bias, eps=1e-5, out_dtype=None):
     """(s, y) with s = res + x*scale (per-sample scale or None), y = LayerNorm(s)."""
     if out_dtype is None:
-        out_dtype = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else x.dtype
+        out_dtype = _compute_dtype(x, on_cpu=True)
     return _offer_lazy(*_AddLayerNorm.apply(x, res, scale, weight, bias, eps, out_dtype))
 
 
@@ -2742,8 +2684,7 @@ class _CrossEntropyRows(torch.autograd.Function):
         rows, C_ = logits.shape
         lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
         xent = torch.empty(rows, dtype=torch.float32, device=logits.device)
-        _lib.check(_lib.lib().tgt_cross_entropy_fwd(_ptr(logits), _DT[logits.dtype], _ptr(target), rows, C_, _ptr(lse), _ptr(xent),
-                                                    _stream()), 'tgt_cross_entropy_fwd')
+        _launch('tgt_cross_entropy_fwd', _ptr(logits), _DT[logits.dtype], _ptr(target), rows, C_, _ptr(lse), _ptr(xent))
         ctx.save_for_backward(logits, target, lse)
         return xent
 
@@ -2752,8 +2693,8 @@ class _CrossEntropyRows(torch.autograd.Function):
         logits, target, lse = ctx.saved_tensors
         g = g.contiguous().float()
         d = torch.empty_like(logits)
-        _lib.check(_lib.lib().tgt_cross_entropy_bwd(_ptr(logits), _DT[logits.dtype], _ptr(target), _ptr(lse), _ptr(g), logits.shape[0],
-                                                    logits.shape[1], _ptr(d), _stream()), 'tgt_cross_entropy_bwd')
+        _launch('tgt_cross_entropy_bwd', _ptr(logits), _DT[logits.dtype], _ptr(target), _ptr(lse), _ptr(g), logits.shape[0],
+                logits.shape[1], _ptr(d))
         return d, None
 
 
@@ -2774,8 +2715,7 @@ class _GaussianBasis(torch.autograd.Function):
         xf, mf, bf = (t.detach().reshape(-1).float().contiguous() for t in (x, mul, bias))
         mw, sw = means.detach().reshape(-1).float().contiguous(), stds.detach().reshape(-1).float().contiguous()
         y = torch.empty(*x.shape, K, dtype=out_dtype, device=x.device)
-        _lib.check(_lib.lib().tgt_gaussian_basis_fwd(_ptr(xf), _ptr(mf), _ptr(bf), _ptr(mw), _ptr(sw), xf.numel(), K, _DT[out_dtype],
-                                                     _ptr(y), _stream()), 'tgt_gaussian_basis_fwd')
+        _launch('tgt_gaussian_basis_fwd', _ptr(xf), _ptr(mf), _ptr(bf), _ptr(mw), _ptr(sw), xf.numel(), K, _DT[out_dtype], _ptr(y))
         ctx.save_for_backward(xf, mf, bf, mw, sw)
         ctx.meta = (x.shape, mul.shape, bias.shape, means.shape, stds.shape, means.dtype, out_dtype)
         return y
@@ -2788,11 +2728,10 @@ class _GaussianBasis(torch.autograd.Function):
         g = g.contiguous()
         if g.dtype != out_dtype:
             g = g.to(out_dtype)
-        L = _lib.lib()
         dt = torch.empty(pairs, dtype=torch.float32, device=g.device)
-        partial = torch.empty(L.tgt_gaussian_basis_parts(pairs), 2 * K, dtype=torch.float32, device=g.device)
-        _lib.check(L.tgt_gaussian_basis_bwd(_ptr(xf), _ptr(mf), _ptr(bf), _ptr(mw), _ptr(sw), pairs, K, _DT[out_dtype], _ptr(g), _ptr(dt),
-                                            _ptr(partial), _stream()), 'tgt_gaussian_basis_bwd')
+        partial = torch.empty(_lib.lib().tgt_gaussian_basis_parts(pairs), 2 * K, dtype=torch.float32, device=g.device)
+        _launch('tgt_gaussian_basis_bwd', _ptr(xf), _ptr(mf), _ptr(bf), _ptr(mw), _ptr(sw), pairs, K, _DT[out_dtype], _ptr(g), _ptr(dt),
+                _ptr(partial))
         dms = sum_rows(partial, defer=False)          # (sliced and cast right below)
         dx = (dt * mf).view(xs) if ctx.needs_input_grad[0] else None
         return dx, (dt * xf).view(ms), dt.view(bs), dms[:K].view(mws).to(pdt), dms[K:].view(sws).to(pdt), None
@@ -2802,5 +2741,4 @@ def gaussian_basis(x, mul, bias, means, stds):
     """y[..., k] = exp(-((mul*x + bias - means[k]) / (|stds[k]| + 0.01))^2 / 2) / ((2*3.14159)^0.5 (|stds[k]| + 0.01)); x, mul, bias
     broadcast-free tensors of one shape (mul / bias may carry a trailing 1).  One HIP pass each way; the result comes out
     in the autocast dtype when autocast is on (the reference's float32 result is cast to it by the Linear that follows)."""
-    cd = torch.get_autocast_dtype('cuda') if (x.is_cuda and torch.is_autocast_enabled('cuda')) else means.dtype
-    return _GaussianBasis.apply(x, mul, bias, means, stds, cd)
+    return _GaussianBasis.apply(x, mul, bias, means, stds, _compute_dtype(x, otherwise=means.dtype))

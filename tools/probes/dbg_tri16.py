@@ -1,8 +1,9 @@
+import ctypes
 import sys, torch, numpy as np
 sys.path.insert(0, '.')
 sys.path.insert(0, 'tests')
 import golden_util as gu
-from tgt_amd import ops, _lib
+from tgt_amd import ops
 dt = torch.float16 if len(sys.argv) < 2 else getattr(torch, sys.argv[1])
 B, N, C, H = 2, 48, 64, 4
 L = ops.TripletLayout(C, H)
@@ -19,7 +20,7 @@ def run(split, cs):
         a = ops._tri_args(qkv, mask, out, L, d_out, d_fused, colsum, eg=eg)
     else:
         a = ops._tri_args(fused, mask, out, L, d_out, d_fused, colsum)
-    ops._call('bwd', _lib.lib().tgt_triplet_attention_bwd, a)
+    ops._launch('tgt_triplet_attention_bwd', ctypes.byref(a))
     torch.cuda.synchronize()
     return d_fused, colsum
 ref, _ = run(False, False)
