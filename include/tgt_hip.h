@@ -193,6 +193,15 @@ int tgt_mask_node_counts(const float* mask, int32_t B, int32_t N, int32_t* count
  * 1 / 0): C = 256, D = 16, H = 16, N <= 32, bf16 / fp16.  Checks before any launch: sizes (TGT_ERR_INVALID), the supported
  * predicate (TGT_ERR_UNSUPPORTED), then null / misaligned x / w / b / eg / mask / out, then e_off / g_off + H outside a row of ld_eg elements (TGT_ERR_INVALID).
  *
+ * tgt_triplet_aggregate_proj64_fwd: the same forward for 33 <= N <= 64 (csrc/triplet_aggregate_proj64.hip): same arguments, same
+ * contract -- V never written, v / ld_v / v_off not read, eg[dir] may lie inside its direction's columns of `out` (the workgroup of a
+ * (graph, direction) reads ALL of its E/G, for both 32-row query tiles, before it writes its first O row), the dropout pattern of
+ * tgt_triplet_aggregate_fwd at this N.  Every X row is projected once per shared node j, for both query tiles.  Supported
+ * (tgt_triplet_aggregate_proj64_supported, host only, 1 / 0): C = 256, D = 16, H = 16, 33 <= N <= 64, bf16 / fp16 -- disjoint from
+ * tgt_triplet_aggregate_proj_supported, which stays 0 above 32 nodes.  Checks before any launch, in this order: sizes
+ * (TGT_ERR_INVALID), the predicate (TGT_ERR_UNSUPPORTED), B == 0 (TGT_OK), null / misaligned x / w / b / eg / mask / out, e_off /
+ * g_off + H outside a row of ld_eg elements, graph_scale not 4-byte aligned (TGT_ERR_INVALID).  _fwd_skip: graph_scale as below.
+ *
  * DropPath-dropped graphs: tgt_triplet_aggregate_fwd_skip / _bwd_skip / _proj_fwd_skip are the three entry points above plus
  * graph_scale: (B) float32 DEVICE memory, the per-graph DropPath factor of the residual branch the call belongs to (see
  * tgt_triplet_attention_args.graph_scale), or NULL (= the entry point without _skip, which forwards here with NULL and computes
@@ -234,6 +243,11 @@ int tgt_triplet_aggregate_fwd_skip(const tgt_triplet_aggregate_args* a, const fl
 int tgt_triplet_aggregate_bwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale, void* stream);
 int tgt_triplet_aggregate_proj_fwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale,
                                         const void* x, int32_t C, const void* w, const void* b, void* stream);
+int tgt_triplet_aggregate_proj64_supported(const tgt_triplet_aggregate_args* a, int32_t C);
+int tgt_triplet_aggregate_proj64_fwd(const tgt_triplet_aggregate_args* a, const void* x, int32_t C, const void* w, const void* b,
+                                     void* stream);
+int tgt_triplet_aggregate_proj64_fwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale,
+                                          const void* x, int32_t C, const void* w, const void* b, void* stream);
 
 /* ------------------------------------------------------------------------
  * TriangularUpdate core (reference lib/tgt/layers/triplet.py:156-172: the four

@@ -22,7 +22,7 @@ SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_l
            ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip', 'triplet_attention_bwd2.hip',
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=9'], '.f32'), ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=2'], '.bf16'),
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=4'], '.f16'), ('triplet_aggregate.hip', ['-DTGT_AGG_INST=1'], '.plain'),
-           ('triplet_aggregate.hip', ['-DTGT_AGG_INST=2'], '.skip'), 'triplet_aggregate_proj.hip',
+           ('triplet_aggregate.hip', ['-DTGT_AGG_INST=2'], '.skip'), 'triplet_aggregate_proj.hip', 'triplet_aggregate_proj64.hip',
            ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=9'], '.f32'), ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=2'], '.bf16'),
            ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=4'], '.f16'), 'node_attention.hip', 'node_attention_mfma.hip', 'node_attention16.hip', 'node_attention_kb.hip', 'node_attention_kb_bwd.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip']
 ABI_VERSION = 32
@@ -133,6 +133,9 @@ SYMBOLS = {
     'tgt_triplet_aggregate_fwd_skip': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp, _vp]),
     'tgt_triplet_aggregate_bwd_skip': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp, _vp]),
     'tgt_triplet_aggregate_proj_fwd_skip': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp, _vp, _i32, _vp, _vp, _vp]),
+    'tgt_triplet_aggregate_proj64_supported': (C.c_int, [C.POINTER(TripletAggregateArgs), _i32]),
+    'tgt_triplet_aggregate_proj64_fwd': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp, _i32, _vp, _vp, _vp]),
+    'tgt_triplet_aggregate_proj64_fwd_skip': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp, _vp, _i32, _vp, _vp, _vp]),
     'tgt_node_attention_fwd': (C.c_int, [C.POINTER(NodeAttentionArgs), _vp]),
     'tgt_node_attention_bwd': (C.c_int, [C.POINTER(NodeAttentionArgs), _vp]),
     'tgt_node_attention_family': (C.c_int, [C.POINTER(NodeAttentionArgs), _i32]),

@@ -54,6 +54,9 @@ int triplet_attention_proj_run(const tgt_triplet_attention_args* a, const int32_
 int triplet_aggregate_proj_supported(const tgt_triplet_aggregate_args* a, int C);
 int triplet_aggregate_proj_run(const tgt_triplet_aggregate_args* a, const float* graph_scale, const void* x, int C, const void* w,
                                const void* bias, hipStream_t st);
+int triplet_aggregate_proj64_supported(const tgt_triplet_aggregate_args* a, int C);
+int triplet_aggregate_proj64_run(const tgt_triplet_aggregate_args* a, const float* graph_scale, const void* x, int C, const void* w,
+                                 const void* bias, hipStream_t st);
 int fuse_rows_run(const tgt_fuse_rows_args* a, bool scatter, hipStream_t st);
 int permute_cols_run(const void* src, int sd, const int32_t* idx, void* dst, int dd, int rows, int cols, hipStream_t st);
 int sum_planes_run(const float* x, int planes, int64_t n, float* out, hipStream_t st);
@@ -206,6 +209,15 @@ int tgt_triplet_aggregate_proj_fwd(const tgt_triplet_aggregate_args* a, const vo
 int tgt_triplet_aggregate_proj_fwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale, const void* x, int32_t C,
                                         const void* w, const void* b, void* stream) {
     return triplet_aggregate_proj_run(a, graph_scale, x, C, w, b, reinterpret_cast<hipStream_t>(stream));
+}
+int tgt_triplet_aggregate_proj64_supported(const tgt_triplet_aggregate_args* a, int32_t C) { return triplet_aggregate_proj64_supported(a, C); }
+int tgt_triplet_aggregate_proj64_fwd(const tgt_triplet_aggregate_args* a, const void* x, int32_t C, const void* w, const void* b,
+                                     void* stream) {
+    return tgt_triplet_aggregate_proj64_fwd_skip(a, nullptr, x, C, w, b, stream);
+}
+int tgt_triplet_aggregate_proj64_fwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale, const void* x, int32_t C,
+                                          const void* w, const void* b, void* stream) {
+    return triplet_aggregate_proj64_run(a, graph_scale, x, C, w, b, reinterpret_cast<hipStream_t>(stream));
 }
 int tgt_fuse_rows(const tgt_fuse_rows_args* a, void* stream) { return fuse_rows_run(a, false, reinterpret_cast<hipStream_t>(stream)); }
 int tgt_unfuse_rows(const tgt_fuse_rows_args* a, void* stream) { return fuse_rows_run(a, true, reinterpret_cast<hipStream_t>(stream)); }

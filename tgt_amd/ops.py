@@ -27,6 +27,7 @@ _TRI_SPLIT = K.tri_split        # A/B knobs: tgt_amd/knobs.py reads the environm
 _TRI_PROJ = K.tri_proj
 _TRI_PROJ_INFER = K.tri_proj_infer
 _AGG_PROJ_INFER = K.agg_proj_infer
+_AGG_PROJ64_INFER = K.agg_proj64_infer
 _TRI_COLSUM = K.tri_colsum
 # graph_scale (DropPath-dropped graphs skipped by the triplet kernels) reaches the BACKWARD kernel only with TGT_TRI_SKIP=2: at the
 # BASELINE shapes the backward is 1024 workgroups in exactly four rounds on 256 CUs (one workgroup per CU), and with ~10 % of them
@@ -898,6 +899,13 @@ def _agg_proj_ok(x, N, L, cd):
             cd in (torch.bfloat16, torch.float16) and x.numel() // L.C >= _SPLIT_MIN_ROWS)
 
 
+def _agg_proj64_ok(x, N, L, cd):
+    """the same for 33 <= N <= 64 (tgt_triplet_aggregate_proj64_fwd): that kernel's shape limits, an unpadded
+    fused row and the row gate of _agg_proj_ok"""
+    return (x.is_cuda and 33 <= N <= 64 and L.C == 256 and L.D == 16 and L.H == 16 and L.width == L.used and
+            cd in (torch.bfloat16, torch.float16) and x.numel() // L.C >= _SPLIT_MIN_ROWS)
+
+
 def _agg_proj_eg_view(out, L):
     """where the narrow E/G rows of a fused call live: ne = used - 2C columns INSIDE `out`, ne / 2 on either side of the boundary
     between the two directions' column blocks -- [E_in | G_in] are the last columns of the inward block, [E_out | G_out] the first of
@@ -926,13 +934,21 @@ def projected_triplet_aggregate(x, params, mask3, layout, table, dropout=(0.0, 0
     """triplet_aggregate(fused_linear(x, table, params), mask3, layout, dropout, graph_scale).  params: the module's nn.Linear parameters
     (lin_V.weight, lin_V.bias, lin_E(G).weight, lin_E(G).bias).  A call that no backward can follow (torch.no_grad(), or nothing
     requires grad) projects V inside the aggregate kernel where _agg_proj_ok holds: only the narrow E/G rows are projected
-    beforehand, into columns of the result itself, and no fused row is allocated (TGT_AGG_PROJ_INFER is the A/B knob).
+    beforehand, into columns of the result itself, and no fused row is allocated (TGT_AGG_PROJ_INFER is the A/B knob).  With
+    33 <= N <= 64 the same call goes to tgt_triplet_aggregate_proj64_fwd where _agg_proj64_ok holds (TGT_AGG_PROJ64_INFER).
     graph_scale: see triplet_aggregate; both paths skip the dropped graphs in the aggregate kernel (the projections that run as
     library GEMMs still cover every graph)."""
     L = layout
     cd = _compute_dtype(x)
     N = x.shape[1]
-    if not (_no_backward(x, *params) and _AGG_PROJ_INFER and _agg_proj_ok(x, N, L, cd)):
+    # (the two kernels' node counts are disjoint: at most one entry point answers)
+    entry = None
+    if _no_backward(x, *params):
+        if _AGG_PROJ_INFER and _agg_proj_ok(x, N, L, cd):
+            entry = 'tgt_triplet_aggregate_proj_fwd'
+        elif _AGG_PROJ64_INFER and _agg_proj64_ok(x, N, L, cd):
+            entry = 'tgt_triplet_aggregate_proj64_fwd'
+    if entry is None:
         return triplet_aggregate(fused_linear(x, table, params), mask3, L, dropout, graph_scale)
     with torch.no_grad():
         _dev(x, mask3)
@@ -946,10 +962,9 @@ def projected_triplet_aggregate(x, params, mask3, layout, table, dropout=(0.0, 0
         _narrow_linear(x2, w[2 * L.C:L.used], b[2 * L.C:L.used], cd, out=egv)
         a = _agg_proj_args(out, mask3, out, L, dropout)
         if graph_scale is None:
-            _launch('tgt_triplet_aggregate_proj_fwd', C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), prof='tgt_triplet_aggregate_proj_fwd')
+            _launch(entry, C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), prof=entry)
         else:
-            _launch('tgt_triplet_aggregate_proj_fwd_skip', C.byref(a), _ptr(graph_scale), _ptr(x2), L.C, _ptr(w), _ptr(b),
-                    prof='tgt_triplet_aggregate_proj_fwd')
+            _launch(entry + '_skip', C.byref(a), _ptr(graph_scale), _ptr(x2), L.C, _ptr(w), _ptr(b), prof=entry)
     return out
 
 

@@ -8,7 +8,9 @@ on one MI355X.  One JSON line per configuration.
         predict_in_train) of TGT_Distance -> argmax bins of the symmetrised softmax -> bins2dist on the device ->
         S stochastic forwards of TGT_Gap, one per bins sample (tgt_amd/pcqm/predict.py::two_stage_predict)
 
-python tools/infer_bench.py [--samples 4] [--batch 512] [--steps 3]
+python tools/infer_bench.py [--samples 4] [--batch 512] [--steps 3] [--nodes 32]
+(--nodes: the padded node count of cfg5's batch; above 32 the aggregate forward is tgt_triplet_aggregate_proj64_fwd,
+TGT_AGG_PROJ64_INFER=0 is the A/B knob and `knobs` in the line says which side ran)
 """
 import argparse
 import json
@@ -19,7 +21,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from tgt_amd import ops                                              # noqa: E402
+from tgt_amd import knobs, ops                                       # noqa: E402
 from tgt_amd.pcqm import TGT_Distance, TGT_Gap, predict as pp        # noqa: E402
 from tgt_amd.training import configs, gemm_tuning                   # noqa: E402
 from tgt_amd.training.synthetic import make_batch                    # noqa: E402
@@ -50,6 +52,7 @@ def main():
     ap.add_argument('--samples', type=int, default=4, help='MC samples per stage of cfg5 (the shipped configs use 50)')
     ap.add_argument('--batch', type=int, default=512)
     ap.add_argument('--steps', type=int, default=3)
+    ap.add_argument('--nodes', type=int, default=32, help='padded node count of the cfg5 batch (the BASELINE shape is 32)')
     ap.add_argument('--only', default='')
     a = ap.parse_args()
     gemm_tuning.enable_gemm_tuning(online=True)
@@ -87,11 +90,11 @@ def main():
         gk.pop('num_dist_bins')
         dist_model = TGT_Distance(**dk).cuda().train()                                # predict_in_train: dropout ON
         gap_model = TGT_Gap(**gk).cuda().train()
-        batch = device_batch(B, 32, 12, ragged=False)
+        batch = device_batch(B, a.nodes, 12, ragged=False)
         batch['num_nodes'] = batch['node_mask'].sum(-1).long()
         # (events only around the attention kernels, one launch in three: an event pair around every launch slows the host AND the queue,
         #  DESIGN.md 5.2)
-        prof = ops.profile_kernels(True, only=('tgt_triplet_aggregate_fwd', 'tgt_triplet_aggregate_proj_fwd', 'tgt_node_attention_fwd', 'tgt_node_attention_fwd(logits)'), stride=3)
+        prof = ops.profile_kernels(True, only=('tgt_triplet_aggregate_fwd', 'tgt_triplet_aggregate_proj_fwd', 'tgt_triplet_aggregate_proj64_fwd', 'tgt_node_attention_fwd', 'tgt_node_attention_fwd(logits)'), stride=3)
 
         def run():
             return pp.two_stage_predict(dist_model, gap_model, batch, S, 256, 8, autocast_dtype=torch.float16)
@@ -99,11 +102,12 @@ def main():
         ops.profile_kernels(False)
         bins, gap = run()
         kt = {k: round(sum(v) / len(v), 4) for k, v in ops.kernel_times_ms(prof).items()}
-        print(json.dumps(dict(metric='graphs/sec end-to-end two-stage inference, TGT-Agx2 12x2 (dist+gap), fp16, batch 512 (cfg 5)',
+        print(json.dumps(dict(metric=f'graphs/sec end-to-end two-stage inference, TGT-Agx2 12x2 (dist+gap), fp16, batch {B} (cfg 5)',
                               value=round(B / dt, 1), unit='graphs/s', ms_per_batch=round(dt * 1e3, 2), dtype='fp16',
                               mc_samples_per_stage=S, stochastic_forwards_per_batch=2 * S,
                               graph_forwards_per_s=round(2 * S * B / dt, 1), n_gpus=1, data='synthetic',
-                              gap_finite=bool(torch.isfinite(gap).all()), kernel_ms=kt)), flush=True)
+                              gap_finite=bool(torch.isfinite(gap).all()), kernel_ms=kt, batch=B, nodes=a.nodes,
+                              knobs=knobs.K.non_default())), flush=True)
 
     if 'tgt_at' in a.only:
         # (opt-in: --only tgt_at)  TGT-At 24L, the training benchmark's model, as a forward without autograd: eval mode, bf16

@@ -130,6 +130,8 @@ def main():
         # tgt_triplet_aggregate_proj_fwd itself (the C entry point on pre-projected E/G rows, a.v = NULL) + the narrow E/G Linear it
         # needs, against what it replaces: the library GEMM of the fused row [V_in | V_out | E | G] + tgt_triplet_aggregate_fwd.
         # fp16 and bf16, 7 alternating rounds in one process; algorithmic bytes of both paths from the shapes
+        # --N above 32: tgt_triplet_aggregate_proj64_fwd (33..64 nodes); the plain kernel it is compared with then
+        # walks the graph once per 32-row query tile and reads every V slab twice
         import ctypes
         import statistics
         from tgt_amd import _lib
@@ -137,7 +139,8 @@ def main():
         L = ops.AggregateLayout(C, Ht)
         ne, rows = L.used - 2 * C, Bp * n2
         maskp = torch.zeros(Bp, N, N, device=dev)
-        byts = dict(unfused=rows * (C + L.width + L.width + 2 * C) * 2, fused=rows * (C + ne + 2 * C + ne + 2 * C) * 2,
+        v_reads = 1 if N <= 32 else 2
+        byts = dict(unfused=rows * (C + L.width + L.width + (v_reads - 1) * 2 * C + 2 * C) * 2, fused=rows * (C + ne + 2 * C + ne + 2 * C) * 2,
                     kernel=rows * (2 * C + ne + 2 * C) * 2)
         out['aggproj_bytes'] = dict(byts, B=Bp, N=N, H=Ht)
         cases = {}
@@ -154,10 +157,11 @@ def main():
             def narrow(x2=x2, we=we, be=be, own_eg=own_eg, egv=egv):
                 return ops.edge_linear_raw(x2, we, be, out=egv) if own_eg else torch.addmm(be, x2, we.t(), out=egv)
             ap_ = ops._agg_proj_args(o, maskp, o, L)
-            fn = _lib.lib().tgt_triplet_aggregate_proj_fwd
+            entry = 'tgt_triplet_aggregate_proj_fwd' if N <= 32 else 'tgt_triplet_aggregate_proj64_fwd'
+            fn = getattr(_lib.lib(), entry)
 
             def kernel(ap_=ap_, x=x, w=w, bias=bias):
-                _lib.check(fn(ctypes.byref(ap_), ops._ptr(x), C, ops._ptr(w), ops._ptr(bias), ops._stream()), 'tgt_triplet_aggregate_proj_fwd')
+                _lib.check(fn(ctypes.byref(ap_), ops._ptr(x), C, ops._ptr(w), ops._ptr(bias), ops._stream()), entry)
 
             def fused(narrow=narrow, kernel=kernel):
                 narrow()
