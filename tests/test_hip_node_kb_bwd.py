@@ -3,7 +3,6 @@ softmax statistics read from what the forward saved) against the float64 oracle,
 
 Oracle and bars are those of tests/test_hip_ops.py::test_node_attention: oracle.core.egt_attention_core in float64 on the values as
 the kernel sees them; rel-L2 8e-3 (bf16) / 1e-3 (fp16) on outputs, twice that on gradients."""
-import ctypes as C
 import functools
 import json
 import os
@@ -15,6 +14,7 @@ import pytest
 import torch
 
 import golden_util as gu
+from node_family_cases import family
 from oracle import core
 
 pytestmark = pytest.mark.gpu
@@ -39,15 +39,6 @@ def rel(a, b):
 
 def rnd(rng, *shape):
     return torch.from_numpy(rng.standard_normal(shape))
-
-
-def family(qkv, eg, mask3, H, bwd=1):
-    """tgt_node_attention_family for the call ops.node_attention makes with these tensors (the addresses are only looked at)"""
-    from tgt_amd import _lib, ops
-    a, _ = ops._node_args(qkv, eg, mask3, H, True, False)
-    for f in ('vatt', 'hhat', 'lse', 'gsum', 'd_vatt', 'd_hhat', 'd_qkv', 'd_eg'):
-        setattr(a, f, qkv.data_ptr())
-    return _lib.lib().tgt_node_attention_family(C.byref(a), bwd)
 
 
 @functools.lru_cache(maxsize=None)

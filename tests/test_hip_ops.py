@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import golden_util as gu
+import node_family_cases as nfc
 import parity_log
 from oracle import core
 
@@ -434,7 +435,7 @@ NODE_CASES = [  # B, N, num_nodes, W, H
     (2, 7, [7, 2], 96, 12),       # H not a power of two
     (1, 40, [33], 64, 8),         # N > 32
     (2, 9, [9, 5], 128, 16),      # D = 8: matrix-core kernels both ways (16-bit)
-    (2, 12, [12, 7], 256, 16),    # D = 16: matrix-core forward, lane-per-head backward
+    (2, 12, [12, 7], 256, 16),    # D = 16: matrix-core kernels both ways (16-bit)
     (2, 48, [48, 37], 768, 64),   # BASELINE config 4's node count at BASELINE width: 16-wide matrix-core tiles, 3 x 3 blocks, D = 12, four head groups
     (2, 33, [33, 20], 128, 16),   # one node past two blocks, D = 8
     (1, 64, [57], 128, 16),       # four blocks, D = 8 (the largest backward image that fits the LDS), ragged last block
@@ -442,7 +443,7 @@ NODE_CASES = [  # B, N, num_nodes, W, H
     (2, 40, [40, 33], 256, 32),   # H = 32, D = 8: key-blocked forward with two heads per wave
     (1, 33, [33], 512, 32),       # H = 32, D = 16
     (3, 12, [12, 7, 1], 384, 32), # one key block, D = 12, a one-node graph
-    (1, 80, [71], 256, 32),       # N > 64: key-blocked forward (five blocks), lane-per-head backward
+    (1, 80, [71], 256, 32),       # N > 64: key-blocked forward (five blocks), key-blocked backward (16-bit)
 ]
 
 
@@ -534,6 +535,8 @@ def test_node_attention_arbitrary_mask_and_large_logits(case, dtype):
     v_ref, h_ref = core.egt_attention_core(q64, e64, m.double().reshape(gu.additive_mask([N] * B, N, torch.float32).shape), H, True)
     ((v_ref * d_v.double()).sum() + (h_ref * d_h.double()).sum()).backward()
     qx, ex = qkv.cuda().requires_grad_(True), eg.cuda().requires_grad_(True)
+    fwd, bwd = nfc.families(nfc.EXISTING_HARD)[case + (dtype,)]         # the kernel families this case is here for
+    assert (nfc.family(qx, ex, m.cuda(), H, 0), nfc.family(qx, ex, m.cuda(), H, 1)) == (nfc.family_id(fwd), nfc.family_id(bwd))
     v, hh = ops.node_attention(qx, ex, m.cuda(), H, True, True)
     ((v.float() * d_v.cuda().float()).sum() + (hh.float() * d_h.cuda().float()).sum()).backward()
     assert torch.isfinite(v).all() and torch.isfinite(qx.grad).all() and torch.isfinite(ex.grad).all()
