@@ -405,3 +405,31 @@ def test_compute_dtype_keeps_both_spellings_of_its_call_sites(monkeypatch):
     assert ops._no_backward(x, None) and not ops._no_backward(x, None, p)
     with torch.no_grad():
         assert ops._no_backward(x, p)
+
+
+def test_timing_probes_accept_every_parameter_of_what_they_replace(monkeypatch):
+    """tools/probes/skip_probes.py replaces functions of tgt_amd.ops that the autograd Functions call with keywords: a replacement
+    that lacks a parameter of the real function (as _ln_backward's lacked `live`) raises TypeError on the first backward of
+    bench.py --timing-probe.  Every replacement takes every parameter of the function it replaces, under the same name."""
+    import importlib.util
+    import inspect
+    import os
+    from tgt_amd import ops
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools', 'probes', 'skip_probes.py')
+    spec = importlib.util.spec_from_file_location('skip_probes', path)
+    skip_probes = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(skip_probes)
+    replaced = {'skip_sums': 'sum_planes', 'skip_proj_ln': '_ln_backward', 'skip_wgrad': '_wgrad_into'}
+    assert set(replaced) == set(skip_probes.PROBES)
+    for probe, name in replaced.items():
+        real = getattr(ops, name)
+        monkeypatch.setattr(ops, name, real)                # (registers the real function for restoration: install() overwrites it)
+        monkeypatch.setattr(ops, 'torch', ops.torch)        # (skip_wgrad also wraps the module's view of torch)
+        skip_probes.install(probe)
+        probe_fn = getattr(ops, name)
+        assert probe_fn is not real, (probe, name)
+        have = inspect.signature(probe_fn).parameters
+        for pname, par in inspect.signature(real).parameters.items():
+            assert pname in have and have[pname].kind == par.kind, (probe, name, pname)
+        monkeypatch.undo()
+        assert getattr(ops, name) is real and ops.torch is torch

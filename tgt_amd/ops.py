@@ -7,6 +7,7 @@ eager / CPU fallback (a missing library or a CPU tensor raises).
 import collections
 import contextlib
 import ctypes as C
+import inspect
 import os
 import weakref
 
@@ -114,6 +115,29 @@ def _no_backward(*tensors):
     """can NO backward follow this call (torch.no_grad(), or nothing requires grad)?  Grad mode is always off INSIDE
     Function.forward and ctx.needs_input_grad ignores torch.no_grad(): asked before .apply"""
     return not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors))
+
+
+_XWB = ('x', 'weight', 'bias')     # how the forward of every Function on _linear_backward_db begins
+
+
+def _forward_args(function, begins=()):
+    """the named parameters of an autograd Function's forward behind ctx, in order (a *rest is left out): what its backward asks
+    ctx.needs_input_grad by (NAMES.index('pre')) and returns one slot each for (_grads); begins: checked"""
+    params = list(inspect.signature(function.forward).parameters.values())[1:]
+    names = tuple(p.name for p in params if p.kind is not p.VAR_POSITIONAL)
+    assert names[:len(begins)] == begins, names
+    return names
+
+
+def _grads(names, *leading, **named):
+    """what a backward returns, one slot per parameter of its forward (`names`): the gradients of the leading parameters and of
+    those given by name, None in every other slot"""
+    if not named:                      # (a tuple sum, 0.3 us: every Linear's backward ends here, hundreds of times a step)
+        return leading + (None,) * (len(names) - len(leading))
+    out = list(leading) + [None] * (len(names) - len(leading))
+    for name, grad in named.items():
+        out[names.index(name)] = grad
+    return tuple(out)
 
 
 def _stream():
@@ -707,9 +731,7 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             # Q/K/V projected inside the attention kernel (it still writes them once, for the
             # backward); only the narrow E/G third-arm projection stays a library GEMM, written
             # straight into its columns of the fused row
-            x2 = x.reshape(-1, L.C)
-            x2 = (x2 if x2.dtype == cd else x2.to(cd)).contiguous()
-            w, b = _as_dtype(weight, cd).contiguous(), _as_dtype(bias, cd).contiguous()
+            x2, w, b = _linear_operands(x, weight, bias, cd, x_contiguous=True, wb_contiguous=True)
             # the Q/K/V rows (written by the kernel, for the backward) and the narrow third-arm E/G projection as two tensors,
             # as in the split-GEMM path below.  no_backward (torch.no_grad(), or no input requires grad): nothing will read
             # those rows, so they are neither allocated nor written (TRI_NO_QKV_STORE: 2/3 of the kernel's bytes);
@@ -731,9 +753,7 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             # two GEMMs: Q/K/V (6C = 1536 channels: six full 256-wide tile columns, 294 us) and the
             # narrow E/G (39 us) instead of one ragged 1600-wide GEMM (376 us; tools/gemm_probe.py);
             # the backward still writes ONE fused gradient row (ld_dqkv / ld_deg)
-            x2 = x.reshape(-1, L.C)
-            x2 = x2 if x2.dtype == cd else x2.to(cd)
-            w, b = _as_dtype(weight, cd), _as_dtype(bias, cd)
+            x2, w, b = _linear_operands(x, weight, bias, cd)
             fused = torch.addmm(b[:6 * L.C], x2, w[:6 * L.C].t()).view(B, N, N, 6 * L.C)
             eg = _narrow_linear(x2, w[6 * L.C:L.used], b[6 * L.C:L.used], cd).view(B, N, N, L.used - 6 * L.C)
             skip.launch_attention(_tri_args(fused, mask3, out, L, dropout=dropout, eg=eg, graph_scale=graph_scale))
@@ -743,7 +763,7 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         ctx.save_for_backward(x2, w, fused, mask3, out, eg if eg is not None else fused.new_empty(0),
                               *(wb if table is not None else ()))
         ctx.L, ctx.table, ctx.dropout, ctx.skip = L, table, dropout, skip.for_backward(projection_fused)
-        ctx.meta = (x.shape, x.dtype, weight.dtype, bias.dtype)
+        ctx.lin = _LinearSaved.of(x, weight, bias, edge=False)
         return out
 
     @staticmethod
@@ -751,8 +771,7 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         x2, w, fused, mask3, out, eg = ctx.saved_tensors[:6]
         params = ctx.saved_tensors[6:]
         eg = eg if eg.numel() else None
-        L, table = ctx.L, ctx.table
-        xs, xdt, wdt, bdt = ctx.meta
+        L, table, lin = ctx.L, ctx.table, ctx.lin
         d_out = d_out.contiguous()
         d_fused = torch.empty(*fused.shape[:3], L.width, dtype=fused.dtype, device=fused.device)   # every used column is written
         if L.width > L.used:
@@ -764,7 +783,8 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         ctx.skip.launch_attention(a, bwd=True)
         if _GATE_NODE_BWD == 1:
             _gate_record(d_fused.device)
-        need_p = any(ctx.needs_input_grad[9:])
+        need_dx = ctx.needs_input_grad[_PTA_ARGS.index('x')]
+        need_p = any(ctx.needs_input_grad[len(_PTA_ARGS):])
         d2 = d_fused.view(-1, L.width)
         if kb:
             db = column_sum(d2) if need_p else None
@@ -779,7 +799,7 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             # (213 us with 32 chunks) and the 64-row E/G block is cheap (35 us), against 303 us for the
             # 1600-row product (tools/wgrad_chunk_probe.py); dx stays one GEMM over the fused row
             ws = _wgrad_fork(d2, x2, db)
-            dx, _, _ = _linear_backward(x2, w, d2, xs, xdt, torch.float32, None, ctx.needs_input_grad[0], False, False)
+            dx, _, _ = _linear_backward(lin, x2, w, d2, need_dx, False, False)
             if _GATE_NODE_BWD == 2:
                 _gate_record(d_fused.device)
             with _on_stream(ws):
@@ -788,15 +808,18 @@ class _ProjectedTripletAttention(torch.autograd.Function):
                 _wgrad_into(dw[6 * L.C:], d2[:, 6 * L.C:], x2, 128)
         else:
             ws = None
-            dx, dw, _ = _linear_backward(x2, w, d2, xs, xdt, torch.float32, None,
-                                         ctx.needs_input_grad[0], need_p, False)
+            dx, dw, _ = _linear_backward(lin, x2, w, d2, need_dx, need_p, False, wdt=torch.float32)
         if not need_p:
-            return (dx, None, None, None, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 9)
-        if table is None:
-            return dx, None, None, None, None, None, None, None, None, _param_grad(dw, wdt), _param_grad(db, bdt)
-        with _on_stream(ws):           # (the parameter gradients leave on the stream their weight gradient was computed on)
-            grads = _unfuse_grads(table, params, dw, db)
-        return (dx, None, None, None, None, None, None, None, None, *grads)
+            grads = (None,) * (len(ctx.needs_input_grad) - len(_PTA_ARGS))
+        elif table is None:
+            grads = (_param_grad(dw, lin.wdt), _param_grad(db, lin.bdt))
+        else:
+            with _on_stream(ws):           # (the parameter gradients leave on the stream their weight gradient was computed on)
+                grads = _unfuse_grads(table, params, dw, db)
+        return _grads(_PTA_ARGS, dx) + tuple(grads)
+
+
+_PTA_ARGS = _forward_args(_ProjectedTripletAttention)
 
 
 def projected_triplet_attention(x, weight, bias, mask3, layout, table=None, dropout=(0.0, 0), graph_scale=None, node_counts=None):
@@ -954,9 +977,7 @@ def projected_triplet_aggregate(x, params, mask3, layout, table, dropout=(0.0, 0
         _dev(x, mask3)
         B = x.shape[0]
         _check_per_graph(graph_scale, B, torch.float32, 'triplet aggregate: graph_scale')
-        w, b = _fuse_params(table, params, cd)
-        x2 = x.reshape(-1, L.C)
-        x2 = (x2 if x2.dtype == cd else x2.to(cd)).contiguous()
+        x2, w, b = _linear_operands(x, *_fuse_params(table, params, cd), cd, x_contiguous=True)
         out = torch.empty(B, N, N, 2 * L.C, dtype=cd, device=x.device)
         egv, _ = _agg_proj_eg_view(out, L)                   # (the E/G rows wait inside `out` for the kernel: no tensor of their own)
         _narrow_linear(x2, w[2 * L.C:L.used], b[2 * L.C:L.used], cd, out=egv)
@@ -1338,8 +1359,7 @@ def gelu_dropout(x, p, training, sample_scale=None):
     The drop pattern comes from a per-call seed drawn from torch's CPU generator (no device sync).
     sample_scale (B,) float32: the result is multiplied by sample_scale[b] -- the DropPath factor of the residual
     branch, folded in here (see linear_residual_layer_norm(prescaled=True))."""
-    p = float(p) if training else 0.0
-    seed = _host_seed() if p > 0 else 0
+    p, seed = draw_dropout(p, training)
     if sample_scale is not None and (x.numel() // x.shape[0]) % 8:
         raise RuntimeError('gelu_dropout: sample_scale needs a multiple of 8 elements per sample')
     return _GeluDropout.apply(x, p, seed, sample_scale)
@@ -1405,8 +1425,7 @@ def glu_dropout(x, kind, p, training, sample_scale=None):
     lib/tgt/layers/layers.py:158.  Only x is kept for the backward; the drop pattern comes from a per-call seed (no mask tensor).
     sample_scale (B,) float32: the result is multiplied by sample_scale[b] (the branch's DropPath factor, see gelu_dropout)."""
     kind = _glu_kind(kind)
-    p = float(p) if training else 0.0
-    seed = _host_seed() if p > 0 else 0
+    p, seed = draw_dropout(p, training)
     _dev(x, sample_scale)
     _glu_check(x.shape[-1], x.numel() // 2, x.dtype, sample_scale, 'glu_dropout')
     return _GluDropout.apply(x, kind, p, seed, sample_scale)
@@ -1913,26 +1932,54 @@ def _narrow_linear(x2, w, b, cd, out=None, gemm=_addmm_tn):
     return gemm(x2, w, b, out=out)
 
 
-def _linear_forward(x, weight, bias, cd):
-    """(x2, w, y): the operands saved for the backward and y = x W^T + b in dtype cd"""
-    xs = x.shape
-    x2 = x.reshape(-1, xs[-1])
+def _linear_operands(x, weight, bias, cd, x_contiguous=False, wb_contiguous=False):
+    """(x2, w, b), THE operand prologue of every Linear here: x as (rows, K), weight and bias (may be None), all in dtype cd (a cast
+    only where the dtype differs; _as_dtype: a Trainer's 16-bit shadow instead of one); *_contiguous: dense, a copy only if needed"""
+    x2 = x.reshape(-1, x.size(-1))
     if x2.dtype != cd:
         x2 = x2.to(cd)
     w = _as_dtype(weight, cd)
     b = None if bias is None else _as_dtype(bias, cd)
+    if x_contiguous:
+        x2 = x2.contiguous()
+    if wb_contiguous:
+        w, b = w.contiguous(), None if b is None else b.contiguous()
+    return x2, w, b
+
+
+class _LinearSaved(collections.namedtuple('_LinearSaved', 'xs xdt wdt bdt wptr live lazy')):
+    """What the backward of ONE Linear needs besides its saved tensors, as ctx.lin: shape and dtype of x, the dtypes the gradients
+    of weight and bias are returned in (bdt None: no bias), the weight's address (its slice of a Trainer's flat gradient buffer:
+    _grad_dst), the tile list of the forward's row kernels (_edge_live) and whether dx may be left to a LayerNorm entry (_lazy_ok)."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, x, weight, bias, lazy=False, edge=True, fused=False):
+        """edge=False: a Linear outside the edge-row plumbing -- no tile list, no flat-gradient slice.  fused: weight and bias are
+        this call's own image of several parameters (_fuse_params): float32 gradients for the unfuse launch, no slice either."""
+        if fused:
+            return cls(x.shape, x.dtype, torch.float32, torch.float32, None, _edge_live, lazy)
+        return cls(x.shape, x.dtype, weight.dtype, None if bias is None else bias.dtype, weight.data_ptr() if edge else None,
+                   _edge_live if edge else None, lazy)
+
+
+def _linear_forward(x, weight, bias, cd):
+    """(x2, w, y): the operands saved for the backward and y = x W^T + b in dtype cd"""
+    x2, w, b = _linear_operands(x, weight, bias, cd)
     # the result must own its storage (not be a view): the layer adds the residual in place
-    y = torch.empty(*xs[:-1], weight.shape[0], dtype=cd, device=x.device)
+    y = torch.empty(*x.shape[:-1], weight.shape[0], dtype=cd, device=x.device)
     _narrow_linear(x2, w, b, cd, out=y.view(-1, weight.shape[0]), gemm=_gemm.linear_tn)    # (torch.mm / torch.addmm(out=) from a cached plan)
     return x2, w, y
 
 
-def _linear_backward(x2, w, dy2, xs, xdt, wdt, bdt, need_dx, need_dw, need_db, lazy_dx=False, dw_post=None, fork=True, dw_ptr=None,
-                     live=None):
-    """(dx, dW, db) of y = x W^T + b.  dW = dY^T X contracts over M = B*N*N = 262144 rows into a
+def _linear_backward(lin, x2, w, dy2, need_dx, need_dw, need_db, *, wdt=None, dw_post=None, fork=True):
+    """(dx, dW, db) of y = x W^T + b, lin: the forward's _LinearSaved.  dW = dY^T X contracts over M = B*N*N = 262144 rows into a
     tiny (out,in) result; as one GEMM the library runs it on a handful of workgroups
     (0.4-0.8 ms), as 64-128 independent chunk products + an fp32 sum it is HBM-bound (57 us for
-    256x256, measured; tools/wgrad_probe.py)."""
+    256x256, measured; tools/wgrad_probe.py).  wdt: the dtype dW is computed in when that is not the weight's own (float32 ahead
+    of a dw_post or of the unfuse launch)."""
+    xs, xdt, bdt, dw_ptr, live, lazy_dx = lin.xs, lin.xdt, lin.bdt, lin.wptr, lin.live, lin.lazy
+    wdt = wdt or lin.wdt
     if dy2.dtype != w.dtype:
         dy2 = dy2.to(w.dtype)
     dx = dw = db = None
@@ -1975,6 +2022,21 @@ def _linear_backward(x2, w, dy2, xs, xdt, wdt, bdt, need_dx, need_dw, need_db, l
     return dx, dw, db
 
 
+def _linear_backward_db(ctx, x2, w, dy2, cs=None, handed=None, want_dx=True, want_dw=True, **kw):
+    """_linear_backward for ctx.lin of a Function on (x, weight, bias, ...) (_XWB), the bias gradient taken from column sums of dy2
+    that a kernel upstream already produced where there are any: `cs`, or what rides on the gradient tensor `handed` (_hand_colsum);
+    x, weight and bias get what autograd asks for (want_dx / want_dw False: the caller has that one already)."""
+    lin = ctx.lin
+    need_dx, need_dw, need_db, *_ = ctx.needs_input_grad
+    need_db = need_db and lin.bdt is not None
+    if cs is None and handed is not None and need_db:
+        cs = _take_colsum(handed, handed.shape[-1])
+    dx, dw, db = _linear_backward(lin, x2, w, dy2, want_dx and need_dx, want_dw and need_dw, need_db and cs is None, **kw)
+    if need_db and cs is not None:
+        db = _param_grad(cs, lin.bdt)
+    return dx, dw, db
+
+
 class _Linear(torch.autograd.Function):
     """y = x W^T + b on the library GEMM, with the weight gradient computed as a BATCHED GEMM
     over row chunks (see _linear_backward)."""
@@ -1983,24 +2045,16 @@ class _Linear(torch.autograd.Function):
     def forward(ctx, x, weight, bias, cd, lazy=False):
         x2, w, y = _linear_forward(x, weight, bias, cd)
         ctx.save_for_backward(x2, w)
-        ctx.meta = (x.shape, x.dtype, weight.dtype, None if bias is None else bias.dtype)
-        ctx.lazy = lazy
-        ctx.wptr = weight.data_ptr()
-        ctx.live = _edge_live
+        ctx.lin = _LinearSaved.of(x, weight, bias, lazy)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x2, w = ctx.saved_tensors
-        xs, xdt, wdt, bdt = ctx.meta
-        need_db = bdt is not None and ctx.needs_input_grad[2]
-        cs = _take_colsum(dy, dy.shape[-1]) if need_db else None
-        dx, dw, db = _linear_backward(x2, w, dy.reshape(-1, dy.shape[-1]), xs, xdt, wdt, bdt,
-                                      ctx.needs_input_grad[0], ctx.needs_input_grad[1], need_db and cs is None, ctx.lazy,
-                                      dw_ptr=ctx.wptr, live=ctx.live)
-        if cs is not None:
-            db = _param_grad(cs, bdt)
-        return dx, dw, db, None, None
+        return _grads(_LINEAR_ARGS, *_linear_backward_db(ctx, x2, w, dy.reshape(-1, dy.shape[-1]), handed=dy))
+
+
+_LINEAR_ARGS = _forward_args(_Linear, _XWB)
 
 
 def _permute_cols(src, idx, dtype, after_sums=False):
@@ -2019,6 +2073,18 @@ def _permute_cols(src, idx, dtype, after_sums=False):
     return out
 
 
+def _permuted_weight(weight, cd, idx):
+    """weight[:, idx] in dtype cd -- the weight's input columns in the order the producing kernel emits its channels (lin_O of
+    the triplet modules): one launch, cast included, from the 16-bit shadow where the Trainer keeps one"""
+    return _permute_cols(_as_dtype_view(weight, cd).contiguous(), idx, cd)
+
+
+def _permuted_weight_grad(inv, wdt):
+    """the keywords of _linear_backward behind _permuted_weight: dW in float32, then back through the inverse permutation (one
+    launch, the cast to the weight's dtype wdt included); inv None: the weight was not permuted"""
+    return {} if inv is None else dict(wdt=torch.float32, dw_post=lambda t: _permute_cols(t.contiguous(), inv, wdt, after_sums=True))
+
+
 class _LinearPermutedCols(torch.autograd.Function):
     """y = x W[:, idx]^T + b: the weight's input columns re-ordered (and cast) by one launch,
     the weight gradient re-ordered back by one launch (lin_O of the triplet modules)."""
@@ -2026,25 +2092,19 @@ class _LinearPermutedCols(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, cd, idx, inv):
         _dev(x, weight)
-        w = _permute_cols(_as_dtype_view(weight, cd).contiguous(), idx, cd)
-        x2, w, y = _linear_forward(x, w, bias, cd)
+        x2, w, y = _linear_forward(x, _permuted_weight(weight, cd, idx), bias, cd)
         ctx.save_for_backward(x2, w, inv)
-        ctx.meta = (x.shape, x.dtype, weight.dtype, None if bias is None else bias.dtype)
-        ctx.live = _edge_live
+        ctx.lin = _LinearSaved.of(x, weight, bias)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x2, w, inv = ctx.saved_tensors
-        xs, xdt, wdt, bdt = ctx.meta
-        need_db = bdt is not None and ctx.needs_input_grad[2]
-        cs = _take_colsum(dy, dy.shape[-1]) if need_db else None
-        dx, dw, db = _linear_backward(x2, w, dy.reshape(-1, dy.shape[-1]), xs, xdt, torch.float32, bdt,
-                                      ctx.needs_input_grad[0], ctx.needs_input_grad[1], need_db and cs is None,
-                                      dw_post=lambda t: _permute_cols(t.contiguous(), inv, wdt, after_sums=True), live=ctx.live)
-        if cs is not None:
-            db = _param_grad(cs, bdt)
-        return dx, dw, db, None, None, None
+        return _grads(_LINEAR_PERMUTED_ARGS, *_linear_backward_db(ctx, x2, w, dy.reshape(-1, dy.shape[-1]), handed=dy,
+                                                                  **_permuted_weight_grad(inv, ctx.lin.wdt)))
+
+
+_LINEAR_PERMUTED_ARGS = _forward_args(_LinearPermutedCols, _XWB)
 
 
 def linear_permuted_cols(x, weight, bias, idx, inv):
@@ -2062,20 +2122,21 @@ class _FusedLinear(torch.autograd.Function):
         weight, bias = _fuse_params(table, params, cd)
         x2, w, y = _linear_forward(x, weight, bias, cd)
         ctx.save_for_backward(x2, w, *params)
-        ctx.table, ctx.meta = table, (x.shape, x.dtype)
-        ctx.live = _edge_live
+        ctx.table, ctx.lin = table, _LinearSaved.of(x, weight, bias, fused=True)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x2, w = ctx.saved_tensors[:2]
         params = ctx.saved_tensors[2:]
-        xs, xdt = ctx.meta
-        need_p = any(ctx.needs_input_grad[3:])
-        dx, dw, db = _linear_backward(x2, w, dy.reshape(-1, dy.shape[-1]), xs, xdt, torch.float32, torch.float32,
-                                      ctx.needs_input_grad[0], need_p, need_p, fork=False, live=ctx.live)
+        need_p = any(ctx.needs_input_grad[len(_FUSED_LINEAR_ARGS):])
+        dx, dw, db = _linear_backward(ctx.lin, x2, w, dy.reshape(-1, dy.shape[-1]), ctx.needs_input_grad[_FUSED_LINEAR_ARGS.index('x')],
+                                      need_p, need_p, fork=False)
         grads = _unfuse_grads(ctx.table, params, dw, db) if need_p else (None,) * len(params)
-        return (dx, None, None, *grads)
+        return _grads(_FUSED_LINEAR_ARGS, dx) + tuple(grads)
+
+
+_FUSED_LINEAR_ARGS = _forward_args(_FusedLinear)
 
 
 def fused_linear(x, table, params):
@@ -2195,6 +2256,23 @@ _FFN_GELU_EPI = K.ffn_gelu_epi     # A/B knob: lin_W1 + GELU + dropout as one la
 _FFN_GELU_BWD_EPI = K.ffn_gelu_bwd_epi
 
 
+def _linear_act_forward(ctx, x, weight, bias, cd, epilogue, act_cols, p, seed, sample_scale, lazy=False, flags=0):
+    """(act, pre) of the ONE launch behind _LinearGeluDropout / _LinearGluDropout: pre = x W^T + b and act = dropout(activation(pre),
+    p) * sample_scale[b] of act_cols channels; ctx gets (x2, w, pre, sample_scale), ctx.lin, and p / seed / elements per sample"""
+    _dev(x, weight, sample_scale)
+    x2, w, b = _linear_operands(x, weight, bias, cd)
+    N = weight.shape[0]
+    ctx.lin = _LinearSaved.of(x, weight, bias, lazy)
+    pre = torch.empty(*ctx.lin.xs[:-1], N, dtype=cd, device=x.device)
+    act = torch.empty(*ctx.lin.xs[:-1], act_cols, dtype=cd, device=x.device)
+    rps = (x2.shape[0] // sample_scale.numel()) if sample_scale is not None else 0
+    edge_linear_raw(x2, w, b, epilogue, out=act.view(-1, act_cols), out2=pre.view(-1, N), dropout=(p, seed),
+                    row_scale=sample_scale, rows_per_sample=rps, flags=flags, live=ctx.lin.live)
+    ctx.save_for_backward(x2, w, pre, sample_scale)
+    ctx.p, ctx.seed, ctx.eps_ = float(p), seed, rps * act_cols
+    return act, pre
+
+
 class _LinearGeluDropout(torch.autograd.Function):
     """act = dropout(gelu(x W^T + b), p) * sample_scale[b] as ONE launch (tgt_edge_linear, TGT_EPI_GELU on the row-phase
     kernel): the pre-activation is written once for the backward and never re-read by a separate activation pass
@@ -2203,37 +2281,19 @@ class _LinearGeluDropout(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, cd, p, seed, sample_scale, lazy=False):
-        _dev(x, weight, sample_scale)
-        ctx.lazy = lazy
-        xs = x.shape
-        x2 = x.reshape(-1, xs[-1])
-        if x2.dtype != cd:
-            x2 = x2.to(cd)
-        w = _as_dtype(weight, cd)
-        b = None if bias is None else _as_dtype(bias, cd)
-        N = weight.shape[0]
-        pre = torch.empty(*xs[:-1], N, dtype=cd, device=x.device)
-        act = torch.empty_like(pre)
-        rps = (x2.shape[0] // sample_scale.numel()) if sample_scale is not None else 0
-        ctx.live = _edge_live
-        edge_linear_raw(x2, w, b, _lib.EPI_GELU, out=act.view(-1, N), out2=pre.view(-1, N), dropout=(p, seed),
-                        row_scale=sample_scale, rows_per_sample=rps, live=ctx.live)
-        ctx.save_for_backward(x2, w, pre, sample_scale)
-        ctx.meta = (xs, x.dtype, weight.dtype, None if bias is None else bias.dtype, float(p), seed, rps * N)
-        ctx.wptr = weight.data_ptr()
         ctx.set_materialize_grads(False)
         # TWO outputs: the activation, and the pre-activation as a differentiable value of its own -- a consumer that owns the
         # activation's derivative (linear_residual_layer_norm: GELU backward as the epilogue of its data-gradient GEMM) reads
         # the activation detached and sends its gradient to `pre` directly
-        return act, pre
+        return _linear_act_forward(ctx, x, weight, bias, cd, _lib.EPI_GELU, weight.shape[0], p, seed, sample_scale, lazy)
 
     @staticmethod
     def backward(ctx, d_act, d_pre_in):
         x2, w, pre, sample_scale = ctx.saved_tensors
-        xs, xdt, wdt, bdt, p, seed, eps_ = ctx.meta
+        p, seed, eps_ = ctx.p, ctx.seed, ctx.eps_
         d_pre = None
-        need_db = bdt is not None and ctx.needs_input_grad[2]
-        cs = None
+        need_db = ctx.lin.bdt is not None and ctx.needs_input_grad[_LINEAR_GELU_ARGS.index('bias')]
+        cs = handed = None
         if d_act is not None:
             d_act = d_act.contiguous()
             d_pre = torch.empty_like(pre)
@@ -2250,35 +2310,39 @@ class _LinearGeluDropout(torch.autograd.Function):
                 _launch('tgt_gelu_dropout_scaled_bwd', _ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel(), _DT[pre.dtype], p, seed,
                         _ptr(sample_scale), eps_, prof='tgt_gelu_dropout_bwd')
         if d_pre_in is not None:
-            if d_pre is None and need_db:
-                cs = _take_colsum(d_pre_in, d_pre_in.shape[-1])        # (the GELU_BWD epilogue that wrote it summed its columns)
+            if d_pre is None:
+                handed = d_pre_in                                      # (the GELU_BWD epilogue that wrote it summed its columns)
             d_pre = d_pre_in.contiguous() if d_pre is None else d_pre + d_pre_in
         if d_pre is None:
-            return None, None, None, None, None, None, None, None
-        dx, dw, db = _linear_backward(x2, w, d_pre.view(-1, d_pre.shape[-1]), xs, xdt, wdt, bdt, ctx.needs_input_grad[0],
-                                      ctx.needs_input_grad[1], need_db and cs is None, ctx.lazy, dw_ptr=ctx.wptr, live=ctx.live)
-        if need_db and cs is not None:
-            db = _param_grad(cs, bdt)
-        return dx, dw, db, None, None, None, None, None
+            return _grads(_LINEAR_GELU_ARGS)
+        return _grads(_LINEAR_GELU_ARGS, *_linear_backward_db(ctx, x2, w, d_pre.view(-1, d_pre.shape[-1]), cs, handed))
 
 
-def linear_gelu_dropout_ok(x, weight, sample_scale=None):
-    """whether linear_gelu_dropout takes this call: edge rows (many of them), 16-bit compute dtype, 256 outputs, K in {64,128,256}"""
-    if not (_FFN_GELU_EPI and x.is_cuda):
+_LINEAR_GELU_ARGS = _forward_args(_LinearGeluDropout, _XWB)
+
+
+def _linear_act_ok(x, weight, sample_scale, N, ks, epilogue):
+    """does the one-launch Linear + activation + dropout take this call: edge rows (many of them), a 16-bit compute dtype, N
+    outputs from K in `ks` inputs, a float32 factor per sample over a whole number of rows each"""
+    if not x.is_cuda:
         return False
     cd = _compute_dtype(x, on_cpu=True)
     rows = x.numel() // x.shape[-1]
     if sample_scale is not None and (rows % sample_scale.numel() or sample_scale.dtype != torch.float32):
         return False
-    return weight.shape[0] == 256 and _edge_kernel_ok(x.reshape(-1, x.shape[-1]), 256, cd) and \
-        edge_linear_supported(x.shape[-1], 256, cd, _lib.EPI_GELU, row_scale=sample_scale is not None)
+    return weight.shape[0] == N and _edge_kernel_ok(x.reshape(-1, x.shape[-1]), N, cd, ks) and \
+        edge_linear_supported(x.shape[-1], N, cd, epilogue, row_scale=sample_scale is not None)
+
+
+def linear_gelu_dropout_ok(x, weight, sample_scale=None):
+    """whether linear_gelu_dropout takes this call: edge rows (many of them), 16-bit compute dtype, 256 outputs, K in {64,128,256}"""
+    return bool(_FFN_GELU_EPI) and _linear_act_ok(x, weight, sample_scale, 256, (64, 128, 256), _lib.EPI_GELU)
 
 
 def linear_gelu_dropout(x, weight, bias, p, training, sample_scale=None):
     """dropout(gelu(linear(x, weight, bias)), p) [* sample_scale per graph] in one launch; see linear_gelu_dropout_ok"""
     cd = _compute_dtype(x, on_cpu=True)
-    p = float(p) if training else 0.0
-    seed = _host_seed() if p > 0 else 0
+    p, seed = draw_dropout(p, training)
     act, pre = _LinearGeluDropout.apply(x, weight, bias, cd, p, seed, sample_scale, _lazy_ok(x, weight, cd))
     # rides on the tensor object (as _tgt_colsum does): what a consumer needs to take over the activation's backward
     act._tgt_gelu = (pre, p, seed, sample_scale)
@@ -2293,45 +2357,23 @@ class _LinearGluDropout(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, cd, kind, p, seed, sample_scale):
-        _dev(x, weight, sample_scale)
-        xs = x.shape
-        x2 = x.reshape(-1, xs[-1])
-        if x2.dtype != cd:
-            x2 = x2.to(cd)
-        w = _as_dtype(weight, cd)
-        b = None if bias is None else _as_dtype(bias, cd)
-        N2 = weight.shape[0]
-        pre = torch.empty(*xs[:-1], N2, dtype=cd, device=x.device)
-        act = torch.empty(*xs[:-1], N2 // 2, dtype=cd, device=x.device)
-        rps = (x2.shape[0] // sample_scale.numel()) if sample_scale is not None else 0
-        ctx.live = _edge_live
-        edge_linear_raw(x2, w, b, _lib.EPI_GLU, out=act.view(-1, N2 // 2), out2=pre.view(-1, N2), dropout=(p, seed),
-                        row_scale=sample_scale, rows_per_sample=rps, flags=kind << _lib.EDGE_GLU_KIND_SHIFT, live=ctx.live)
-        ctx.save_for_backward(x2, w, pre, sample_scale)
-        ctx.meta = (xs, x.dtype, weight.dtype, None if bias is None else bias.dtype, kind, float(p), seed, rps * (N2 // 2))
-        ctx.wptr = weight.data_ptr()
-        return act
+        ctx.kind = kind
+        return _linear_act_forward(ctx, x, weight, bias, cd, _lib.EPI_GLU, weight.shape[0] // 2, p, seed, sample_scale,
+                                   flags=kind << _lib.EDGE_GLU_KIND_SHIFT)[0]
 
     @staticmethod
     def backward(ctx, d_act):
         x2, w, pre, sample_scale = ctx.saved_tensors
-        xs, xdt, wdt, bdt, kind, p, seed, eps_ = ctx.meta
-        d_pre = _glu_backward(pre, d_act, kind, p, seed, sample_scale, eps_)
-        dx, dw, db = _linear_backward(x2, w, d_pre.view(-1, d_pre.shape[-1]), xs, xdt, wdt, bdt, ctx.needs_input_grad[0],
-                                      ctx.needs_input_grad[1], bdt is not None and ctx.needs_input_grad[2], dw_ptr=ctx.wptr, live=ctx.live)
-        return dx, dw, db, None, None, None, None, None
+        d_pre = _glu_backward(pre, d_act, ctx.kind, ctx.p, ctx.seed, sample_scale, ctx.eps_)
+        return _grads(_LINEAR_GLU_ARGS, *_linear_backward_db(ctx, x2, w, d_pre.view(-1, d_pre.shape[-1])))
+
+
+_LINEAR_GLU_ARGS = _forward_args(_LinearGluDropout, _XWB)
 
 
 def linear_glu_dropout_ok(x, weight, sample_scale=None):
     """whether linear_glu_dropout takes this call: edge rows (many of them), a 16-bit compute dtype, a (512, 256) weight"""
-    if not x.is_cuda:
-        return False
-    cd = _compute_dtype(x, on_cpu=True)
-    rows = x.numel() // x.shape[-1]
-    if sample_scale is not None and (rows % sample_scale.numel() or sample_scale.dtype != torch.float32):
-        return False
-    return tuple(weight.shape) == (512, 256) and _edge_kernel_ok(x.reshape(-1, x.shape[-1]), 512, cd, ks=(256,)) and \
-        edge_linear_supported(256, 512, cd, _lib.EPI_GLU, row_scale=sample_scale is not None)
+    return tuple(weight.shape) == (512, 256) and _linear_act_ok(x, weight, sample_scale, 512, (256,), _lib.EPI_GLU)
 
 
 def linear_glu_dropout(x, weight, bias, kind, p, training, sample_scale=None):
@@ -2339,14 +2381,18 @@ def linear_glu_dropout(x, weight, bias, kind, p, training, sample_scale=None):
     glu_dropout; see linear_glu_dropout_ok"""
     kind = _glu_kind(kind)
     cd = _compute_dtype(x, on_cpu=True)
-    p = float(p) if training else 0.0
-    seed = _host_seed() if p > 0 else 0
+    p, seed = draw_dropout(p, training)
     return _LinearGluDropout.apply(x, weight, bias, cd, kind, p, seed, sample_scale)
 
 
 # ---------------------------------------------------------------------------
 # residual entry of a pre-norm block: s = res + x*scale ; y = LN(s)   (one pass each way)
 # ---------------------------------------------------------------------------
+def _ln_unused_backward(ds, scale):
+    """(d_res, d_z) of s = res + scale z when nothing used the LayerNorm output: the stream gradient, and its per-sample multiple"""
+    return ds, ds if scale is None else ds * scale.view(-1, *([1] * (ds.ndim - 1))).to(ds.dtype)
+
+
 class _AddLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, scale, weight, bias, eps, out_dtype):
@@ -2363,27 +2409,28 @@ class _AddLayerNorm(torch.autograd.Function):
         _launch('tgt_add_layer_norm_fwd', _ptr(x), _DT[x.dtype], _ptr(res), _DT[res.dtype], _ptr(scale), rps, _ptr(s), _ptr(w), _ptr(b),
                 _ptr(y), _DT[out_dtype], _ptr(mean), _ptr(rstd), rows, C_, float(eps), prof='tgt_add_layer_norm_fwd')
         ctx.save_for_backward(s, w, mean, rstd, scale)
-        ctx.meta = (weight.dtype, res.dtype, rps)
+        ctx.wdt, ctx.rdt, ctx.rps = weight.dtype, res.dtype, rps
         ctx.live = _edge_live             # (the backward may run a Linear's data gradient fused with its own: a row kernel, _ln_backward)
         return s, y
 
     @staticmethod
     def backward(ctx, ds, dy):
         s, w, mean, rstd, scale = ctx.saved_tensors
-        wdt, rdt, rps = ctx.meta
-        C_ = s.shape[-1]
-        rows = s.numel() // C_
+        wdt, rdt = ctx.wdt, ctx.rdt
         if dy is None:                                  # the LN branch was not used
-            d_res = ds
-            d_x = ds if scale is None else ds * scale.view(-1, *([1] * (ds.ndim - 1))).to(ds.dtype)
-            return d_x, d_res.to(rdt), None, None, None, None, None
+            d_res, d_x = _ln_unused_backward(ds, scale)
+            return _grads(_ADD_LN_ARGS, d_x, d_res.to(rdt))
         # (column sums of d_x: the bias gradient of the Linear that produced x (lin_O / lin_W2 / lin_O_e), handed over on the
         # gradient tensor, see _hand_colsum)
-        d_res, d_x, dg, dbeta, cs = _ln_backward(dy, s, w, mean, rstd, ds, scale, rps, scale is not None, live=ctx.live)
+        d_res, d_x, dg, dbeta, cs = _ln_backward(dy, s, w, mean, rstd, ds, scale, ctx.rps, scale is not None, live=ctx.live)
         if d_x is None:
             d_x = d_res
         _hand_colsum(d_x, cs)
-        return d_x, (d_res if rdt == d_res.dtype else d_res.to(rdt)), None, _param_grad(dg, wdt), _param_grad(dbeta, wdt), None, None
+        return _grads(_ADD_LN_ARGS, d_x, d_res if rdt == d_res.dtype else d_res.to(rdt), weight=_param_grad(dg, wdt),
+                      bias=_param_grad(dbeta, wdt))
+
+
+_ADD_LN_ARGS = _forward_args(_AddLayerNorm)
 
 
 class _LinearResidualLN(torch.autograd.Function):
@@ -2397,18 +2444,12 @@ class _LinearResidualLN(torch.autograd.Function):
         # pre / gelu = (p, seed, sample_scale): x is dropout(gelu(pre)) * sample_scale, handed in DETACHED; this node then owns the
         # activation's derivative and returns the gradient of `pre` (GELU backward as the epilogue of the data-gradient GEMM)
         _dev(x, weight, res, ln_w, ln_b)
-        xs = x.shape
-        x2 = x.reshape(-1, xs[-1])
-        if x2.dtype != cd:
-            x2 = x2.to(cd)
-        if col_perm is not None:
-            # the weight's input columns in the order the producing kernel emits its channels (lin_O of the triplet modules:
-            # one launch, cast included); the weight gradient goes back through the inverse permutation
-            w = _permute_cols(_as_dtype_view(weight, cd).contiguous(), col_perm[0], cd)
-        else:
-            w = _as_dtype(weight, cd).contiguous()
+        ctx.lin = _LinearSaved.of(x, weight, bias)
+        xs = ctx.lin.xs
+        # col_perm: lin_O of the triplet modules (_permuted_weight; the weight gradient goes back through the inverse permutation)
+        x2, w, b = _linear_operands(x, weight if col_perm is None else _permuted_weight(weight, cd, col_perm[0]), bias, cd,
+                                    wb_contiguous=True)
         ctx.col_inv = None if col_perm is None else col_perm[1]
-        b = None if bias is None else _as_dtype(bias, cd).contiguous()
         N, rows = weight.shape[0], x2.shape[0]
         res2 = res.reshape(rows, N)
         if res2.dtype != cd:
@@ -2419,55 +2460,50 @@ class _LinearResidualLN(torch.autograd.Function):
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         rps = rows // xs[0]
-        ctx.live = _edge_live
         edge_linear_raw(x2, w, b, _lib.EPI_RESID, out=s.view(rows, N), res=res2, row_scale=scale, rows_per_sample=rps,
                         ln=(g, be, eps), stats=(mean, rstd), y=y.view(rows, N),
-                        flags=_lib.EDGE_BIAS_SCALED if (prescaled and scale is not None) else 0, live=ctx.live)
+                        flags=_lib.EDGE_BIAS_SCALED if (prescaled and scale is not None) else 0, live=ctx.lin.live)
         ctx.gelu = None
         if pre is not None:
             ctx.gelu = (float(gelu[0]), gelu[1], gelu[2] is not None)
             ctx.save_for_backward(x2, w, s, g, mean, rstd, scale, pre, gelu[2])
         else:
             ctx.save_for_backward(x2, w, s, g, mean, rstd, scale)
-        ctx.meta = (xs, x.dtype, weight.dtype, None if bias is None else bias.dtype, ln_w.dtype, res.dtype, rps)
+        ctx.lndt, ctx.rdt, ctx.rps = ln_w.dtype, res.dtype, rps
         ctx.prescaled = bool(prescaled and scale is not None)
-        ctx.wptr = weight.data_ptr()
         return s, y
 
     @staticmethod
     def backward(ctx, ds, dy):
         x2, w, s, g, mean, rstd, scale = ctx.saved_tensors[:7]
-        xs, xdt, wdt, bdt, lndt, rdt, rps = ctx.meta
+        lin, rdt, rps, need = ctx.lin, ctx.rdt, ctx.rps, ctx.needs_input_grad
+        wdt, live, need_dw = lin.wdt, lin.live, need[_LINEAR_RESIDUAL_LN_ARGS.index('weight')]
         N = s.shape[-1]
         rows = s.numel() // N
         pres = ctx.prescaled       # x arrived pre-scaled: the gradient of x W^T IS the stream gradient, only the bias carries the factor
         if dy is None:                                  # the LayerNorm branch was not used
-            d_res = ds
-            d_z = ds if (scale is None or pres) else ds * scale.view(-1, *([1] * (ds.ndim - 1))).to(ds.dtype)
+            d_res, d_z = _ln_unused_backward(ds, None if pres else scale)
             dg = dbeta = None
             cs = None
-            if pres and bdt is not None and ctx.needs_input_grad[2]:
+            if pres and lin.bdt is not None and need[_LINEAR_RESIDUAL_LN_ARGS.index('bias')]:
                 cs = (ds.reshape(scale.numel(), -1, N).float().sum(1) * scale.view(-1, 1)).sum(0)
         else:
-            d_res, d_z, dg, dbeta, cs = _ln_backward(dy, s, g, mean, rstd, ds, scale, rps, scale is not None and not pres, live=ctx.live)
+            d_res, d_z, dg, dbeta, cs = _ln_backward(dy, s, g, mean, rstd, ds, scale, rps, scale is not None and not pres, live=live)
             if d_z is None:
                 d_z = d_res
 
-        need_db = bdt is not None and ctx.needs_input_grad[2]
         d_pre = None
         fused_dw = None
-        need_dx = ctx.needs_input_grad[0]
         if ctx.gelu is not None:
             # d_pre = ((d_z W) * sample_scale) * gelu'(pre) * keep / (1 - p): the data gradient and the activation's backward in
             # one launch (TGT_EPI_GELU_BWD); x was handed in detached, its slot gets no gradient
             pre, g_scale = ctx.saved_tensors[7], (ctx.saved_tensors[8] if ctx.gelu[2] else None)
-            need_dx = False
-            if ctx.needs_input_grad[11]:
+            if need[_LINEAR_RESIDUAL_LN_ARGS.index('pre')]:
                 d_pre = torch.empty_like(pre)
                 # (256 outputs = the row-phase kernel: it also returns the column sums of d_pre, lin_W1's bias gradient)
                 # the weight gradient of THIS Linear rides on the same launch (TGT_EDGE_WGRAD): dW = d_z^T x with x = the activation
                 # recomputed from `pre` in the row phase -- neither d_z nor x is read again by a weight-gradient GEMM
-                fuse_dw = (_EDGE_WGRAD and ctx.needs_input_grad[1] and ctx.col_inv is None and N == 256 and pre.shape[-1] == 256 and
+                fuse_dw = (_EDGE_WGRAD and need_dw and ctx.col_inv is None and N == 256 and pre.shape[-1] == 256 and
                            x2.shape[1] == 256 and wdt == torch.float32)
                 parts = _lib.lib().tgt_edge_linear_parts(rows, 256)
                 if fuse_dw and parts > 2 * _EDGE_WGRAD_SPARE > 0:
@@ -2477,24 +2513,23 @@ class _LinearResidualLN(torch.autograd.Function):
                 dw_part = torch.empty(parts, 256, 256, dtype=torch.float32, device=pre.device) if fuse_dw else None
                 edge_linear_raw(d_z.reshape(rows, N), weight_t(w), None, _lib.EPI_GELU_BWD, out=d_pre.view(rows, -1),
                                 res=pre.view(rows, -1), out_scale=g_scale, rows_per_sample=rps, dropout=(ctx.gelu[0], ctx.gelu[1]),
-                                colsum_partial=part, dw_partial=dw_part, live=ctx.live)
+                                colsum_partial=part, dw_partial=dw_part, live=live)
                 if part is not None:
                     with _on_stream(_terminal_fork(rows, part)):
                         _hand_colsum(d_pre, sum_rows(part))
                 if dw_part is not None:
-                    dst = _grad_dst(ctx.wptr, (256, 256), torch.float32)
+                    dst = _grad_dst(lin.wptr, (256, 256), torch.float32)
                     with _on_stream(_terminal_fork(rows, dw_part)):
                         fused_dw = sum_planes(dw_part, dst if dst is not None else torch.empty(256, 256, dtype=torch.float32, device=pre.device))
-        dx, dw, db = _linear_backward(x2, w, d_z.reshape(rows, N), xs, xdt, torch.float32 if ctx.col_inv is not None else wdt, bdt,
-                                      need_dx, ctx.needs_input_grad[1] and fused_dw is None, need_db and cs is None,
-                                      dw_post=None if ctx.col_inv is None else (lambda t: _permute_cols(t.contiguous(), ctx.col_inv, wdt, after_sums=True)),
-                                      dw_ptr=ctx.wptr, live=ctx.live)
-        if need_db and cs is not None:
-            db = _param_grad(cs, bdt)
+        dx, dw, db = _linear_backward_db(ctx, x2, w, d_z.reshape(rows, N), cs, want_dx=ctx.gelu is None, want_dw=fused_dw is None,
+                                         **_permuted_weight_grad(ctx.col_inv, wdt))
         if fused_dw is not None:
             dw = fused_dw
-        return (dx, dw, db, d_res if rdt == d_res.dtype else d_res.to(rdt), None,
-                _param_grad(dg, lndt), _param_grad(dbeta, lndt), None, None, None, None, d_pre, None, None)
+        return _grads(_LINEAR_RESIDUAL_LN_ARGS, dx, dw, db, d_res if rdt == d_res.dtype else d_res.to(rdt),
+                      ln_w=_param_grad(dg, ctx.lndt), ln_b=_param_grad(dbeta, ctx.lndt), pre=d_pre)
+
+
+_LINEAR_RESIDUAL_LN_ARGS = _forward_args(_LinearResidualLN, _XWB)
 
 
 _GELU_BWD_EPI_COLSUM = K.gelu_bwd_epi_colsum      # A/B knob: lin_W1's bias gradient from the GELU_BWD epilogue
@@ -2748,8 +2783,11 @@ class _GaussianBasis(torch.autograd.Function):
         _launch('tgt_gaussian_basis_bwd', _ptr(xf), _ptr(mf), _ptr(bf), _ptr(mw), _ptr(sw), pairs, K, _DT[out_dtype], _ptr(g), _ptr(dt),
                 _ptr(partial))
         dms = sum_rows(partial, defer=False)          # (sliced and cast right below)
-        dx = (dt * mf).view(xs) if ctx.needs_input_grad[0] else None
+        dx = (dt * mf).view(xs) if ctx.needs_input_grad[_GAUSSIAN_BASIS_ARGS.index('x')] else None
         return dx, (dt * xf).view(ms), dt.view(bs), dms[:K].view(mws).to(pdt), dms[K:].view(sws).to(pdt), None
+
+
+_GAUSSIAN_BASIS_ARGS = _forward_args(_GaussianBasis)
 
 
 def gaussian_basis(x, mul, bias, means, stds):

@@ -29,11 +29,11 @@ def install(name):
     if name == 'skip_proj_ln':
         real = ops._ln_backward
 
-        def _ln_backward(dy, s, g, mean, rstd, ds, scale, rps, want_dz):
+        def _ln_backward(dy, s, g, mean, rstd, ds, scale, rps, want_dz, live=None):
             N = s.shape[-1]
             rows = s.numel() // N
             if rows < 65536 or ops._take_lazy_dgrad(dy) is not None:
-                return real(dy, s, g, mean, rstd, ds, scale, rps, want_dz)
+                return real(dy, s, g, mean, rstd, ds, scale, rps, want_dz, live=live)
             d_res = torch.empty_like(s)
             d_res.copy_(dy.view_as(d_res))                 # a plain copy (2 E) in place of the 4 E pass keeps the gradients finite
             zeros = torch.zeros(3 * N, dtype=torch.float32, device=s.device)
