@@ -43,7 +43,7 @@ enum {
     TGT_TRI_BIASED      = 1,   /* third-arm bias E present      */
     TGT_TRI_GATED       = 2,   /* third-arm sigmoid gate present */
     TGT_TRI_MASK_OUT    = 4,   /* aggregate only: mask the outward direction (ungated variant) */
-    TGT_TRI_NO_QKV_STORE = 8,  /* tgt_triplet_attention_proj_fwd only: do not write the projected Q/K/V rows (no backward follows) */
+    TGT_TRI_NO_QKV_STORE = 8,  /* tgt_triplet_attention_proj_fwd / _proj64_fwd: do not write the projected Q/K/V rows (no backward follows) */
     TGT_TRI_COUNTS_KB   = 16,  /* tgt_triplet_attention_fwd_counts / _bwd_counts only, N > 64, node_counts != NULL: the key-blocked kernels use the counts */
 };
 
@@ -568,16 +568,38 @@ int tgt_colsum(const void* x, int32_t x_dtype, int64_t rows, int32_t C, float* o
  *          the backward kernel); a->eg (E/G third arm) is still an input.
  *          With TGT_TRI_NO_QKV_STORE in a->flags (a forward that no backward follows: inference) nothing is written
  *          through a->qkv[dir]: the pointers may be NULL, ld_qkv is not read, and q_off/k_off/v_off only select the rows
- *          of w / bias.  `out` is bit-identical with and without the flag.  Every other entry point ignores the bit.
+ *          of w / bias.  `out` is bit-identical with and without the flag.  tgt_triplet_attention_proj64_fwd (below) REQUIRES
+ *          the bit; every other entry point ignores it.
  * Supported: N <= 32, D = 16, H % 8 == 0, bf16/fp16, C = 256
- * (tgt_triplet_attention_proj_supported() tells; otherwise project with a GEMM and call
- * tgt_triplet_attention_fwd). */
+ * (tgt_triplet_attention_proj_supported() tells; otherwise tgt_triplet_attention_proj64_fwd, below, where it applies, or
+ * project with a GEMM and call tgt_triplet_attention_fwd). */
 int tgt_triplet_attention_proj_supported(const tgt_triplet_attention_args* a, int32_t C);
 int tgt_triplet_attention_proj_fwd(const tgt_triplet_attention_args* a, const void* x, int32_t C, const void* w,
                                    const void* bias, void* stream);
 /* the same with per-graph node counts (see tgt_triplet_attention_fwd_counts): the projection waves skip the padded units too */
 int tgt_triplet_attention_proj_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x, int32_t C,
                                           const void* w, const void* bias, void* stream);
+
+/* The same forward for 33 <= N <= 64, inference only (csrc/triplet_attention_proj64.hip): x, w, bias, q_off/k_off/v_off, eg, mask
+ * and out mean what they mean for tgt_triplet_attention_proj_fwd with TGT_TRI_NO_QKV_STORE; the bit must be set -- there is no
+ * form that writes Q/K/V at these node counts (a training forward projects with a GEMM and calls tgt_triplet_attention_fwd) --
+ * and a->qkv is never dereferenced.  Every X row is projected once per shared node j and workgroup; keys k >= N of a partly filled
+ * key block get a weight of exactly 0; rows i >= N and anything outside `out` are never written.
+ * graph_scale: a graph whose factor is exactly 0 gets zeros in all its `out` rows, nothing of it is read.  _counts: the N <= 64
+ * contract of tgt_triplet_attention_fwd_counts (out[b, :, j, :] = 0 for j >= n, those units' X rows are not read, everything with
+ * j < n bit-identical to the call without counts; keys are not bounded by the count); node_counts == NULL is the entry point
+ * without _counts.
+ * Supported (tgt_triplet_attention_proj64_supported, host only, 1 / 0): C = 256, D = 16, H = 16, 33 <= N <= 64, bf16 / fp16,
+ * dropout_p == 0, TGT_TRI_NO_QKV_STORE set; gated (BIASED | GATED), ungated (BIASED) and axial (neither, no eg) -- disjoint from
+ * tgt_triplet_attention_proj_supported, which stays 0 above 32 nodes.  Checks before any launch, in this order: null args
+ * (TGT_ERR_INVALID), sizes (TGT_ERR_INVALID), the predicate (TGT_ERR_UNSUPPORTED), B == 0 (TGT_OK), null / misaligned x / w /
+ * bias / mask / out and eg missing with a third-arm flag set (TGT_ERR_INVALID), graph_scale not 4-byte aligned
+ * (TGT_ERR_INVALID).  Nothing is read on the host: capturable. */
+int tgt_triplet_attention_proj64_supported(const tgt_triplet_attention_args* a, int32_t C);
+int tgt_triplet_attention_proj64_fwd(const tgt_triplet_attention_args* a, const void* x, int32_t C, const void* w,
+                                     const void* bias, void* stream);
+int tgt_triplet_attention_proj64_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x,
+                                            int32_t C, const void* w, const void* bias, void* stream);
 
 /* Kernel-order parameters of a triplet module in one launch.  The reference holds the
  * projections as separate nn.Linear with head-minor channels (lib/tgt/layers/triplet.py:198-203,

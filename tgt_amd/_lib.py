@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, 'libtgt_hip.so')
 LIB_OVERRIDE = os.environ.get('TGT_HIP_LIB')
 CSRC = os.path.join(_HERE, 'csrc')
 # (source, extra flags, object suffix): the triplet attention kernels compile one dtype per translation unit
-SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_live.hip', 'edge_wgrad.hip', 'params.hip', 'loss.hip', 'predict.hip', 'gaussian.hip', 'triplet_attention_proj.hip',
+SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_live.hip', 'edge_wgrad.hip', 'params.hip', 'loss.hip', 'predict.hip', 'gaussian.hip', 'triplet_attention_proj.hip', 'triplet_attention_proj64.hip',
            ('triplet_attention.hip', ['-DTGT_TRI_INST=9'], '.f32'), ('triplet_attention.hip', ['-DTGT_TRI_INST=2'], '.bf16'),
            ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip', 'triplet_attention_bwd2.hip',
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=9'], '.f32'), ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=2'], '.bf16'),
@@ -31,7 +31,7 @@ TGT_F32, TGT_BF16, TGT_F16 = 0, 1, 2
 TRI_BIASED, TRI_GATED, TRI_MASK_OUT = 1, 2, 4
 # tgt_node_attention_family(): the kernel family behind tgt_node_attention_fwd / _bwd for a call
 NODE_FAMILY_NONE, NODE_FAMILY_LANE, NODE_FAMILY_MFMA32, NODE_FAMILY_TILES16, NODE_FAMILY_KB_FWD, NODE_FAMILY_KB_BWD = range(6)
-TRI_NO_QKV_STORE = 8              # tgt_triplet_attention_proj_fwd only: the projected Q/K/V rows are not written
+TRI_NO_QKV_STORE = 8              # tgt_triplet_attention_proj_fwd / _proj64_fwd: the projected Q/K/V rows are not written
 TRI_COUNTS_KB = 16                # tgt_triplet_attention_fwd_counts / _bwd_counts only: the kernels for N > 64 use the node counts
 
 _i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -126,6 +126,9 @@ SYMBOLS = {
     'tgt_triplet_attention_workspace_bytes': (_i64, [C.POINTER(TripletAttentionArgs), _i32]),
     'tgt_triplet_attention_proj_supported': (C.c_int, [C.POINTER(TripletAttentionArgs), _i32]),
     'tgt_triplet_attention_proj_fwd': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _i32, _vp, _vp, _vp]),
+    'tgt_triplet_attention_proj64_supported': (C.c_int, [C.POINTER(TripletAttentionArgs), _i32]),
+    'tgt_triplet_attention_proj64_fwd': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _i32, _vp, _vp, _vp]),
+    'tgt_triplet_attention_proj64_fwd_counts': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _vp, _i32, _vp, _vp, _vp]),
     'tgt_triplet_aggregate_fwd': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp]),
     'tgt_triplet_aggregate_bwd': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp]),
     'tgt_triplet_aggregate_proj_supported': (C.c_int, [C.POINTER(TripletAggregateArgs), _i32]),

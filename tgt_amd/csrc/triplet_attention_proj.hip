@@ -31,23 +31,16 @@
 
 namespace tgt {
 
-__device__ __forceinline__ f32x4 mma16x32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 mma16x32(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-
 namespace proj2 {
-constexpr int kC = 256, kKS = 16, kRowBytes = kC * 2, kSlots = kRowBytes / 16;      // an X row: 512 bytes = 32 slots of 16
-constexpr int kXPitch = kRowBytes + 16;                                             // LDS pitch of an X row: 16 bytes of padding
+constexpr int kC = xtile::kC, kKS = 16, kRowBytes = xtile::kRowBytes, kSlots = kRowBytes / 16;   // an X row: 512 bytes = 32 slots of 16
+constexpr int kXPitch = xtile::kPitch;                                              // LDS pitch of an X row (triplet_common.hpp, xtile)
 constexpr int kXTile = 64 * kXPitch;                                                // 33 KB (inward: 64 rows; outward uses 32)
 constexpr int kSlab = 32 * 8 * 16 * 2;                                              // 32 rows x (8 heads x 16 d) x 2 B = 8 KB
 constexpr int kOffSets = 2 * kXTile, kSet = 3 * kSlab;                              // {Q | K | V} x 2
 constexpr int kOffO = kOffSets + 2 * kSet, kOffBias = kOffO + 2 * kSlab;            // O slabs x 2, then the bias floats
 constexpr int kLds = kOffBias + 8 * 48 * 4;
 constexpr uint32_t kNone = 0xffffffffu;
-// Rows PADDED by one 16-byte slot instead of XOR-swizzled: the 16 rows a ds_read_b128 lane group touches land in 16 different
-// bank slots (pitch 528 = 33 slots), and a fragment address is  lane base + k-step x constant  -- the k-loop's reads take
-// immediate offsets.  (With the XOR form every k-step needs its own address register or three VALU instructions; hipcc chose
-// the registers, hoisted them out of the walk and spilled them next to the resident weights.)
-__device__ __forceinline__ int xoff(int row, int slot) { return row * kXPitch + (slot << 4); }
+__device__ __forceinline__ int xoff(int row, int slot) { return xtile::off(row, slot); }
 }  // namespace proj2
 
 // zeros to the O rows of the units j0 .. N-1 of this head group (threads 512-1023, the chunk map of store_step; the others go out

@@ -77,6 +77,22 @@ __device__ __forceinline__ void slab_colsum_finish(const float* cs, float* out, 
 //   voffset (vector)  = row*row_stride + slot*16                        -- fixed per thread
 // so the walk over j issues buffer_load/store ... s[rsrc], s_off offen with no vector address math.
 // ---------------------------------------------------------------------------
+// 16 x 16 matrix-core tile with 32-deep k (the projection-fused kernels): lane l = (x = l & 15, g = l >> 4) supplies
+// A[m = x][kk = 8g + t] / B[kk = 8g + t][n = x], t = 0..7, and holds C[m = 4g + q][n = x], q = 0..3
+__device__ __forceinline__ f32x4 mma16x32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mma16x32(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+
+// LDS image of a tile of LayerNorm'd edge rows X (C = 256, 16-bit: 512 bytes = 32 slots of 16) that a projection-fused kernel
+// reads as matrix-core operand fragments.  Rows PADDED by one 16-byte slot instead of XOR-swizzled: the 16 rows a ds_read_b128
+// lane group touches land in 16 different bank slots (pitch 528 = 33 slots), and a fragment address is
+// lane base + k-step x constant -- the k-loop's reads take immediate offsets.  (With the XOR form every k-step needs its own
+// address register or three VALU instructions; hipcc chose the registers, hoisted them out of the walk and spilled them next to
+// the resident weights.)
+namespace xtile {
+constexpr int kC = 256, kRowBytes = kC * 2, kPitch = kRowBytes + 16;
+__device__ __forceinline__ int off(int row, int slot) { return row * kPitch + (slot << 4); }
+}  // namespace xtile
+
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 struct SlabBuf {
     __amdgpu_buffer_rsrc_t rsrc;

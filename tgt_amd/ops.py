@@ -27,6 +27,7 @@ _PROFILE = None
 _TRI_SPLIT = K.tri_split        # A/B knobs: tgt_amd/knobs.py reads the environment once; tests patch these names
 _TRI_PROJ = K.tri_proj
 _TRI_PROJ_INFER = K.tri_proj_infer
+_TRI_PROJ64_INFER = K.tri_proj64_infer
 _AGG_PROJ_INFER = K.agg_proj_infer
 _AGG_PROJ64_INFER = K.agg_proj64_infer
 _TRI_COLSUM = K.tri_colsum
@@ -673,6 +674,15 @@ def _proj_fused_ok(x, N, L, cd):
             cd in (torch.bfloat16, torch.float16) and L.C == 256 and x.numel() // L.C >= _SPLIT_MIN_ROWS)
 
 
+def _proj64_fused_ok(x, N, L, cd):
+    """the projection-fused inference forward for 33..64 nodes (tgt_triplet_attention_proj64_fwd): the kernel's
+    shape limits (tgt_triplet_attention_proj64_supported, less the flag and the dropout the caller decides), an unpadded fused row
+    and enough edge rows (the gate of _proj_fused_ok).  It exists without the Q/K/V store only: a call a backward follows never
+    gets here"""
+    return (33 <= N <= 64 and L.D == 16 and L.H == 16 and L.width == L.used and
+            cd in (torch.bfloat16, torch.float16) and L.C == 256 and x.numel() // L.C >= _SPLIT_MIN_ROWS)
+
+
 # A/B knob (round 5, VERDICT r4 item 3): keep the node side stream's backward chain of a layer off the HBM-bound triplet backward
 # kernel of that layer.  The host enqueues a layer's node-FFN backward AFTER the layer's triplet backward (lower sequence numbers),
 # but on the GPU the chain starts as soon as dh arrives from the layer above -- i.e. under the edge FFN's backward and, with its
@@ -715,7 +725,10 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         out = torch.empty(B, N, N, 2 * L.C, dtype=cd, device=x.device)
         eg = None
         projection_fused = False
-        if x.numel() // L.C >= _SPLIT_MIN_ROWS and not (dropout[0] == 0 and _proj_fused_ok(x, N, L, cd)) and _TRI_PROJ:
+        # 33..64 nodes, no backward: Q/K/V projected inside tgt_triplet_attention_proj64_fwd and never written (TGT_TRI_PROJ64_INFER=0
+        # is the A/B knob: the library GEMMs + tri_att16_fwd_kernel below)
+        infer64 = bool(no_backward and dropout[0] == 0 and _TRI_PROJ and _TRI_PROJ64_INFER and _proj64_fused_ok(x, N, L, cd))
+        if x.numel() // L.C >= _SPLIT_MIN_ROWS and not (dropout[0] == 0 and _proj_fused_ok(x, N, L, cd)) and _TRI_PROJ and not infer64:
             why = ('N > 64' if N > 64 else 'N > 32' if N > 32 else 'attention dropout > 0' if dropout[0] else 'head dim != 16' if L.D != 16 else
                    'heads not a multiple of 8' if L.H % 8 else 'edge width != 256' if L.C != 256 else
                    'fp32' if cd not in (torch.bfloat16, torch.float16) else 'padded / unbiased layout')
@@ -749,6 +762,17 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             if infer:
                 return out                 # (nothing to save: no backward exists)
             projection_fused = True        # (dropped graphs have NO Q/K/V rows: the backward must skip them too)
+        elif infer64:
+            x2, w, b = _linear_operands(x, weight, bias, cd, x_contiguous=True, wb_contiguous=True)
+            if L.biased:                       # (axial: no third arm)
+                eg = _narrow_linear(x2, w[6 * L.C:L.used], b[6 * L.C:L.used], cd).view(B, N, N, L.used - 6 * L.C)
+            a = _tri_args(None, mask3, out, L, eg=eg, graph_scale=graph_scale)
+            if node_counts is None:
+                _launch('tgt_triplet_attention_proj64_fwd', C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), prof='tgt_triplet_attention_proj64_fwd')
+            else:
+                _launch('tgt_triplet_attention_proj64_fwd_counts', C.byref(a), _ptr(node_counts), _ptr(x2), L.C, _ptr(w), _ptr(b),
+                        prof='tgt_triplet_attention_proj64_fwd')
+            return out                     # (nothing to save: no backward exists)
         elif _split_projection_ok(x, L):
             # two GEMMs: Q/K/V (6C = 1536 channels: six full 256-wide tile columns, 294 us) and the
             # narrow E/G (39 us) instead of one ragged 1600-wide GEMM (376 us; tools/gemm_probe.py);
@@ -827,7 +851,9 @@ def projected_triplet_attention(x, weight, bias, mask3, layout, table=None, drop
     projection produced inside the backward kernel.  weight/bias: the fused (layout.width, C)
     projection in kernel order (see TripletLayout) -- or, with a ParamTable, `weight` is the
     tuple of the module's nn.Linear parameters (w0, b0, w1, b1, ...) and bias is None.  node_counts: as triplet_attention; in
-    the projection-fused forward the padded columns are not projected either.  N > 64 (library GEMMs + the key-blocked kernels):
+    the projection-fused forward the padded columns are not projected either.  A call no backward can follow takes, at N <= 32, that
+    forward without its Q/K/V stores (TGT_TRI_PROJ_INFER) and, at 33 <= N <= 64 where _proj64_fused_ok holds,
+    tgt_triplet_attention_proj64_fwd (TGT_TRI_PROJ64_INFER): no Q/K/V tensor exists.  N > 64 (library GEMMs + the key-blocked kernels):
     the counts are used with TGT_TRI_RAGGED_KB=1 only, as in triplet_attention."""
     if not _TRI_COLSUM and table is None:      # A/B knob: separate bias-gradient pass
         return triplet_attention(linear(x, weight, bias), mask3, layout, dropout, graph_scale, node_counts)

@@ -10,7 +10,8 @@ on one MI355X.  One JSON line per configuration.
 
 python tools/infer_bench.py [--samples 4] [--batch 512] [--steps 3] [--nodes 32]
 (--nodes: the padded node count of cfg5's batch; above 32 the aggregate forward is tgt_triplet_aggregate_proj64_fwd,
-TGT_AGG_PROJ64_INFER=0 is the A/B knob and `knobs` in the line says which side ran)
+TGT_AGG_PROJ64_INFER=0 is the A/B knob and `knobs` in the line says which side ran.  --only tgt_at honours --nodes and --batch
+too: above 32 nodes its triplet forward is tgt_triplet_attention_proj64_fwd, TGT_TRI_PROJ64_INFER=0 is the A/B knob)
 """
 import argparse
 import json
@@ -115,10 +116,12 @@ def main():
         # (TGT_TRI_PROJ_INFER=0 is the A/B knob; `knobs` in the line says which side ran)
         from tgt_amd.knobs import K
         from tgt_amd.pcqm import TGT_Multi
-        B = min(a.batch, 256)
+        # --nodes / --batch: the padded node count and the graphs of the batch (--batch is capped at 256, the benchmark's batch).  33..64
+        # nodes: the forward is tgt_triplet_attention_proj64_fwd; TGT_TRI_PROJ64_INFER=0 (GEMMs + tgt_triplet_attention_fwd) is the A/B knob
+        B, Nn = min(a.batch, 256), a.nodes
         model = TGT_Multi(**configs.tgt_at_24l(dropouts=False)).cuda().eval()
-        batch = device_batch(B, 32, 13, ragged=False)
-        prof = ops.profile_kernels(True, only=('tgt_triplet_attention_proj_fwd',), stride=3)
+        batch = device_batch(B, Nn, 13, ragged=False)
+        prof = ops.profile_kernels(True, only=('tgt_triplet_attention_proj_fwd', 'tgt_triplet_attention_proj64_fwd', 'tgt_triplet_attention_fwd'), stride=3)
 
         def fwd_at():
             with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16):
@@ -126,9 +129,9 @@ def main():
         dt = timed(fwd_at, 3, max(a.steps, 10))
         ops.profile_kernels(False)
         kt = {k: round(sum(v) / len(v), 4) for k, v in ops.kernel_times_ms(prof).items()}
-        print(json.dumps(dict(metric='graphs/sec forward, TGT-At 24L, bf16, batch 256, N = 32, no autograd', value=round(B / dt, 1),
+        print(json.dumps(dict(metric=f'graphs/sec forward, TGT-At 24L, bf16, batch {B}, N = {Nn}, no autograd', value=round(B / dt, 1),
                               unit='graphs/s', ms_per_forward=round(dt * 1e3, 3), dtype='bf16', n_gpus=1, data='synthetic',
-                              launch='eager', kernel_ms=kt, knobs=K.non_default())), flush=True)
+                              launch='eager', kernel_ms=kt, batch=B, nodes=Nn, knobs=K.non_default())), flush=True)
 
 
 if __name__ == '__main__':
