@@ -582,8 +582,9 @@ int tgt_triplet_attention_proj_fwd_counts(const tgt_triplet_attention_args* a, c
 
 /* The same forward for 33 <= N <= 64, inference only (csrc/triplet_attention_proj64.hip): x, w, bias, q_off/k_off/v_off, eg, mask
  * and out mean what they mean for tgt_triplet_attention_proj_fwd with TGT_TRI_NO_QKV_STORE; the bit must be set -- there is no
- * form that writes Q/K/V at these node counts (a training forward projects with a GEMM and calls tgt_triplet_attention_fwd) --
- * and a->qkv is never dereferenced.  Every X row is projected once per shared node j and workgroup; keys k >= N of a partly filled
+ * form that writes Q/K/V at these node counts behind THESE entry points (the form that does is
+ * tgt_triplet_attention_proj64_train_fwd, below; without it a training forward projects with a GEMM and calls
+ * tgt_triplet_attention_fwd) -- and a->qkv is never dereferenced.  Every X row is projected once per shared node j and workgroup; keys k >= N of a partly filled
  * key block get a weight of exactly 0; rows i >= N and anything outside `out` are never written.
  * graph_scale: a graph whose factor is exactly 0 gets zeros in all its `out` rows, nothing of it is read.  _counts: the N <= 64
  * contract of tgt_triplet_attention_fwd_counts (out[b, :, j, :] = 0 for j >= n, those units' X rows are not read, everything with
@@ -600,6 +601,26 @@ int tgt_triplet_attention_proj64_fwd(const tgt_triplet_attention_args* a, const 
                                      const void* bias, void* stream);
 int tgt_triplet_attention_proj64_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x,
                                             int32_t C, const void* w, const void* bias, void* stream);
+
+/* The TRAINING form of the forward above (33 <= N <= 64; the same file, a translation unit of its own): same arguments, same walk,
+ * same arithmetic, and every projected Q, K and V value is written once through a->qkv[dir] -- row pitch ld_qkv[dir], columns
+ * q_off / k_off / v_off[dir] + h*D + d, the layout tgt_triplet_attention_bwd reads and tgt_triplet_attention_proj_fwd writes at
+ * N <= 32.  The stored values are the rounded values the kernel itself consumes: `out` is bit-identical to
+ * tgt_triplet_attention_proj64_fwd's on the same inputs.  Rows i >= N / k >= N and anything outside `qkv` and `out` are never
+ * written.  graph_scale: a graph whose factor is exactly 0 gets zeros in `out` and NO Q/K/V row (the backward must be given the
+ * factors too).  _counts: the N <= 64 contract of tgt_triplet_attention_fwd_counts; the Q/K/V rows of the units j >= n -- rows
+ * [:, j] (Q; K / V outward) and [j, :] (K / V inward) -- are neither projected nor written and keep what the buffer held,
+ * everything with j < n is bit-identical to the call without counts.
+ * Supported (tgt_triplet_attention_proj64_train_supported, host only, 1 / 0): C = 256, D = 16, H = 16, 33 <= N <= 64, bf16 / fp16,
+ * dropout_p == 0, TGT_TRI_NO_QKV_STORE CLEAR.  Checks before any launch, in this order: null args, sizes (TGT_ERR_INVALID), the
+ * predicate (TGT_ERR_UNSUPPORTED), B == 0 (TGT_OK), everything tgt_triplet_attention_proj64_fwd checks, then qkv[0] / qkv[1]
+ * null, rows or offsets not 16-byte aligned or outside a row of ld_qkv, a graph of 2 GB or more (TGT_ERR_INVALID).  Nothing is
+ * read on the host: capturable. */
+int tgt_triplet_attention_proj64_train_supported(const tgt_triplet_attention_args* a, int32_t C);
+int tgt_triplet_attention_proj64_train_fwd(const tgt_triplet_attention_args* a, const void* x, int32_t C, const void* w,
+                                           const void* bias, void* stream);
+int tgt_triplet_attention_proj64_train_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x,
+                                                  int32_t C, const void* w, const void* bias, void* stream);
 
 /* Kernel-order parameters of a triplet module in one launch.  The reference holds the
  * projections as separate nn.Linear with head-minor channels (lib/tgt/layers/triplet.py:198-203,

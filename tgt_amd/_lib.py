@@ -18,6 +18,7 @@ LIB_OVERRIDE = os.environ.get('TGT_HIP_LIB')
 CSRC = os.path.join(_HERE, 'csrc')
 # (source, extra flags, object suffix): the triplet attention kernels compile one dtype per translation unit
 SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_live.hip', 'edge_wgrad.hip', 'params.hip', 'loss.hip', 'predict.hip', 'gaussian.hip', 'triplet_attention_proj.hip', 'triplet_attention_proj64.hip',
+           ('triplet_attention_proj64.hip', ['-DTGT_TRI_PROJ64_INST=2'], '.train'),      # (the storing form: a unit of its own)
            ('triplet_attention.hip', ['-DTGT_TRI_INST=9'], '.f32'), ('triplet_attention.hip', ['-DTGT_TRI_INST=2'], '.bf16'),
            ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip', 'triplet_attention_bwd2.hip',
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=9'], '.f32'), ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=2'], '.bf16'),
@@ -129,6 +130,9 @@ SYMBOLS = {
     'tgt_triplet_attention_proj64_supported': (C.c_int, [C.POINTER(TripletAttentionArgs), _i32]),
     'tgt_triplet_attention_proj64_fwd': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _i32, _vp, _vp, _vp]),
     'tgt_triplet_attention_proj64_fwd_counts': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _vp, _i32, _vp, _vp, _vp]),
+    'tgt_triplet_attention_proj64_train_supported': (C.c_int, [C.POINTER(TripletAttentionArgs), _i32]),
+    'tgt_triplet_attention_proj64_train_fwd': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _i32, _vp, _vp, _vp]),
+    'tgt_triplet_attention_proj64_train_fwd_counts': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _vp, _i32, _vp, _vp, _vp]),
     'tgt_triplet_aggregate_fwd': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp]),
     'tgt_triplet_aggregate_bwd': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp]),
     'tgt_triplet_aggregate_proj_supported': (C.c_int, [C.POINTER(TripletAggregateArgs), _i32]),

@@ -54,6 +54,9 @@ int triplet_attention_proj_run(const tgt_triplet_attention_args* a, const int32_
 int triplet_attention_proj64_supported(const tgt_triplet_attention_args* a, int C);
 int triplet_attention_proj64_run(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x, int C, const void* w,
                                  const void* bias, hipStream_t st);
+int triplet_attention_proj64_train_supported(const tgt_triplet_attention_args* a, int C);
+int triplet_attention_proj64_train_run(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x, int C, const void* w,
+                                       const void* bias, hipStream_t st);
 int triplet_aggregate_proj_supported(const tgt_triplet_aggregate_args* a, int C);
 int triplet_aggregate_proj_run(const tgt_triplet_aggregate_args* a, const float* graph_scale, const void* x, int C, const void* w,
                                const void* bias, hipStream_t st);
@@ -212,6 +215,17 @@ int tgt_triplet_attention_proj64_fwd(const tgt_triplet_attention_args* a, const 
 int tgt_triplet_attention_proj64_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x, int32_t C,
                                             const void* w, const void* bias, void* stream) {
     return triplet_attention_proj64_run(a, node_counts, x, C, w, bias, reinterpret_cast<hipStream_t>(stream));
+}
+int tgt_triplet_attention_proj64_train_supported(const tgt_triplet_attention_args* a, int32_t C) {
+    return triplet_attention_proj64_train_supported(a, C);
+}
+int tgt_triplet_attention_proj64_train_fwd(const tgt_triplet_attention_args* a, const void* x, int32_t C, const void* w, const void* bias,
+                                           void* stream) {
+    return tgt_triplet_attention_proj64_train_fwd_counts(a, nullptr, x, C, w, bias, stream);
+}
+int tgt_triplet_attention_proj64_train_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, const void* x, int32_t C,
+                                                  const void* w, const void* bias, void* stream) {
+    return triplet_attention_proj64_train_run(a, node_counts, x, C, w, bias, reinterpret_cast<hipStream_t>(stream));
 }
 int tgt_triplet_aggregate_proj_supported(const tgt_triplet_aggregate_args* a, int32_t C) { return triplet_aggregate_proj_supported(a, C); }
 int tgt_triplet_aggregate_proj_fwd(const tgt_triplet_aggregate_args* a, const void* x, int32_t C, const void* w, const void* b,

@@ -26,8 +26,21 @@
 //   their WEIGHT is exactly 0 (a logit of -inf and a gate of 0, as tri_att16_fwd_kernel); key blocks wholly past N are skipped.
 // Supported: C = 256, D = 16, H = 16, 33 <= N <= 64, 16-bit dtypes, gated / ungated / axial, no attention dropout,
 // TGT_TRI_NO_QKV_STORE set (a->qkv is never dereferenced).
+//
+// The TRAINING form (TGT_TRI_PROJ64_INST == 2, a translation unit of its own so that the kernels above keep
+// the instruction streams they were measured with): the same walk with STORE = true.  Phase A additionally puts the packed Q, K
+// and V values it consumes into three 64-row slabs next to the O slab -- Q and K as the 8 bytes per lane of the O-slab write, V
+// (lane column = d, four keys per lane) element by element, which is its transpose -- and after barrier 1 they leave as whole
+// 128-byte row pieces through slab_store into a->qkv[dir], the layout tri_att16_bwd_kernel reads.  The slabs are written before
+// B1_j, read by the stores between B1_j and B2_j and written again after B2_j: no third barrier.  Over the walk every row is
+// projected once (inward: Q of (i, j), K / V of (j, k); outward: all three of (t, j)), so no element has two writers; rows >= N,
+// a dropped graph's rows and the units j >= n of a ragged graph are never written.
 #include "node_tiles16.hpp"
 #include "triplet_common.hpp"
+
+#ifndef TGT_TRI_PROJ64_INST
+#define TGT_TRI_PROJ64_INST 1      // 1: the inference kernels and their entry; 2: the training (storing) kernels and theirs
+#endif
 
 namespace tgt {
 
@@ -42,6 +55,7 @@ constexpr int kXTile = 2 * kRows * xtile::kPitch;            // inward: rows (i,
 constexpr int kKvx = kHG * 4 * 2 * 512;                      // exchange area: [head][key block][K | V] x (64 lanes x 8 bytes)
 constexpr int kOSlab = kRows * kHG * kD * 2;
 constexpr int kOffKvx = kXTile, kOffO = kOffKvx + kKvx, kWalk = kOffO + kOSlab;
+constexpr int kOffQkv = kWalk, kWalkStore = kOffQkv + 3 * kOSlab;           // training form: the Q | K | V row slabs behind the O slab
 constexpr uint32_t kNone = 0xffffffffu;
 // the 4-head slab geometry of triplet_common.hpp, walked by this kernel's 512 threads
 template <typename T>
@@ -113,7 +127,7 @@ __device__ __forceinline__ void arm_stage_load2(const ThirdArm& ta, int b, int g
 }
 }  // namespace proj64
 
-template <typename T, int DIR, bool RG>
+template <typename T, int DIR, bool RG, bool STORE = false>
 __device__ __forceinline__ void proj64_walk(const tgt_triplet_attention_args& a, const int32_t* node_counts, const TriCtx& c, const T* x,
                                             const T* w, const T* bias, char* smem, int tid) {
     using namespace proj64;
@@ -199,6 +213,15 @@ __device__ __forceinline__ void proj64_walk(const tgt_triplet_attention_args& a,
 
     char* kvx = smem + kOffKvx + hw * (4 * 2 * 512) + lane * 8;              // this lane's 8 bytes of [key block][K | V] of its head
     char* sO = smem + kOffO;
+    // STORE: the Q / K / V rows of step j, as rows of this head group's 64 channels (the O slab's geometry).  Q rows are the
+    // edges (i, j); K / V rows the edges (j, k) inward, (k, j) outward
+    auto qkv_slab = [&](int part) {
+        const uint32_t ldq = (uint32_t)(a.ld_qkv[DIR] * sz);
+        const int off = part == 0 ? a.q_off[DIR] : part == 1 ? a.k_off[DIR] : a.v_off[DIR];
+        const bool rows_ij = part == 0 || DIR == 1;
+        return SlabBuf{graph_rsrc(a.qkv[DIR], Nl * Nl * a.ld_qkv[DIR] * sz, c.b), (uint32_t)((off + c.g * kHG * kD) * sz),
+                       rows_ij ? (uint32_t)N * ldq : ldq, rows_ij ? ldq : (uint32_t)N * ldq};
+    };
     const int nblk = (N + 15) >> 4;                                         // blocks of 16 rows that hold a real node (3 or 4)
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 
@@ -247,6 +270,26 @@ __device__ __forceinline__ void proj64_walk(const tgt_triplet_attention_args& a,
                 __builtin_memcpy(&r1, &fv, 8);
                 *reinterpret_cast<uint2*>(kvx + (blk * 2 + 0) * 512) = r0;
                 *reinterpret_cast<uint2*>(kvx + (blk * 2 + 1) * 512) = r1;
+                if constexpr (STORE) {
+                    // the packed values themselves.  Q^T, K^T: lane (row x16, g) holds channels 4g .. 4g+3 of its row, 8 bytes;
+                    // V: lane (d = x16, g) holds keys 4g .. 4g+3 of the block, one element each into their rows
+                    // (the slab offsets are rebuilt from an opaque copy of the lane index: hoisted out of the walk they would live
+                    // next to the resident weights and the third arm, and the register file is full)
+                    int l_ = lane;
+                    asm volatile("" : "+v"(l_));
+                    const int x16 = l_ & 15, g = l_ >> 4;
+                    char* sQkv = smem + kOffQkv;
+                    uint2 rq;
+                    __builtin_memcpy(&rq, &fq[bl], 8);
+                    const int o8 = G::lds_elem(16 * blk + x16, hw * kD + 4 * g);
+                    *reinterpret_cast<uint2*>(sQkv + o8) = rq;
+                    *reinterpret_cast<uint2*>(sQkv + kOSlab + o8) = r0;
+                    uint16_t tv[4];
+                    __builtin_memcpy(tv, &r1, 8);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        *reinterpret_cast<uint16_t*>(sQkv + 2 * kOSlab + G::lds_elem(16 * blk + 4 * g + q, hw * kD + x16)) = tv[q];
+                }
             } else {
                 fq[bl] = pack4<T>(z);
             }
@@ -255,6 +298,15 @@ __device__ __forceinline__ void proj64_walk(const tgt_triplet_attention_args& a,
         x_commit();                                                         // X tile of step j + 1
         x_issue(j + 2);                                                     // (a whole step ahead of its commit; j + 2 >= n: nothing is read)
         asm volatile("" ::: "memory");
+        if constexpr (STORE) {
+            // the Q / K / V rows of step j (written before B1, not rewritten before B2); rows >= N are not stored.  Behind the X
+            // loads of step j + 2, so that the loads are not queued behind 24 KB of stores
+            int t_ = tid;
+            asm volatile("" : "+v"(t_));
+#pragma unroll
+            for (int part = 0; part < 3; ++part) slab_store<G, kRows>(smem + kOffQkv + part * kOSlab, qkv_slab(part), j, 0, N, t_);
+            asm volatile("" ::: "memory");
+        }
         // ---- phase B
 #pragma unroll
         for (int bl = 0; bl < 2; ++bl) {
@@ -323,6 +375,20 @@ __device__ __forceinline__ void proj64_walk(const tgt_triplet_attention_args& a,
     }
 }
 
+// what both entry points ask of the tensors every form reads or writes, after their predicate and the empty batch
+static int proj64_check_tensors(const tgt_triplet_attention_args* a, const void* x, const void* w, const void* bias) {
+    if (!x || !w || !bias || !a->mask || !a->out)                           // (a->qkv: the training entry's own check)
+        return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes): null tensor");
+    if ((a->flags & (TGT_TRI_BIASED | TGT_TRI_GATED)) && (!a->eg[0] || !a->eg[1]))
+        return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes): eg missing");
+    if ((a->ld_out * 2) % 16 || (a->o_off[0] * 2) % 16 || (a->o_off[1] * 2) % 16 || ((uintptr_t)a->out % 16) ||
+        (((uintptr_t)x | (uintptr_t)w) % 16) || ((uintptr_t)bias % 2) || ((uintptr_t)a->mask % 4))
+        return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes): x / w / out rows and offsets must be 16-byte aligned");
+    if ((uintptr_t)a->graph_scale % 4) return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes): graph_scale must be 4-byte aligned");
+    return TGT_OK;
+}
+
+#if TGT_TRI_PROJ64_INST == 1
 template <typename T, typename... NC>
 __global__ void __launch_bounds__(proj64::kThreads, 2) tri_att_proj64_fwd_kernel(const tgt_triplet_attention_args a, const T* x, const T* w,
                                                                                  const T* bias, NC... nc) {
@@ -368,15 +434,70 @@ int triplet_attention_proj64_run(const tgt_triplet_attention_args* a, const int3
                          "dropout and TGT_TRI_NO_QKV_STORE set: it has no form that writes Q/K/V (got N=%d D=%d H=%d dtype=%d C=%d flags=%d dropout_p=%g)",
                          a->N, a->D, a->H, a->dtype, C, a->flags, (double)a->dropout_p);
     if (a->B == 0) return TGT_OK;
-    if (!x || !w || !bias || !a->mask || !a->out)                           // (a->qkv is never examined)
-        return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes): null tensor");
-    if ((a->flags & (TGT_TRI_BIASED | TGT_TRI_GATED)) && (!a->eg[0] || !a->eg[1]))
-        return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes): eg missing");
-    if ((a->ld_out * 2) % 16 || (a->o_off[0] * 2) % 16 || (a->o_off[1] * 2) % 16 || ((uintptr_t)a->out % 16) ||
-        (((uintptr_t)x | (uintptr_t)w) % 16) || ((uintptr_t)bias % 2) || ((uintptr_t)a->mask % 4))
-        return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes): x / w / out rows and offsets must be 16-byte aligned");
-    if ((uintptr_t)a->graph_scale % 4) return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes): graph_scale must be 4-byte aligned");
+    if (int rc = proj64_check_tensors(a, x, w, bias)) return rc;
     return a->dtype == TGT_BF16 ? launch_proj64<bf16_t>(*a, nc, x, w, bias, st) : launch_proj64<f16_t>(*a, nc, x, w, bias, st);
 }
+
+#else   // TGT_TRI_PROJ64_INST == 2: the training form
+// tri_att_proj64_fwd_kernel with STORE = true: a kernel of another name, so that the inference kernels keep theirs
+template <typename T, typename... NC>
+__global__ void __launch_bounds__(proj64::kThreads, 2) tri_att_proj64_train_fwd_kernel(const tgt_triplet_attention_args a, const T* x, const T* w,
+                                                                                       const T* bias, NC... nc) {
+    constexpr bool RG = sizeof...(NC) > 0;
+    const int32_t* node_counts = tri_counts_ptr(nc...);
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    TriCtx c;
+    {
+        int pair, grp;
+        if (!na16::unit_of_block(2 * a.B, proj64::kH / proj64::kHG, pair, grp)) return;
+        c.b = pair >> 1; c.dir = pair & 1; c.g = grp; c.h = grp * proj64::kHG + ((tid >> 6) & 3); c.N = a.N; c.tile = 0;
+    }
+    if (c.dir == 0) proj64_walk<T, 0, RG, true>(a, node_counts, c, x, w, bias, smem, tid);
+    else proj64_walk<T, 1, RG, true>(a, node_counts, c, x, w, bias, smem, tid);
+}
+
+int triplet_attention_proj64_train_supported(const tgt_triplet_attention_args* a, int C) {
+    return a && a->dropout_p == 0.f && a->N >= 33 && a->N <= 64 && a->D == proj64::kD && a->H == proj64::kH &&
+           (a->dtype == TGT_BF16 || a->dtype == TGT_F16) && C == proj64::kC && !(a->flags & TGT_TRI_NO_QKV_STORE);
+}
+
+template <typename T>
+static int launch_proj64_train(const tgt_triplet_attention_args& a, const int32_t* nc, const void* x, const void* w, const void* bias,
+                               hipStream_t st) {
+    constexpr int kLds = cmax(proj64::kWalkStore, 2 * proj64::Arm<T>::kBytes);
+    static_assert(kLds <= 160 * 1024, "one workgroup must fit the LDS of a CU");
+    const T *xp = reinterpret_cast<const T*>(x), *wp = reinterpret_cast<const T*>(w), *bp = reinterpret_cast<const T*>(bias);
+    const dim3 g(8 * ((a.B * 2 + 7) / 8) * (proj64::kH / proj64::kHG)), blk(proj64::kThreads);
+    return nc ? launch_lds<tri_att_proj64_train_fwd_kernel<T, const int32_t*>>("tri_att_proj64_train_fwd_kernel", g, blk, kLds, st, a, xp, wp, bp, nc)
+              : launch_lds<tri_att_proj64_train_fwd_kernel<T>>("tri_att_proj64_train_fwd_kernel", g, blk, kLds, st, a, xp, wp, bp);
+}
+
+int triplet_attention_proj64_train_run(const tgt_triplet_attention_args* a, const int32_t* nc, const void* x, int C, const void* w,
+                                       const void* bias, hipStream_t st) {
+    if (!a) return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes, training): null args");
+    if (a->B < 0 || a->N < 0 || a->H <= 0 || C <= 0)
+        return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes, training): bad sizes");
+    if (!triplet_attention_proj64_train_supported(a, C))
+        return set_error(TGT_ERR_UNSUPPORTED,
+                         "projected triplet attention (33..64 nodes, training) needs 33 <= N <= 64, D = 16, H = 16, a 16-bit dtype, C = 256, no "
+                         "attention dropout and TGT_TRI_NO_QKV_STORE clear: it writes Q/K/V (got N=%d D=%d H=%d dtype=%d C=%d flags=%d dropout_p=%g)",
+                         a->N, a->D, a->H, a->dtype, C, a->flags, (double)a->dropout_p);
+    if (a->B == 0) return TGT_OK;
+    if (int rc = proj64_check_tensors(a, x, w, bias)) return rc;
+    // the Q/K/V rows: 128-byte row pieces of whole 16-byte chunks, inside a graph the kernel addresses with 32-bit offsets
+    for (int dir = 0; dir < 2; ++dir) {
+        if (!a->qkv[dir]) return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes, training): null qkv");
+        const int64_t ld = a->ld_qkv[dir];
+        const int offs[3] = {a->q_off[dir], a->k_off[dir], a->v_off[dir]};
+        bool ok = ld > 0 && (ld * 2) % 16 == 0 && (uintptr_t)a->qkv[dir] % 16 == 0 && (int64_t)a->N * a->N * ld * 2 <= INT32_MAX;
+        for (int p = 0; p < 3; ++p) ok = ok && offs[p] >= 0 && (offs[p] * 2) % 16 == 0 && offs[p] + proj64::kH * proj64::kD <= ld;
+        if (!ok)
+            return set_error(TGT_ERR_INVALID, "projected triplet attention (33..64 nodes, training): qkv rows and offsets must be 16-byte aligned, "
+                                              "inside a row of ld_qkv, and a graph below 2 GB");
+    }
+    return a->dtype == TGT_BF16 ? launch_proj64_train<bf16_t>(*a, nc, x, w, bias, st) : launch_proj64_train<f16_t>(*a, nc, x, w, bias, st);
+}
+#endif
 
 }  // namespace tgt

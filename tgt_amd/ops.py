@@ -28,6 +28,7 @@ _TRI_SPLIT = K.tri_split        # A/B knobs: tgt_amd/knobs.py reads the environm
 _TRI_PROJ = K.tri_proj
 _TRI_PROJ_INFER = K.tri_proj_infer
 _TRI_PROJ64_INFER = K.tri_proj64_infer
+_TRI_PROJ64_TRAIN = K.tri_proj64_train
 _AGG_PROJ_INFER = K.agg_proj_infer
 _AGG_PROJ64_INFER = K.agg_proj64_infer
 _TRI_COLSUM = K.tri_colsum
@@ -728,7 +729,11 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         # 33..64 nodes, no backward: Q/K/V projected inside tgt_triplet_attention_proj64_fwd and never written (TGT_TRI_PROJ64_INFER=0
         # is the A/B knob: the library GEMMs + tri_att16_fwd_kernel below)
         infer64 = bool(no_backward and dropout[0] == 0 and _TRI_PROJ and _TRI_PROJ64_INFER and _proj64_fused_ok(x, N, L, cd))
-        if x.numel() // L.C >= _SPLIT_MIN_ROWS and not (dropout[0] == 0 and _proj_fused_ok(x, N, L, cd)) and _TRI_PROJ and not infer64:
+        # 33..64 nodes, a backward can follow: the same kernel's storing form (tgt_triplet_attention_proj64_train_fwd, DESIGN.md
+        # 4.w-64t) writes Q/K/V once, for the backward, and reads nothing back.  Opt-in (TGT_TRI_PROJ64_TRAIN=1)
+        train64 = bool(not no_backward and dropout[0] == 0 and _TRI_PROJ and _TRI_PROJ64_TRAIN and _proj64_fused_ok(x, N, L, cd))
+        if (x.numel() // L.C >= _SPLIT_MIN_ROWS and not (dropout[0] == 0 and _proj_fused_ok(x, N, L, cd)) and _TRI_PROJ and not infer64 and
+                not train64):
             why = ('N > 64' if N > 64 else 'N > 32' if N > 32 else 'attention dropout > 0' if dropout[0] else 'head dim != 16' if L.D != 16 else
                    'heads not a multiple of 8' if L.H % 8 else 'edge width != 256' if L.C != 256 else
                    'fp32' if cd not in (torch.bfloat16, torch.float16) else 'padded / unbiased layout')
@@ -773,6 +778,21 @@ class _ProjectedTripletAttention(torch.autograd.Function):
                 _launch('tgt_triplet_attention_proj64_fwd_counts', C.byref(a), _ptr(node_counts), _ptr(x2), L.C, _ptr(w), _ptr(b),
                         prof='tgt_triplet_attention_proj64_fwd')
             return out                     # (nothing to save: no backward exists)
+        elif train64:
+            # what the N <= 32 branch above does and saves, with the kernel for 33..64 nodes: the Q/K/V rows (written by the
+            # kernel) and the narrow E/G projection as two tensors, as in the split-GEMM branch below
+            x2, w, b = _linear_operands(x, weight, bias, cd, x_contiguous=True, wb_contiguous=True)
+            fused = torch.empty(B, N, N, 6 * L.C, dtype=cd, device=x.device)
+            if L.biased:                       # (axial: no third arm)
+                eg = _narrow_linear(x2, w[6 * L.C:L.used], b[6 * L.C:L.used], cd).view(B, N, N, L.used - 6 * L.C)
+            a = _tri_args(fused, mask3, out, L, eg=eg, graph_scale=graph_scale)
+            if node_counts is None:
+                _launch('tgt_triplet_attention_proj64_train_fwd', C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b),
+                        prof='tgt_triplet_attention_proj64_train_fwd')
+            else:              # (padded units: no Q/K/V rows either -- the backward below gets the same counts)
+                _launch('tgt_triplet_attention_proj64_train_fwd_counts', C.byref(a), _ptr(node_counts), _ptr(x2), L.C, _ptr(w), _ptr(b),
+                        prof='tgt_triplet_attention_proj64_train_fwd')
+            projection_fused = True        # (dropped graphs have NO Q/K/V rows: the backward must skip them too)
         elif _split_projection_ok(x, L):
             # two GEMMs: Q/K/V (6C = 1536 channels: six full 256-wide tile columns, 294 us) and the
             # narrow E/G (39 us) instead of one ragged 1600-wide GEMM (376 us; tools/gemm_probe.py);
@@ -853,7 +873,8 @@ def projected_triplet_attention(x, weight, bias, mask3, layout, table=None, drop
     tuple of the module's nn.Linear parameters (w0, b0, w1, b1, ...) and bias is None.  node_counts: as triplet_attention; in
     the projection-fused forward the padded columns are not projected either.  A call no backward can follow takes, at N <= 32, that
     forward without its Q/K/V stores (TGT_TRI_PROJ_INFER) and, at 33 <= N <= 64 where _proj64_fused_ok holds,
-    tgt_triplet_attention_proj64_fwd (TGT_TRI_PROJ64_INFER): no Q/K/V tensor exists.  N > 64 (library GEMMs + the key-blocked kernels):
+    tgt_triplet_attention_proj64_fwd (TGT_TRI_PROJ64_INFER): no Q/K/V tensor exists.  With TGT_TRI_PROJ64_TRAIN=1 a call at 33..64 nodes
+    that a backward can follow takes that kernel's storing form (tgt_triplet_attention_proj64_train_fwd).  N > 64 (library GEMMs + the key-blocked kernels):
     the counts are used with TGT_TRI_RAGGED_KB=1 only, as in triplet_attention."""
     if not _TRI_COLSUM and table is None:      # A/B knob: separate bias-gradient pass
         return triplet_attention(linear(x, weight, bias), mask3, layout, dropout, graph_scale, node_counts)

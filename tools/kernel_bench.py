@@ -35,7 +35,7 @@ def main():
     ap.add_argument('--only', default='')
     a = ap.parse_args()
     # ('aggproj' / 'triproj64' name their own blocks only, not the 'agg', 'tri' and 'proj' ones)
-    rest = a.only.replace('aggproj', '').replace('triproj64', '')
+    rest = a.only.replace('aggproj', '').replace('triproj64_train', '').replace('triproj64', '')
     agg_b = a.B or 512
     a.B = a.B or 256
     dt = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32}[a.dtype]
@@ -185,7 +185,7 @@ def main():
                                            rounds=[round(t, 4) for t in ts])
         del cases
 
-    if 'triproj64' in a.only:
+    if 'triproj64' in a.only.replace('triproj64_train', ''):
         # tgt_triplet_attention_proj64_fwd itself (the C entry point on pre-projected E/G rows, a.qkv = NULL), the same + the narrow
         # E/G Linear it needs, and what the pair replaces: the split GEMMs (Q/K/V 1536 wide, E/G narrow) + tgt_triplet_attention_fwd
         # (tri_att16_fwd_kernel at these node counts).  fp16 and bf16, 7 alternating rounds in one process; algorithmic bytes per edge
@@ -237,6 +237,62 @@ def main():
             out[f'triproj64_{k}_{n_}'] = dict(ms=round(med, 4), min=round(min(ts), 4), max=round(max(ts), 4),
                                              GBs=round(byts[k] / med / 1e6, 1), share_of_8TBs=round(byts[k] / med / 1e6 / 8000, 3),
                                              rounds=[round(t, 4) for t in ts])
+        del cases
+
+    if 'triproj64_train' in a.only:
+        # tgt_triplet_attention_proj64_train_fwd: the kernel alone (pre-projected E/G rows, a preallocated Q/K/V
+        # tensor), the same + the narrow E/G Linear and the allocation as ops runs it, the inference kernel for scale, and what the
+        # training forward is without it: the split GEMMs + tgt_triplet_attention_fwd.  Rounds and bytes as the triproj64 block
+        import ctypes
+        import statistics
+        from tgt_amd import _lib
+        assert 33 <= N <= 64, '--only triproj64_train needs --N in 33..64'
+        Bp = a.B
+        L = ops.TripletLayout(C, Ht)
+        ne, rows = L.used - 6 * C, Bp * n2
+        maskp = torch.zeros(Bp, N, N, device=dev)
+        byts = dict(kernel=rows * (3 * C + ne + 2 * C + 6 * C) * 2, fused=rows * (C + ne + 3 * C + ne + 2 * C + 6 * C) * 2,
+                    infer=rows * (3 * C + ne + 2 * C) * 2, unfused=rows * (C + 6 * C + ne + 6 * C + ne + 2 * C) * 2)
+        out['triproj64_train_bytes'] = dict(byts, B=Bp, N=N, H=Ht, per_row={k: v // rows for k, v in byts.items()})
+        cases = {}
+        for name, dtp in (('fp16', torch.float16), ('bf16', torch.bfloat16)):
+            x = torch.randn(Bp, N, N, C, device=dev, dtype=dtp)
+            w = (torch.randn(L.width, C, device=dev) * C ** -0.5).to(dtp)
+            bias = torch.randn(L.width, device=dev).to(dtp)
+            x2, wq, bq, we, be = x.view(-1, C), w[:6 * C], bias[:6 * C], w[6 * C:L.used], bias[6 * C:L.used]
+            o = torch.empty(Bp, N, N, 2 * C, device=dev, dtype=dtp)
+            qkv = torch.empty(Bp, N, N, 6 * C, device=dev, dtype=dtp)
+
+            def narrow(x2=x2, we=we, be=be, dtp=dtp):
+                return ops._narrow_linear(x2, we, be, dtp).view(Bp, N, N, ne)
+            at_, ai_ = ops._tri_args(qkv, maskp, o, L, eg=narrow()), ops._tri_args(None, maskp, o, L, eg=narrow())
+            fn, fi = _lib.lib().tgt_triplet_attention_proj64_train_fwd, _lib.lib().tgt_triplet_attention_proj64_fwd
+
+            def kernel(at_=at_, x=x, w=w, bias=bias):
+                _lib.check(fn(ctypes.byref(at_), ops._ptr(x), C, ops._ptr(w), ops._ptr(bias), ops._stream()), 'tgt_triplet_attention_proj64_train_fwd')
+
+            def infer(ai_=ai_, x=x, w=w, bias=bias):
+                _lib.check(fi(ctypes.byref(ai_), ops._ptr(x), C, ops._ptr(w), ops._ptr(bias), ops._stream()), 'tgt_triplet_attention_proj64_fwd')
+
+            def fused(narrow=narrow, x=x, w=w, bias=bias, o=o, dtp=dtp):
+                f = torch.empty(Bp, N, N, 6 * C, device=dev, dtype=dtp)
+                af = ops._tri_args(f, maskp, o, L, eg=narrow())
+                _lib.check(fn(ctypes.byref(af), ops._ptr(x), C, ops._ptr(w), ops._ptr(bias), ops._stream()), 'tgt_triplet_attention_proj64_train_fwd')
+
+            def unfused(narrow=narrow, x2=x2, wq=wq, bq=bq, o=o):
+                f = torch.addmm(bq, x2, wq.t()).view(Bp, N, N, 6 * C)
+                au = ops._tri_args(f, maskp, o, L, eg=narrow())
+                _lib.check(_lib.lib().tgt_triplet_attention_fwd(ctypes.byref(au), ops._stream()), 'tgt_triplet_attention_fwd')
+            cases[name] = dict(kernel=kernel, infer=infer, fused=fused, unfused=unfused, keep=(x, w, bias, o, qkv, at_, ai_))
+        times = {(n_, k): [] for n_ in cases for k in ('kernel', 'infer', 'fused', 'unfused')}
+        for _ in range(7):
+            for key in times:
+                times[key].append(timeit(cases[key[0]][key[1]], a.iters))
+        for (n_, k), ts in times.items():
+            med = statistics.median(ts)
+            out[f'triproj64_train_{k}_{n_}'] = dict(ms=round(med, 4), min=round(min(ts), 4), max=round(max(ts), 4),
+                                                   GBs=round(byts[k] / med / 1e6, 1), share_of_8TBs=round(byts[k] / med / 1e6 / 8000, 3),
+                                                   rounds=[round(t, 4) for t in ts])
         del cases
 
     if not a.only or 'node' in a.only:
