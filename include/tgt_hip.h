@@ -688,7 +688,8 @@ int tgt_transpose_many(const tgt_transpose_item* items, int32_t n, int32_t block
  * (reference lib/training_schemes/pcqm/commons.py:36-38) and its autograd chain, on the logits in
  * their storage dtype (fp32 math on the stored values, which is what autocast's fp32 cast computes).
  *   fwd: lse[r] = log sum_c exp(logits[r][c]);  xent[r] = lse[r] - logits[r][target[r]]
- *   bwd: d_logits[r][c] = row_weight[r] * (exp(logits[r][c] - lse[r]) - [c == target[r]])
+ *   bwd: d_logits[r][c] = row_weight[r] * (e[c] / sum(e) - [c == target[r]]),  e[c] = exp(logits[r][c] - lse[r])   (lse is the
+ *        offset only: a float32 lse is rounded at the magnitude of the logits, and the row's own sum takes that rounding out)
  * row_weight is the upstream gradient of xent (the reference's mask / (mask.sum() + 1e-9), :44-46,
  * times whatever scales the loss); rows with weight 0 are written as zeros without being read.
  * logits / d_logits: (rows, C) contiguous, 16-byte aligned, C a multiple of 8, <= 2048; target int64. */

@@ -237,8 +237,13 @@ __device__ __forceinline__ void keep_vector(uint64_t seed, int64_t vec, uint32_t
         keep[2 * w + 1] = (r >> 16) >= thresh16;
     }
 }
-// Phi(v) = 0.5 (1 + erf(v / sqrt2)) and exp(-v^2/2): erf by Abramowitz & Stegun 7.1.26
-// (|error| <= 1.5e-7, below fp32 parity tolerance); the kernel is otherwise ALU-bound on erff.
+// Phi(v) = 0.5 (1 + erf(v / sqrt2)) and exp(-v^2/2): erf by Abramowitz & Stegun 7.1.26; the kernel is otherwise ALU-bound on
+// erff.  The 1.5e-7 of the formula bounds erf, not this float32 evaluation of x Phi(x).  Measured on the MI355X over every finite
+// bf16 input, a 2^-10 grid on [-8, 8] and 2^17 log-spaced points, against float64 (tests/test_hip_row_hard_inputs.py, float32
+// storage; profiles/parity_errors_row_hard_inputs.json): |y error| <= 2.87e-7 |x|, |dx error| <= 2.84e-7 |dy| (1 + |x|) -- torch's
+// float32 erf form gives 1.05e-7 and 0.81e-7 there.  For v < 0 the small Phi comes out of the cancellation 0.5 - (0.5 - .), so
+// its ABSOLUTE error stays at that level while its relative error does not: x Phi(x) below about 1e-7 |x| (v < -5.2) is noise.
+// A replacement has to meet the per-element bars of tests/row_hard_inputs.py, not a tensor-wide norm.
 __device__ __forceinline__ float gelu_cdf(float v, float& e) {
     const float ax = fabsf(v) * 0.70710678118654752f;
     const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * ax);

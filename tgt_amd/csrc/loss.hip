@@ -94,7 +94,13 @@ __global__ void __launch_bounds__(256) xent_fwd_kernel(const T* x, const int64_t
     }
 }
 
-// backward: dx[row][c] = w[row] * (exp(x[row][c] - lse[row]) - [c == target[row]])
+// backward: dx[row][c] = w[row] * (softmax(x[row])[c] - [c == target[row]])
+// The saved log-sum-exp is ONE float32 number: lse = max + log(sum) is rounded at the magnitude of the logits (common offset 1e4:
+// to 2^-10), and exp(x - lse) alone would hand that rounding whole to every gradient of the row -- 5e-4 relative, where the
+// float32 composition of the reference ((x - max) - log(sum)) loses nothing.  So lse serves as the OFFSET only (x - lse <= ~0: no
+// overflow, and the row maximum need not be found again) and the row is normalised by its own sum: e = exp(x - lse) is the
+// softmax times the common factor exp(rounding of lse), which e / sum(e) cancels exactly.  One wave reduction, the same one
+// exponential per element.
 template <typename T, int VPL>
 __global__ void __launch_bounds__(256) xent_bwd_kernel(const T* x, const int64_t* target, const float* lse, const float* w,
                                                        int64_t rows, int C, T* dx) {
@@ -105,21 +111,39 @@ __global__ void __launch_bounds__(256) xent_bwd_kernel(const T* x, const int64_t
         T* dr = dx + row * C;
         const float l = lse[row], wr = w[row];
         const int64_t t = target[row];
+        float v[VPL][8];
+        if (wr != 0.f) {                    // (one row per wave: uniform)
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < VPL; ++k) {
+                const int col = (k * 64 + lane) * 8;
+                if (col < C) {
+                    xe_load8(xr + col, v[k]);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        v[k][i] = expf(v[k][i] - l);
+                        s += v[k][i];
+                    }
+                }
+            }
+            s = wave_sum(s);
+            const float ws = wr / s;
+#pragma unroll
+            for (int k = 0; k < VPL; ++k) {
+                const int col = (k * 64 + lane) * 8;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[k][i] = v[k][i] * ws - (col + i == t ? wr : 0.f);
+            }
+        } else {                            // masked pair: exact zeros, and no read
+#pragma unroll
+            for (int k = 0; k < VPL; ++k)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[k][i] = 0.f;
+        }
 #pragma unroll
         for (int k = 0; k < VPL; ++k) {
             const int col = (k * 64 + lane) * 8;
-            if (col < C) {
-                float v[8];
-                if (wr != 0.f) {
-                    xe_load8(xr + col, v);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] = wr * (expf(v[i] - l) - (col + i == t ? 1.f : 0.f));
-                } else {            // masked pair: exact zeros, and no read
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] = 0.f;
-                }
-                xe_store8(dr + col, v);
-            }
+            if (col < C) xe_store8(dr + col, v[k]);
         }
     }
 }
