@@ -160,7 +160,9 @@ int tgt_triplet_attention_bwd(const tgt_triplet_attention_args* a, void* stream)
  * the padded rows too, and every real row i < n must have an open key k < n (a prefix mask): the real block of `out` and all
  * gradients are then bit-identical with and without counts.  graph_scale keeps its meaning and wins: a dropped graph is all zeros
  * whatever its count.  The kernels clamp the count; no entry point reads it on the host (no synchronisation, capturable).
- * The aggregate and node attention families take no counts. */
+ * The aggregate and node attention families take no counts through these entry points.  The aggregate family has none at all
+ * (its gated outward direction is unmasked: padded rows reach real outputs); node attention takes them through its own entry
+ * points, tgt_node_attention_fwd_counts / _bwd_counts, under the contract stated there. */
 int tgt_triplet_attention_fwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, void* stream);
 int tgt_triplet_attention_bwd_counts(const tgt_triplet_attention_args* a, const int32_t* node_counts, void* stream);
 /* counts[b] = 1 + the largest j for which some i has an OPEN mask[b,i,j] (open: value > -FLT_MAX/2); 0 when every entry of the
@@ -311,6 +313,28 @@ typedef struct tgt_node_attention_args {
 
 int tgt_node_attention_fwd(const tgt_node_attention_args* a, void* stream);
 int tgt_node_attention_bwd(const tgt_node_attention_args* a, void* stream);
+/* Ragged batches: the same with per-graph node counts.  node_counts: (B) int32 DEVICE memory, or NULL (= the entry point without
+ * _counts, which forwards here with NULL and is bit for bit what it was).  The kernels clamp n = clamp(node_counts[b], 0, N);
+ * nothing is read on the host (no synchronisation, capturable).  Checks: those of the plain entry points, then a node_counts
+ * pointer that is not 4-byte aligned (TGT_ERR_INVALID).  Routing is by tgt_node_attention_family, as without counts.
+ * A count is a permission to skip, never an obligation.  Families that HONOUR it: the key-blocked forward (KB_FWD) and the
+ * MFMA32 and TILES16 backwards.  Families that accept and IGNORE it (a call with counts gives the whole-tensor bits of the call
+ * without): the lane-per-head kernels and with them every logits_only call, the MFMA32 and TILES16 forwards (taken only when
+ * H % 32 != 0), the key-blocked backward of 65..128 nodes.
+ * Forward, honouring family: vatt / lse / gsum rows l >= n are zeros and hhat[b, l, m] is zero wherever l >= n or m >= n;
+ *   nothing of a padded node or pair is loaded -- not the Q/K/V rows of nodes >= n, not the E|G pieces of pairs outside the real
+ *   block [0, n) x [0, n), not their mask entries.  hhat_scale keeps its meaning.
+ * Backward, honouring family: d_vatt[b, l >= n] and d_hhat outside the real block are not read and are taken as zero; d_qkv rows
+ *   >= n and d_eg outside the real block are written as zeros.  A backward does not need its forward to have honoured the count:
+ *   it reads real rows of lse / gsum / vatt only.
+ * It is exact when the mask closes every pair with l >= n or m >= n (value finfo.min or -inf): a closed key has weight exp(.) = 0
+ *   next to any open key and gate sigmoid(G + M) = 0 exactly.  Then vatt[b, l], lse[b, l], gsum[b, l] and hhat[b, l, m] for
+ *   l, m < n are bit-identical to the call without counts, and so is the real block of d_qkv / d_eg given a cotangent that is zero
+ *   on the padding.  A real row WITHOUT an open key (source dropout closed every real key) has gate 0 on every key: A, vatt, gsum
+ *   and every gradient through the softmax are exactly zero with and without counts; its lse is finfo.min + log(keys walked),
+ *   which is finfo.min in float32 whatever the number of keys (or -inf with a closed value of -inf), so it is the same too. */
+int tgt_node_attention_fwd_counts(const tgt_node_attention_args* a, const int32_t* node_counts, void* stream);
+int tgt_node_attention_bwd_counts(const tgt_node_attention_args* a, const int32_t* node_counts, void* stream);
 /* The family tgt_node_attention_fwd (bwd == 0) / _bwd (bwd != 0) would launch for these arguments: the entry points route by this
  * very function.  Host logic only -- sizes, dtype, offsets, pointer nullness and alignment; no pointer is dereferenced and the device
  * is not touched.  Negative: the entry point would refuse the call (NULL args, bad sizes, missing tensors, a D / dtype no kernel takes). */

@@ -25,7 +25,10 @@ SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_l
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=4'], '.f16'), ('triplet_aggregate.hip', ['-DTGT_AGG_INST=1'], '.plain'),
            ('triplet_aggregate.hip', ['-DTGT_AGG_INST=2'], '.skip'), 'triplet_aggregate_proj.hip', 'triplet_aggregate_proj64.hip',
            ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=9'], '.f32'), ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=2'], '.bf16'),
-           ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=4'], '.f16'), 'node_attention.hip', 'node_attention_mfma.hip', 'node_attention16.hip', 'node_attention_kb.hip', 'node_attention_kb_bwd.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip']
+           ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=4'], '.f16'), 'node_attention.hip', 'node_attention_mfma.hip', 'node_attention16.hip', 'node_attention_kb.hip',
+           # (the instantiations with node counts: units of their own, so that the plain units hold the kernels they always held -- DESIGN.md 4.zf)
+           ('node_attention16.hip', ['-DTGT_NODE_COUNTS_UNIT'], '.counts'), ('node_attention_kb.hip', ['-DTGT_NODE_COUNTS_UNIT'], '.counts'),
+           'node_attention_kb_bwd.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip']
 ABI_VERSION = 32
 
 TGT_F32, TGT_BF16, TGT_F16 = 0, 1, 2
@@ -145,6 +148,8 @@ SYMBOLS = {
     'tgt_triplet_aggregate_proj64_fwd_skip': (C.c_int, [C.POINTER(TripletAggregateArgs), _vp, _vp, _i32, _vp, _vp, _vp]),
     'tgt_node_attention_fwd': (C.c_int, [C.POINTER(NodeAttentionArgs), _vp]),
     'tgt_node_attention_bwd': (C.c_int, [C.POINTER(NodeAttentionArgs), _vp]),
+    'tgt_node_attention_fwd_counts': (C.c_int, [C.POINTER(NodeAttentionArgs), _vp, _vp]),
+    'tgt_node_attention_bwd_counts': (C.c_int, [C.POINTER(NodeAttentionArgs), _vp, _vp]),
     'tgt_node_attention_family': (C.c_int, [C.POINTER(NodeAttentionArgs), _i32]),
     'tgt_triangular_update_fwd': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     'tgt_triangular_update_bwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),

@@ -26,7 +26,7 @@ int triplet_attention_run(const tgt_triplet_attention_args* a, const int32_t* no
 int mask_node_counts_run(const float* mask, int B, int N, int32_t* counts, hipStream_t st);
 int64_t tri_att_kb_workspace_bytes(const tgt_triplet_attention_args* a, int bwd);
 int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, const float* graph_scale, bool bwd, hipStream_t st);
-int node_attention_run(const tgt_node_attention_args* a, bool bwd, hipStream_t st);
+int node_attention_run(const tgt_node_attention_args* a, const int32_t* node_counts, bool bwd, hipStream_t st);
 int node_attention_family(const tgt_node_attention_args* a, bool bwd);
 int layer_norm_parts();
 int add_layer_norm_fwd_run(const void* x, int x_dtype, const void* res, int res_dtype, const float* scale,
@@ -133,11 +133,13 @@ int tgt_triplet_aggregate_fwd_skip(const tgt_triplet_aggregate_args* a, const fl
 int tgt_triplet_aggregate_bwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale, void* stream) {
     return triplet_aggregate_run(a, graph_scale, true, reinterpret_cast<hipStream_t>(stream));
 }
-int tgt_node_attention_fwd(const tgt_node_attention_args* a, void* stream) {
-    return node_attention_run(a, false, reinterpret_cast<hipStream_t>(stream));
+int tgt_node_attention_fwd(const tgt_node_attention_args* a, void* stream) { return tgt_node_attention_fwd_counts(a, nullptr, stream); }
+int tgt_node_attention_bwd(const tgt_node_attention_args* a, void* stream) { return tgt_node_attention_bwd_counts(a, nullptr, stream); }
+int tgt_node_attention_fwd_counts(const tgt_node_attention_args* a, const int32_t* node_counts, void* stream) {
+    return node_attention_run(a, node_counts, false, reinterpret_cast<hipStream_t>(stream));
 }
-int tgt_node_attention_bwd(const tgt_node_attention_args* a, void* stream) {
-    return node_attention_run(a, true, reinterpret_cast<hipStream_t>(stream));
+int tgt_node_attention_bwd_counts(const tgt_node_attention_args* a, const int32_t* node_counts, void* stream) {
+    return node_attention_run(a, node_counts, true, reinterpret_cast<hipStream_t>(stream));
 }
 int tgt_node_attention_family(const tgt_node_attention_args* a, int bwd) { return node_attention_family(a, bwd != 0); }
 

@@ -621,13 +621,13 @@ static int dispatch_node_d(const tgt_node_attention_args& a, bool bwd, hipStream
 
 // matrix-core kernels for the 16-bit hot shapes (node_attention_mfma.hip)
 bool node_attention_mfma_eligible(const tgt_node_attention_args& a, bool bwd);
-int node_attention_mfma_run(const tgt_node_attention_args& a, bool bwd, hipStream_t st);
+int node_attention_mfma_run(const tgt_node_attention_args& a, const int32_t* node_counts, bool bwd, hipStream_t st);
 // 16-wide matrix-core tiles for 33 <= N <= 64 (node_attention16.hip): BASELINE config 4
 bool node_attention16_eligible(const tgt_node_attention_args& a, bool bwd);
-int node_attention16_run(const tgt_node_attention_args& a, bool bwd, hipStream_t st);
+int node_attention16_run(const tgt_node_attention_args& a, const int32_t* node_counts, bool bwd, hipStream_t st);
 // key-blocked, whole 128-byte E | G rows per workgroup (node_attention_kb.hip): H a multiple of 32
 bool node_attention_kb_eligible(const tgt_node_attention_args& a, bool bwd);
-int node_attention_kb_run(const tgt_node_attention_args& a, bool bwd, hipStream_t st);
+int node_attention_kb_run(const tgt_node_attention_args& a, const int32_t* node_counts, bool bwd, hipStream_t st);
 
 // key-blocked backward for 65 <= N <= 128 (node_attention_kb_bwd.hip): H a multiple of 8
 bool node_attention_kb_bwd_eligible(const tgt_node_attention_args& a, bool bwd);
@@ -656,7 +656,9 @@ int node_attention_family(const tgt_node_attention_args* a, bool bwd) {
     }
 }
 
-int node_attention_run(const tgt_node_attention_args* a, bool bwd, hipStream_t st) {
+// node_counts: the per-graph node counts of tgt_node_attention_*_counts (tgt_hip.h) or nullptr.  The key-blocked forward and the
+// MFMA32 / TILES16 backwards honour them; every other family (logits_only calls included) accepts and ignores them.
+int node_attention_run(const tgt_node_attention_args* a, const int32_t* node_counts, bool bwd, hipStream_t st) {
     if (!a) return set_error(TGT_ERR_INVALID, "node attention: null args");
     if (a->B < 0 || a->N < 0 || a->H <= 0) return set_error(TGT_ERR_INVALID, "node attention: bad sizes B=%d N=%d H=%d", a->B, a->N, a->H);
     if (a->B == 0 || a->N == 0) return TGT_OK;
@@ -670,11 +672,12 @@ int node_attention_run(const tgt_node_attention_args* a, bool bwd, hipStream_t s
         if (!a->d_qkv || !a->d_eg) return set_error(TGT_ERR_INVALID, "node attention bwd: null d_qkv/d_eg");
         if (!a->logits_only && !a->d_vatt) return set_error(TGT_ERR_INVALID, "node attention bwd: null d_vatt");
     }
+    if ((uintptr_t)node_counts & 3) return set_error(TGT_ERR_INVALID, "node attention: node_counts is not 4-byte aligned");
     switch (node_attention_family(a, bwd)) {
-        case TGT_NODE_FAMILY_KB_FWD: return node_attention_kb_run(*a, bwd, st);
+        case TGT_NODE_FAMILY_KB_FWD: return node_attention_kb_run(*a, node_counts, bwd, st);
         case TGT_NODE_FAMILY_KB_BWD: return node_attention_kb_bwd_run(*a, st);
-        case TGT_NODE_FAMILY_TILES16: return node_attention16_run(*a, bwd, st);
-        case TGT_NODE_FAMILY_MFMA32: return node_attention_mfma_run(*a, bwd, st);
+        case TGT_NODE_FAMILY_TILES16: return node_attention16_run(*a, node_counts, bwd, st);
+        case TGT_NODE_FAMILY_MFMA32: return node_attention_mfma_run(*a, node_counts, bwd, st);
         default: break;                                    // lane-per-head, or a dtype / D it refuses below
     }
     switch (a->dtype) {

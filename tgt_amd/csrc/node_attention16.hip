@@ -296,20 +296,50 @@ __global__ void __launch_bounds__(kThreads, 6) node_att16_fwd_kernel(const tgt_n
     }
 }
 
-template <typename T, int NQ, int D>
-__global__ void __launch_bounds__(kThreads, NQ == 4 ? 2 : 4) node_att16_bwd_kernel(const tgt_node_attention_args a) {
+// zeros into the rows [q0, N) of this head group's part of d_eg (every key) and of the Q segment of d_qkv: the query blocks a
+// ragged backward does not walk
+template <typename T, int D>
+__device__ __forceinline__ void zero_query_rows(const tgt_node_attention_args& a, const Unit& u, int q0, int tid) {
+    const int N = a.N, rows = N - q0;
+    const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
+    T* deg = reinterpret_cast<T*>(a.d_eg) + ((int64_t)u.b * N + q0) * N * a.ld_eg;
+    for (int i = tid; i < rows * N * 2; i += kThreads)       // (pair, E | G): the 16-byte record of this group's 8 heads
+        *reinterpret_cast<uint4*>(deg + (int64_t)(i >> 1) * a.ld_eg + ((i & 1) ? a.g_off : a.e_off) + u.hg * HG) = z4;
+    T* dq = reinterpret_cast<T*>(a.d_qkv) + ((int64_t)u.b * N + q0) * a.ld_qkv + a.q_off + u.hg * HG;
+    for (int i = tid; i < rows * D; i += kThreads) *reinterpret_cast<uint4*>(dq + (int64_t)(i / D) * a.ld_qkv + (i % D) * a.H) = z4;
+}
+
+// Ragged batches (tgt_hip.h, tgt_node_attention_bwd_counts): launched with the node counts as a trailing argument (`NC... nc`,
+// triplet_common.hpp; without it the pack is empty and the kernel is the one it was before the counts existed).  With
+// n = clamp(node_counts[b], 0, N): the query blocks at or past n rounded up to 16 are not walked -- their d_eg / dQ rows are
+// written as zeros; inside a walked block the E | G, dH_hat, mask, Q and dV_att of pairs and rows at or past n are not loaded
+// (node_tiles16.hpp: zeros come back, the mask is the -inf of the keys past N), and neither are the K / V rows at or past n.
+// Why the real block keeps its bits when the mask closes every pair with a padded node: a closed key has weight exp(.) = 0 and
+// gate sigmoid(G + M) = 0 exactly whether M is finfo.min or -inf, so P, the gate sum, delta and every dS / dG of a real pair are
+// the values they were; a padded query with a zero cotangent has dE = dG = 0 and adds exact zeros to dK / dV, so leaving it out
+// changes no sum, and every sum over real queries and keys keeps its order.  A real row without one open key has gate 0 on every
+// key: all of its gradients through the softmax are exactly zero both ways.  Everything at a padded pair or row comes out of
+// this arithmetic as an exact zero (zero operands, weight 0, gate 0) and is stored as such.
+template <typename T, int NQ, int D, typename... NC>
+__global__ void __launch_bounds__(kThreads, NQ == 4 ? 2 : 4) node_att16_bwd_kernel(const tgt_node_attention_args a, NC... nc) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     using L = Lay<NQ, D>;
+    constexpr bool RG = sizeof...(NC) > 0;
     const int tid = threadIdx.x, lane = tid & 63, hh = tid >> 6, x = lane & 15, g = lane >> 4;
-    const int nqb = (a.N + 15) / 16, groups = a.H / HG;
+    const int nqb_all = (a.N + 15) / 16, groups = a.H / HG;
     int b, sub;
     if (!unit_of_block(a.B, groups, b, sub)) return;
     const Unit u{b, sub};
+    int n = 0, nqb = nqb_all;                                               // (n is not read without counts)
+    if constexpr (RG) {
+        n = tri_node_count<true>(tri_counts_ptr(nc...), b, a.N);
+        nqb = (n + 15) / 16;                                                // query blocks with a real node
+    }
     const int chan_eg[2] = {a.e_off + u.hg * HG, a.g_off + u.hg * HG}, chan_h[1] = {u.hg * HG};
     {
-        NodeIO<T, D, 2, 2 * L::NK> nio;
+        NodeIO<T, D, 2, 2 * L::NK, RG> nio;
         const int off[2] = {a.k_off, a.v_off}, rows[2] = {L::NK, L::NK}, row0[2] = {0, 0};
-        nio.issue(a.qkv, a.ld_qkv, off, rows, row0, a.N, a.H, u, tid);
+        nio.issue(a.qkv, a.ld_qkv, off, rows, row0, a.N, a.H, u, tid, n);
         char* const regions[2] = {lds + L::kOffK, lds + L::kOffV};
         nio.template land<L::kPitchN>(regions, rows, tid);
     }
@@ -318,10 +348,10 @@ __global__ void __launch_bounds__(kThreads, NQ == 4 ? 2 : 4) node_att16_bwd_kern
     for (int kb = 0; kb < NQ; ++kb) dk[kb] = dv[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int qb = 0; qb < nqb; ++qb) {
         {
-            PairIO<T, NQ, 2> pio;
-            pio.issue(a.eg, a.ld_eg, chan_eg, a.N, b, qb, tid);
-            PairIO<T, NQ, 1> hio;
-            hio.issue(a.d_hhat, a.H, chan_h, a.N, b, qb, tid);
+            PairIO<T, NQ, 2, RG> pio;
+            pio.issue(a.eg, a.ld_eg, chan_eg, a.N, b, qb, tid, 0, n);
+            PairIO<T, NQ, 1, RG> hio;
+            hio.issue(a.d_hhat, a.H, chan_h, a.N, b, qb, tid, 0, n);
             char* const planes[2] = {lds + L::kOffE, lds + L::kOffG};
             pio.template land<L::kPitchP>(planes, tid);
             char* const hplane[1] = {lds + L::kOffH};
@@ -329,10 +359,10 @@ __global__ void __launch_bounds__(kThreads, NQ == 4 ? 2 : 4) node_att16_bwd_kern
         }
         {
             const int off1[1] = {a.q_off}, rows1[1] = {16}, row01[1] = {16 * qb}, off0[1] = {0};
-            NodeIO<T, D, 1, 16> qio, oio;
-            qio.issue(a.qkv, a.ld_qkv, off1, rows1, row01, a.N, a.H, u, tid);
-            oio.issue(a.d_vatt, (int64_t)D * a.H, off0, rows1, row01, a.N, a.H, u, tid);
-            mask_load<NQ, L::kPitchM>(lds + L::kOffM, a, b, qb, tid);
+            NodeIO<T, D, 1, 16, RG> qio, oio;
+            qio.issue(a.qkv, a.ld_qkv, off1, rows1, row01, a.N, a.H, u, tid, n);
+            oio.issue(a.d_vatt, (int64_t)D * a.H, off0, rows1, row01, a.N, a.H, u, tid, n);
+            mask_load<NQ, L::kPitchM, RG>(lds + L::kOffM, a, b, qb, tid, 0, n);
             char* const rq[1] = {lds + L::kOffQ};
             char* const ro[1] = {lds + L::kOffO};
             qio.template land<L::kPitchN>(rq, rows1, tid);
@@ -350,6 +380,8 @@ __global__ void __launch_bounds__(kThreads, NQ == 4 ? 2 : 4) node_att16_bwd_kern
         }
         __syncthreads();                                   // (the image is restaged for the next query block)
     }
+    // (ragged, n = 0: no query block was walked, so no barrier has passed since the staging threads wrote the K / V regions)
+    if constexpr (RG) __syncthreads();
     // dK^T / dV^T [d 4g + q][key 16 kb + x] of this head: complete sums over every query of the graph
 #pragma unroll
     for (int kb = 0; kb < NQ; ++kb) {
@@ -362,48 +394,68 @@ __global__ void __launch_bounds__(kThreads, NQ == 4 ? 2 : 4) node_att16_bwd_kern
         const int off[2] = {a.k_off, a.v_off}, rows[2] = {L::NK, L::NK}, row0[2] = {0, 0};
         NodeIO<T, D, 2, 2 * L::NK>::template store<L::kPitchN>(regions, a.d_qkv, a.ld_qkv, off, rows, row0, a.N, a.H, u, tid);
     }
+    if constexpr (RG) {
+        if (16 * nqb < a.N) zero_query_rows<T, D>(a, u, 16 * nqb, tid);
+    }
 }
 
 constexpr int kLdsMax = 160 * 1024;
 
-template <typename T, int NQ, int D>
-static int launch(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
+template <typename T, int NQ, int D, typename... NC>
+static int launch(const tgt_node_attention_args& a, bool bwd, hipStream_t st, NC... nc) {
     using L = Lay<NQ, D>;
     const int nqb = (a.N + 15) / 16, groups = a.H / HG;
     if (!bwd) {
-        constexpr int kLds = L::kFwdBytes;
-        static_assert(kLds <= kLdsMax, "forward LDS");
-        const int grid = ((a.B + 7) / 8) * 8 * groups * nqb;
-        return launch_lds<node_att16_fwd_kernel<T, NQ, D>>("node_att16_fwd_kernel", dim3(grid), dim3(kThreads), kLds, st, a);
+        if constexpr (sizeof...(NC) > 0) {
+            return -1;                                      // (the forward takes no counts: not instantiated in the unit with counts)
+        } else {
+            constexpr int kLds = L::kFwdBytes;
+            static_assert(kLds <= kLdsMax, "forward LDS");
+            const int grid = ((a.B + 7) / 8) * 8 * groups * nqb;
+            return launch_lds<node_att16_fwd_kernel<T, NQ, D>>("node_att16_fwd_kernel", dim3(grid), dim3(kThreads), kLds, st, a);
+        }
     } else {
         constexpr int kLds = L::kBwdBytes;
         static_assert(kLds <= kLdsMax, "backward LDS");
         const int grid = ((a.B + 7) / 8) * 8 * groups;
-        return launch_lds<node_att16_bwd_kernel<T, NQ, D>>("node_att16_bwd_kernel", dim3(grid), dim3(kThreads), kLds, st, a);
+        return launch_lds<node_att16_bwd_kernel<T, NQ, D, NC...>>("node_att16_bwd_kernel", dim3(grid), dim3(kThreads), kLds, st, a, nc...);
     }
 }
 
-template <typename T, int NQ>
-static int dispatch_d(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
+template <typename T, int NQ, typename... NC>
+static int dispatch_d(const tgt_node_attention_args& a, bool bwd, hipStream_t st, NC... nc) {
     switch (a.D) {
-        case 8: return launch<T, NQ, 8>(a, bwd, st);
-        case 12: return launch<T, NQ, 12>(a, bwd, st);
-        case 16: return launch<T, NQ, 16>(a, bwd, st);
+        case 8: return launch<T, NQ, 8>(a, bwd, st, nc...);
+        case 12: return launch<T, NQ, 12>(a, bwd, st, nc...);
+        case 16: return launch<T, NQ, 16>(a, bwd, st, nc...);
         default: return -1;
     }
 }
-template <typename T>
-static int dispatch(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
+template <typename T, typename... NC>
+static int dispatch(const tgt_node_attention_args& a, bool bwd, hipStream_t st, NC... nc) {
     switch ((a.N + 15) / 16) {
-        case 1: return dispatch_d<T, 1>(a, bwd, st);
-        case 2: return dispatch_d<T, 2>(a, bwd, st);
-        case 3: return dispatch_d<T, 3>(a, bwd, st);
-        case 4: return dispatch_d<T, 4>(a, bwd, st);
+        case 1: return dispatch_d<T, 1>(a, bwd, st, nc...);
+        case 2: return dispatch_d<T, 2>(a, bwd, st, nc...);
+        case 3: return dispatch_d<T, 3>(a, bwd, st, nc...);
+        case 4: return dispatch_d<T, 4>(a, bwd, st, nc...);
         default: return -1;
     }
 }
 
 }  // namespace na16
+
+// Two units of this file (tgt_amd/_lib.py, as triplet_aggregate.hip's plain / skip units): the plain one holds the kernels every
+// call without counts launches, -DTGT_NODE_COUNTS_UNIT the backward instantiations with counts and nothing else.  In ONE unit the
+// mere presence of the second set moved hipcc's scalar register allocation and schedule of the first (1-2 SGPRs, a few
+// instructions); apart, the plain unit's kernels are the ones they were before the counts existed, instruction for instruction.
+#ifdef TGT_NODE_COUNTS_UNIT
+int node_attention16_run_counts(const tgt_node_attention_args& a, const int32_t* node_counts, hipStream_t st) {
+    int e = a.dtype == TGT_BF16 ? na16::dispatch<bf16_t>(a, true, st, node_counts) : na16::dispatch<f16_t>(a, true, st, node_counts);
+    if (e < 0) return set_error(TGT_ERR_UNSUPPORTED, "node attention (16-wide tiles): unsupported N=%d D=%d", a.N, a.D);
+    return e;
+}
+#else
+int node_attention16_run_counts(const tgt_node_attention_args& a, const int32_t* node_counts, hipStream_t st);
 
 // Is this call one of the shapes the 16-wide kernels take?  Default: 33 <= N <= 64 (N <= 32 stays on node_attention_mfma.hip);
 // TGT_NODE_MFMA16=2 takes every N <= 64 (A/B), 0 none.
@@ -419,11 +471,14 @@ bool node_attention16_eligible(const tgt_node_attention_args& a, bool bwd) {
     return true;
 }
 
-// returns TGT_OK / an error; call only when node_attention16_eligible()
-int node_attention16_run(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
+// returns TGT_OK / an error; call only when node_attention16_eligible().  node_counts: those of a *_counts call or nullptr; the
+// backward honours them, the forward (H % 32 != 0 only: the key-blocked forward comes first) accepts and ignores them
+int node_attention16_run(const tgt_node_attention_args& a, const int32_t* node_counts, bool bwd, hipStream_t st) {
+    if (bwd && node_counts) return node_attention16_run_counts(a, node_counts, st);
     int e = a.dtype == TGT_BF16 ? na16::dispatch<bf16_t>(a, bwd, st) : na16::dispatch<f16_t>(a, bwd, st);
     if (e < 0) return set_error(TGT_ERR_UNSUPPORTED, "node attention (16-wide tiles): unsupported N=%d D=%d", a.N, a.D);
     return e;
 }
+#endif
 
 }  // namespace tgt

@@ -26,6 +26,23 @@
 // was built first and measured 0.052 / 0.058 ms: with one workgroup per CU the land / math / store phases of a tile add up.
 // The backward stays on the other two files: its accumulators (dQ of every query block or dK / dV of every key block, per head)
 // do not leave room for 32 heads per workgroup at two workgroups per CU.
+//
+// Ragged batches (tgt_hip.h, tgt_node_attention_fwd_counts).  The kernel takes the per-graph node counts as a trailing argument
+// (`NC... nc`, triplet_common.hpp; without it the pack is empty and the kernel is the one it was before the counts existed).  With
+// n = clamp(node_counts[b], 0, N) and n16 = n rounded up to 16:
+//   a workgroup whose query block starts at or past n16 writes zeros to its V_att / lse / gsum rows and H_hat rows and returns;
+//   key blocks at or past n16 are neither loaded nor computed, their H_hat columns get zeros after the walk;
+//   inside a computed block the Q / K / V rows of nodes >= n, the E | G pieces and the mask entries of pairs with l >= n or m >= n
+//   are not loaded (offset kOob: zeros come back, no memory is touched) and the mask entry is the -inf the keys past N get.
+// Why the real block keeps its bits when the mask closes every pair with a padded node.  A closed key has logit finfo.min or -inf:
+// next to any open key its weight exp(logit - max) is exactly 0, and its gate sigmoid(G + M) = 1 / (1 + exp(+huge)) is exactly 0, so
+// -inf in its place changes no maximum, sum, gate sum or O: the sums over the real keys keep their order, the padded terms were
+// exact zeros.  A skipped key block would have left the running maximum alone (its block maximum is at most finfo.min, below the
+// real keys of block 0), rescaled by exp(0) = 1 and added zeros: skipping it is the same arithmetic (the argument of
+// triplet_attention_kb.hip's header).  A real row without one open key (source dropout closed every real key) has gate 0 on every
+// key: A, V_att and gsum are exactly zero both ways, and its lse = finfo.min + log(number of closed keys walked) is finfo.min in
+// float32 whatever that number (one ulp of finfo.min is 2e31), -inf where the closed value is -inf.  A padded query row of a computed block
+// has zero operands and -inf on every key: S = 0, H_hat = 0, weights 0, V_att 0; its lse is written as 0, not -inf.
 #include <cstdlib>
 #include "node_tiles16.hpp"
 
@@ -56,15 +73,17 @@ struct Lay {
 __device__ __forceinline__ int head_pos(int hl) { return (hl & ~7) | ((hl + (hl >> 3)) & 7); }
 
 struct Unit { int b, hc, qb; };                            // graph, head chunk, query block
+// (ragged: the loaders' flag RG and last argument n -- rows and pairs at or past n are not loaded and their mask entries are -inf.
+// Without RG the bound is N, written as it always was: n is not in the code)
 
 // ---- the pair image of one key block: task = (query l, key quad mq, octet o of [E octets | G octets])
-template <typename T, int D, int HPW>
+template <typename T, int D, int HPW, bool RG = false>
 struct ImageIO {
     using L = Lay<D, HPW>;
     static constexpr int OCT = 2 * L::OC, kTasks = 16 * 4 * OCT, kIters = (kTasks + kThreads - 1) / kThreads;
     uint4 v[kIters][4];
 
-    __device__ __forceinline__ void issue(const tgt_node_attention_args& a, const Unit& u, int kb, int tid) {
+    __device__ __forceinline__ void issue(const tgt_node_attention_args& a, const Unit& u, int kb, int tid, int n = 0) {
         asm volatile("" : "+v"(tid));
         const int N = a.N;
         const __amdgpu_buffer_rsrc_t rs = graph_rsrc(a.eg, (int64_t)N * N * a.ld_eg * sizeof(T), u.b);
@@ -75,7 +94,9 @@ struct ImageIO {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int m = 16 * kb + 4 * mq + i;
-                const bool ok = task < kTasks && q < N && m < N;
+                bool ok;
+                if constexpr (RG) ok = task < kTasks && q < n && m < n;
+                else ok = task < kTasks && q < N && m < N;
                 v[it][i] = buf_ld16(rs, ok ? (uint32_t)(((int64_t)(q * N + m) * a.ld_eg + ch) * (int64_t)sizeof(T)) : kOob);
             }
         }
@@ -121,14 +142,14 @@ struct ImageIO {
 };
 
 // ---- node rows: task = (segment, row, d quad dq, octet oh): the 16-byte (8 heads) records of (row0 + row, d = 4 dq + i), i < 4
-template <typename T, int D, int HPW, int SEGS>
+template <typename T, int D, int HPW, int SEGS, bool RG = false>
 struct RowsIO {
     using L = Lay<D, HPW>;
     static constexpr int kPerSeg = 16 * L::DQ * L::OC, kTasks = SEGS * kPerSeg, kIters = (kTasks + kThreads - 1) / kThreads;
     uint4 v[kIters][4];
 
     __device__ __forceinline__ void issue(const void* x, int64_t ld, const int (&off)[SEGS], int row0, const tgt_node_attention_args& a, const Unit& u,
-                                          int tid) {
+                                          int tid, int n = 0) {
         asm volatile("" : "+v"(tid));
         const __amdgpu_buffer_rsrc_t rs = graph_rsrc(x, (int64_t)a.N * ld * sizeof(T), u.b);
 #pragma unroll
@@ -137,7 +158,9 @@ struct RowsIO {
             int o = off[0];
 #pragma unroll
             for (int s = 1; s < SEGS; ++s) o = seg == s ? off[s] : o;
-            const bool ok = task < kTasks && row0 + row < a.N;
+            bool ok;
+            if constexpr (RG) ok = task < kTasks && row0 + row < n;
+            else ok = task < kTasks && row0 + row < a.N;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 v[it][i] = buf_ld16(rs, ok ? (uint32_t)(((int64_t)(row0 + row) * ld + o + (4 * dq + i) * a.H + u.hc * L::HW + oh * 8) * (int64_t)sizeof(T))
@@ -181,13 +204,16 @@ struct RowsIO {
 // mask tile of (query block, key block): threads 0..63 hold one key quad of one query; pairs past N get -inf
 struct MaskIO {
     float mk[4];
-    __device__ __forceinline__ void issue(const tgt_node_attention_args& a, const Unit& u, int kb, int tid) {
+    template <bool RG = false>
+    __device__ __forceinline__ void issue(const tgt_node_attention_args& a, const Unit& u, int kb, int tid, int n = 0) {
         const int N = a.N, l = (tid >> 2) & 15, mq = tid & 3, q = 16 * u.qb + l;
         const __amdgpu_buffer_rsrc_t rs = graph_rsrc(a.mask, (int64_t)N * N * 4, u.b);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int m = 16 * kb + 4 * mq + i;
-            const bool ok = tid < 64 && q < N && m < N;
+            bool ok;
+            if constexpr (RG) ok = tid < 64 && q < n && m < n;
+            else ok = tid < 64 && q < N && m < N;
             const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, ok ? (q * N + m) * 4 : (int)kOob, 0, 0));
             mk[i] = ok ? v : -INFINITY;
         }
@@ -209,26 +235,62 @@ __device__ __forceinline__ frag4_t<T> row_frag(const char* region, int row, int 
     return f;
 }
 
-template <typename T, int D, int HPW>
-__global__ void __launch_bounds__(kThreads, 4) node_att_kb_fwd_kernel(const tgt_node_attention_args a) {
+// ragged: zeros into H_hat[b, the block's queries, keys m0 .. N - 1, heads of the chunk] (64 bytes per pair)
+template <typename T, int HW>
+__device__ __forceinline__ void zero_hhat_cols(const tgt_node_attention_args& a, const Unit& u, int m0, int tid) {
+    static_assert(HW * sizeof(T) == 64, "four 16-byte pieces per pair");
+    const int N = a.N, cols = N - m0, rows = min(16, N - 16 * u.qb);
+    T* base = reinterpret_cast<T*>(a.hhat) + ((int64_t)u.b * N + 16 * u.qb) * N * a.H + u.hc * HW;
+    for (int i = tid; i < rows * cols * 4; i += kThreads) {
+        const int piece = i & 3, pr = i >> 2, l = pr / cols, m = m0 + pr % cols;
+        *reinterpret_cast<uint4*>(base + ((int64_t)l * N + m) * a.H + piece * 8) = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+// ragged: a query block of padded nodes only -- zeros into its V_att, lse, gsum and H_hat rows, nothing is read
+template <typename T, int D, int HW>
+__device__ __forceinline__ void zero_query_block(const tgt_node_attention_args& a, const Unit& u, int tid) {
+    const int N = a.N, H = a.H, rows = min(16, N - 16 * u.qb);
+    T* va = reinterpret_cast<T*>(a.vatt) + ((int64_t)u.b * N + 16 * u.qb) * D * H + u.hc * HW;
+    for (int i = tid; i < rows * D * 4; i += kThreads)       // (row, d): 64 bytes
+        *reinterpret_cast<uint4*>(va + (int64_t)(i >> 2) * H + (i & 3) * 8) = make_uint4(0u, 0u, 0u, 0u);
+    const int64_t st = ((int64_t)u.b * N + 16 * u.qb) * H + u.hc * HW;
+    for (int i = tid; i < rows * HW; i += kThreads) {
+        a.lse[st + (int64_t)(i / HW) * H + i % HW] = 0.f;
+        a.gsum[st + (int64_t)(i / HW) * H + i % HW] = 0.f;
+    }
+    if (a.hhat) zero_hhat_cols<T, HW>(a, u, 0, tid);
+}
+
+template <typename T, int D, int HPW, typename... NC>
+__global__ void __launch_bounds__(kThreads, 4) node_att_kb_fwd_kernel(const tgt_node_attention_args a, NC... nc) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     using L = Lay<D, HPW>;
     using F = frag4_t<T>;
+    constexpr bool RG = sizeof...(NC) > 0;           // ragged: launched with the node counts as a trailing argument (header)
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), x = lane & 15, g = lane >> 4;
     const int N = a.N, H = a.H, nkb = (N + 15) / 16, chunks = H / L::HW;
     int b, sub;
     if (!unit_of_block(a.B, chunks * nkb, b, sub)) return;
     const Unit u{b, sub % chunks, sub / chunks};
+    const int n = tri_node_count<RG>(tri_counts_ptr(nc...), b, N);
+    int nwalk = nkb;                                 // key blocks (and query blocks) with a real node
+    if constexpr (RG) {
+        nwalk = (n + 15) / 16;
+        if (u.qb >= nwalk) {
+            zero_query_block<T, D, L::HW>(a, u, tid);
+            return;
+        }
+    }
     char* rQ = lds + L::kOffQ;
     {
-        RowsIO<T, D, HPW, 1> qio;
+        RowsIO<T, D, HPW, 1, RG> qio;
         const int off[1] = {a.q_off};
-        qio.issue(a.qkv, a.ld_qkv, off, 16 * u.qb, a, u, tid);
+        qio.issue(a.qkv, a.ld_qkv, off, 16 * u.qb, a, u, tid, n);
         char* const reg[1] = {rQ};
         qio.land(reg, tid);
     }
-    ImageIO<T, D, HPW> img;
-    RowsIO<T, D, HPW, 2> kv;
+    ImageIO<T, D, HPW, RG> img;
+    RowsIO<T, D, HPW, 2, RG> kv;
     MaskIO msk;
     const int off_kv[2] = {a.k_off, a.v_off};
     char* const reg_kv[2] = {lds + L::kOffK, lds + L::kOffV};
@@ -242,10 +304,10 @@ __global__ void __launch_bounds__(kThreads, 4) node_att_kb_fwd_kernel(const tgt_
     for (int i = 0; i < HPW; ++i) { o[i] = z; mx[i] = -INFINITY; lsum[i] = 0.f; gs[i] = 0.f; }
     const char* pm = lds + L::kOffM + x * L::kPitchM + g * 16;
 
-    for (int kb = 0; kb < nkb; ++kb) {
-        img.issue(a, u, kb, tid);                          // (the other workgroup of the CU computes under these loads)
-        kv.issue(a.qkv, a.ld_qkv, off_kv, 16 * kb, a, u, tid);
-        msk.issue(a, u, kb, tid);
+    for (int kb = 0; kb < nwalk; ++kb) {
+        img.issue(a, u, kb, tid, n);                       // (the other workgroup of the CU computes under these loads)
+        kv.issue(a.qkv, a.ld_qkv, off_kv, 16 * kb, a, u, tid, n);
+        msk.template issue<RG>(a, u, kb, tid, n);
         img.land(lds, tid);
         kv.land(reg_kv, tid);
         msk.template land<L::kPitchM>(lds + L::kOffM, tid);
@@ -307,18 +369,23 @@ __global__ void __launch_bounds__(kThreads, 4) node_att_kb_fwd_kernel(const tgt_
         const float ov[4] = {o[i][0] * f, o[i][1] * f, o[i][2] * f, o[i][3] * f};
         if (4 * g < D) *reinterpret_cast<uint2*>(rQ + x * L::kPitchN + hl * (D * 2) + g * 8) = pack4u<T>(ov);   // V_att leaves through this head's Q columns
         if (row < N && g == 0) {
-            a.lse[((int64_t)u.b * N + row) * H + h] = mx[i] + __logf(sum);
+            float lse = mx[i] + __logf(sum);
+            if constexpr (RG) lse = row < n ? lse : 0.f;   // (a padded row of a computed block: zero, not -inf)
+            a.lse[((int64_t)u.b * N + row) * H + h] = lse;
             a.gsum[((int64_t)u.b * N + row) * H + h] = gsum;
         }
     }
     __syncthreads();
     RowsIO<T, D, HPW, 1>::store(rQ, a.vatt, (int64_t)D * H, 0, 16 * u.qb, a, u, tid);
+    if constexpr (RG) {
+        if (a.hhat && 16 * nwalk < N) zero_hhat_cols<T, L::HW>(a, u, 16 * nwalk, tid);
+    }
 }
 
 constexpr int kLdsMax = 160 * 1024;
 
-template <typename T, int D, int HPW>
-static int launch_fwd(const tgt_node_attention_args& a, hipStream_t st) {
+template <typename T, int D, int HPW, typename... NC>
+static int launch_fwd(const tgt_node_attention_args& a, hipStream_t st, NC... nc) {
     using L = Lay<D, HPW>;
     constexpr int kLds = L::kFwdBytes;
     if constexpr (kLds > kLdsMax) {
@@ -326,20 +393,31 @@ static int launch_fwd(const tgt_node_attention_args& a, hipStream_t st) {
     } else {
         const int nqb = (a.N + 15) / 16, chunks = a.H / L::HW;
         const int grid = ((a.B + 7) / 8) * 8 * chunks * nqb;
-        return launch_lds<node_att_kb_fwd_kernel<T, D, HPW>>("node_att_kb_fwd_kernel", dim3(grid), dim3(kThreads), kLds, st, a);
+        return launch_lds<node_att_kb_fwd_kernel<T, D, HPW, NC...>>("node_att_kb_fwd_kernel", dim3(grid), dim3(kThreads), kLds, st, a, nc...);
     }
 }
-template <typename T>
-static int dispatch_fwd(const tgt_node_attention_args& a, hipStream_t st) {
+template <typename T, typename... NC>
+static int dispatch_fwd(const tgt_node_attention_args& a, hipStream_t st, NC... nc) {
     switch (a.D) {
-        case 8: return launch_fwd<T, 8, 4>(a, st);
-        case 12: return launch_fwd<T, 12, 4>(a, st);
-        case 16: return launch_fwd<T, 16, 4>(a, st);
+        case 8: return launch_fwd<T, 8, 4>(a, st, nc...);
+        case 12: return launch_fwd<T, 12, 4>(a, st, nc...);
+        case 16: return launch_fwd<T, 16, 4>(a, st, nc...);
         default: return -1;
     }
 }
 
 }  // namespace nkb
+
+// Two units of this file (tgt_amd/_lib.py; node_attention16.hip says why): the plain one holds the kernels every call without counts
+// launches, -DTGT_NODE_COUNTS_UNIT the instantiations with counts and nothing else.
+#ifdef TGT_NODE_COUNTS_UNIT
+int node_attention_kb_run_counts(const tgt_node_attention_args& a, const int32_t* node_counts, hipStream_t st) {
+    int e = a.dtype == TGT_BF16 ? nkb::dispatch_fwd<bf16_t>(a, st, node_counts) : nkb::dispatch_fwd<f16_t>(a, st, node_counts);
+    if (e < 0) return set_error(TGT_ERR_UNSUPPORTED, "node attention (key-blocked): unsupported N=%d H=%d D=%d", a.N, a.H, a.D);
+    return e;
+}
+#else
+int node_attention_kb_run_counts(const tgt_node_attention_args& a, const int32_t* node_counts, hipStream_t st);
 
 // Shapes the key-blocked forward takes: 16-bit, any N <= 1024 (nothing in the kernel is sized by N), H a multiple of 32, D in {8, 12, 16}.  TGT_NODE_KB (A/B): 0 off, 1 N > 32
 // only, 2 (default) every N.
@@ -358,11 +436,14 @@ bool node_attention_kb_eligible(const tgt_node_attention_args& a, bool bwd) {
     return true;
 }
 
-int node_attention_kb_run(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
+// (node_counts: those of a *_counts call, honoured, or nullptr)
+int node_attention_kb_run(const tgt_node_attention_args& a, const int32_t* node_counts, bool bwd, hipStream_t st) {
+    if (!bwd && node_counts) return node_attention_kb_run_counts(a, node_counts, st);
     int e = -1;
     if (!bwd) e = a.dtype == TGT_BF16 ? nkb::dispatch_fwd<bf16_t>(a, st) : nkb::dispatch_fwd<f16_t>(a, st);
     if (e < 0) return set_error(TGT_ERR_UNSUPPORTED, "node attention (key-blocked): unsupported N=%d H=%d D=%d", a.N, a.H, a.D);
     return e;
 }
+#endif
 
 }  // namespace tgt

@@ -109,9 +109,9 @@ __device__ __forceinline__ uint32_t eg_chan(const tgt_node_attention_args& a, co
     constexpr int kE = HG / 8;       // 16-byte pieces of E (8 heads each)
     return (uint32_t)(((sub < kE ? a.e_off + sub * 8 : a.g_off + (sub - kE) * 8) + u.hg * HG) * (int)sizeof(T));
 }
-template <typename T, int HG, int NTHR = HG * 64>
+template <typename T, int HG, bool RG = false, int NTHR = HG * 64>
 __device__ __forceinline__ void stage_eg_issue(const tgt_node_attention_args& a, const Unit& u, int tid,
-                                               uint4 (&v)[PairMap<NTHR, HG / 4>::kIters]) {
+                                               uint4 (&v)[PairMap<NTHR, HG / 4>::kIters], int n = 0) {
     using PM = PairMap<NTHR, HG / 4>;
     const PM pm(tid);
     const int N = a.N;
@@ -120,7 +120,9 @@ __device__ __forceinline__ void stage_eg_issue(const tgt_node_attention_args& a,
     const uint32_t off0 = (uint32_t)(pm.l0 * N + pm.m) * ldb + eg_chan<T, HG>(a, u, pm.sub);
 #pragma unroll
     for (int it = 0; it < PM::kIters; ++it) {
-        const bool ok = pm.m < N && pm.l0 + it * PM::kLStep < N;
+        bool ok;
+        if constexpr (RG) ok = pm.m < n && pm.l0 + it * PM::kLStep < n;
+        else ok = pm.m < N && pm.l0 + it * PM::kLStep < N;
         v[it] = buf_ld16(rs, ok ? off0 + (uint32_t)(it * PM::kLStep * N) * ldb : kOob);
     }
 }
@@ -150,10 +152,13 @@ __device__ __forceinline__ void unstage_eg(const char* lds, void* d_eg, const tg
         buf_st16(rs, ok ? off0 + (uint32_t)(it * PM::kLStep * N) * ldb : kOob, lds_get16(src + it * PM::kLStep * L::kPitchEG, rot));
     }
 }
+// (the loaders' flag RG and last argument n, ragged backward only -- see node_att_mfma_bwd_kernel: rows and pairs at or past n are
+// not loaded -- offset kOob, zeros come back -- and their mask entries are the -inf of the keys past N.  Without RG the bound is N,
+// written as it always was: n is not in the code)
 // (B,N,N,H) tensors (H_hat, dH_hat): HG/8 pieces per pair
-template <typename T, int HG, int NTHR = HG * 64>
+template <typename T, int HG, bool RG = false, int NTHR = HG * 64>
 __device__ __forceinline__ void stage_h_issue(const void* x, const tgt_node_attention_args& a, const Unit& u, int tid,
-                                              uint4 (&v)[PairMap<NTHR, HG / 8>::kIters]) {
+                                              uint4 (&v)[PairMap<NTHR, HG / 8>::kIters], int n = 0) {
     using PM = PairMap<NTHR, HG / 8>;
     const PM pm(tid);
     const int N = a.N;
@@ -162,7 +167,9 @@ __device__ __forceinline__ void stage_h_issue(const void* x, const tgt_node_atte
     const uint32_t off0 = (uint32_t)(pm.l0 * N + pm.m) * ldb + (uint32_t)((u.hg * HG + pm.sub * 8) * (int)sizeof(T));
 #pragma unroll
     for (int it = 0; it < PM::kIters; ++it) {
-        const bool ok = x && pm.m < N && pm.l0 + it * PM::kLStep < N;
+        bool ok;
+        if constexpr (RG) ok = x && pm.m < n && pm.l0 + it * PM::kLStep < n;
+        else ok = x && pm.m < N && pm.l0 + it * PM::kLStep < N;
         v[it] = buf_ld16(rs, ok ? off0 + (uint32_t)(it * PM::kLStep * N) * ldb : kOob);
     }
 }
@@ -204,16 +211,18 @@ struct NodeMap {
         piece = c % kPer; d = (c / kPer) % D; row = c / kPer / D; in = c < kChunks;
     }
     __device__ __forceinline__ int lds_off() const { return row * Lay<HG>::pitch_n(D) + d * Lay<HG>::kRecH + piece * 16; }
-    __device__ __forceinline__ uint32_t glb_off(int64_t ld, int off, const tgt_node_attention_args& a, const Unit& u, int esz) const {
-        return (in && row < a.N) ? (uint32_t)((row * ld + off + d * a.H + u.hg * HG + piece * 8) * (int64_t)esz) : kOob;
+    template <bool RG = false>
+    __device__ __forceinline__ uint32_t glb_off(int64_t ld, int off, const tgt_node_attention_args& a, const Unit& u, int esz, int n = 0) const {
+        if constexpr (RG) return (in && row < n) ? (uint32_t)((row * ld + off + d * a.H + u.hg * HG + piece * 8) * (int64_t)esz) : kOob;
+        else return (in && row < a.N) ? (uint32_t)((row * ld + off + d * a.H + u.hg * HG + piece * 8) * (int64_t)esz) : kOob;
     }
 };
-template <typename T, int HG, int D, int NTHR = HG * 64>
+template <typename T, int HG, int D, bool RG = false, int NTHR = HG * 64>
 __device__ __forceinline__ void stage_node_issue(const void* x, int64_t ld, int off, const tgt_node_attention_args& a, const Unit& u,
-                                                 int tid, uint4 (&v)[NodeMap<HG, NTHR, D>::kIters]) {
+                                                 int tid, uint4 (&v)[NodeMap<HG, NTHR, D>::kIters], int n = 0) {
     const __amdgpu_buffer_rsrc_t rs = graph_rsrc(x, (int64_t)a.N * ld * sizeof(T), u.b);
 #pragma unroll
-    for (int it = 0; it < NodeMap<HG, NTHR, D>::kIters; ++it) v[it] = buf_ld16(rs, NodeMap<HG, NTHR, D>(tid, it).glb_off(ld, off, a, u, sizeof(T)));
+    for (int it = 0; it < NodeMap<HG, NTHR, D>::kIters; ++it) v[it] = buf_ld16(rs, NodeMap<HG, NTHR, D>(tid, it).template glb_off<RG>(ld, off, a, u, sizeof(T), n));
 }
 template <int HG, int D, int NTHR = HG * 64>
 __device__ __forceinline__ void stage_node_commit(char* region, int tid, uint4 (&v)[NodeMap<HG, NTHR, D>::kIters]) {
@@ -235,14 +244,18 @@ __device__ __forceinline__ void unstage_node(const char* region, void* x, int64_
 }
 // mask tile: pairs past N get -inf: their logits become -inf (weight exactly 0) and their gates sigmoid(-inf) = 0
 // without a select per tile element
-template <int NTHR>
-__device__ __forceinline__ void stage_mask_issue(const tgt_node_attention_args& a, const Unit& u, int tid, float (&mk)[1024 / NTHR]) {
+template <int NTHR, bool RG = false>
+__device__ __forceinline__ void stage_mask_issue(const tgt_node_attention_args& a, const Unit& u, int tid, float (&mk)[1024 / NTHR], int n = 0) {
     const int N = a.N;
 #pragma unroll
     for (int it = 0; it < 1024 / NTHR; ++it) {
         const int idx = it * NTHR + tid, l = idx >> 5, m = idx & 31;
         mk[it] = -INFINITY;
-        if (l < N && m < N) mk[it] = a.mask[((int64_t)u.b * N + l) * N + m];
+        if constexpr (RG) {
+            if (l < n && m < n) mk[it] = a.mask[((int64_t)u.b * N + l) * N + m];
+        } else {
+            if (l < N && m < N) mk[it] = a.mask[((int64_t)u.b * N + l) * N + m];
+        }
     }
 }
 template <int HG, int NTHR>
@@ -540,8 +553,19 @@ __global__ void __launch_bounds__(HG * 64, 4) node_att_mfma_fwd_kernel(const tgt
     unstage_node<T, HG, D>(rQ, a.vatt, (int64_t)D * a.H, 0, a, u, tid);
 }
 
-template <typename T, int HG, int D>
-__global__ void __launch_bounds__(HG * 64, 4) node_att_mfma_bwd_kernel(const tgt_node_attention_args a, const int ablate) {
+// Ragged batches (tgt_hip.h, tgt_node_attention_bwd_counts): launched with the node counts as a trailing argument (`NC... nc`,
+// triplet_common.hpp; without it the pack is empty and the kernel is the one it was before the counts existed).  The unit is ONE
+// tile per head, so nothing is skipped as a block: with n = clamp(node_counts[b], 0, N) the E | G, dH_hat and mask entries of the
+// pairs with l >= n or m >= n and the Q / K / V / dV_att rows of the nodes >= n are not loaded (zeros; the mask is the -inf of the
+// keys past N), which is what takes them off the HBM stream.
+// Why the real block keeps its bits when the mask closes every pair with a padded node: a closed key has weight exp(.) = 0 and
+// gate sigmoid(G + M) = 0 exactly whether M is finfo.min or -inf, so P, the gate sum, delta and every dS / dG of a real pair are
+// the values they were; a padded query with a zero cotangent has dE = dG = 0 with and without its loads and adds exact zeros to
+// dK / dV, and every sum over real queries and keys keeps its order.  A real row without one open key has gate 0 on every key:
+// all of its gradients through the softmax are exactly zero both ways.  At a padded pair or row every operand is zero, the
+// weight 0 and the gate 0: dE, dG, dQ, dK, dV come out of the same arithmetic as exact zeros and are stored as such.
+template <typename T, int HG, int D, typename... NC>
+__global__ void __launch_bounds__(HG * 64, 4) node_att_mfma_bwd_kernel(const tgt_node_attention_args a, const int ablate, NC... nc) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     using L = Lay<HG>;
     constexpr int NTHR = HG * 64;
@@ -552,19 +576,21 @@ __global__ void __launch_bounds__(HG * 64, 4) node_att_mfma_bwd_kernel(const tgt
     char* rO = lds + L::off_n(D, true, 3);
     Unit u;
     if (!unit_of_block(a, HG, u)) return;
+    constexpr bool RG = sizeof...(NC) > 0;
+    const int n = tri_node_count<RG>(tri_counts_ptr(nc...), u.b, a.N);
 
     if (!(ablate & 2)) {
         uint4 veg[PairMap<NTHR, HG / 4>::kIters], vh[PairMap<NTHR, HG / 8>::kIters];
         uint4 vq[NodeMap<HG, NTHR, D>::kIters], vk[NodeMap<HG, NTHR, D>::kIters], vv[NodeMap<HG, NTHR, D>::kIters],
             vo[NodeMap<HG, NTHR, D>::kIters];
         float mk[1024 / NTHR];
-        stage_eg_issue<T, HG>(a, u, tid, veg);
-        stage_h_issue<T, HG>(a.d_hhat, a, u, tid, vh);
-        stage_node_issue<T, HG, D>(a.qkv, a.ld_qkv, a.q_off, a, u, tid, vq);
-        stage_node_issue<T, HG, D>(a.qkv, a.ld_qkv, a.k_off, a, u, tid, vk);
-        stage_node_issue<T, HG, D>(a.qkv, a.ld_qkv, a.v_off, a, u, tid, vv);
-        stage_node_issue<T, HG, D>(a.d_vatt, (int64_t)D * a.H, 0, a, u, tid, vo);
-        stage_mask_issue<NTHR>(a, u, tid, mk);
+        stage_eg_issue<T, HG, RG>(a, u, tid, veg, n);
+        stage_h_issue<T, HG, RG>(a.d_hhat, a, u, tid, vh, n);
+        stage_node_issue<T, HG, D, RG>(a.qkv, a.ld_qkv, a.q_off, a, u, tid, vq, n);
+        stage_node_issue<T, HG, D, RG>(a.qkv, a.ld_qkv, a.k_off, a, u, tid, vk, n);
+        stage_node_issue<T, HG, D, RG>(a.qkv, a.ld_qkv, a.v_off, a, u, tid, vv, n);
+        stage_node_issue<T, HG, D, RG>(a.d_vatt, (int64_t)D * a.H, 0, a, u, tid, vo, n);
+        stage_mask_issue<NTHR, RG>(a, u, tid, mk, n);
         stage_eg_commit<HG>(lds, tid, veg);
         stage_h_commit<HG>(lds, tid, vh);
         stage_node_commit<HG, D>(rQ, tid, vq);
@@ -585,8 +611,8 @@ __global__ void __launch_bounds__(HG * 64, 4) node_att_mfma_bwd_kernel(const tgt
 
 constexpr int kLdsMax = 160 * 1024;
 
-template <typename T, int HG, int D>
-static int launch(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
+template <typename T, int HG, int D, typename... NC>
+static int launch(const tgt_node_attention_args& a, bool bwd, hipStream_t st, NC... nc) {
     using L = Lay<HG>;
     const int grid = ((a.B + 7) / 8) * 8 * (a.H / HG);       // a multiple of 8: the XCD lists of unit_of_block cover every unit
 #ifdef TGT_PROBES
@@ -601,17 +627,17 @@ static int launch(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
     } else {
         constexpr int kLds = L::lds_bytes(D, true);
         if constexpr (kLds <= kLdsMax)
-            return launch_lds<node_att_mfma_bwd_kernel<T, HG, D>>("node_att_mfma_bwd_kernel", dim3(grid), dim3(HG * 64), kLds, st, a, ablate);
+            return launch_lds<node_att_mfma_bwd_kernel<T, HG, D, NC...>>("node_att_mfma_bwd_kernel", dim3(grid), dim3(HG * 64), kLds, st, a, ablate, nc...);
         return -1;
     }
 }
 
-template <typename T, int HG>
-static int dispatch_d(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
+template <typename T, int HG, typename... NC>
+static int dispatch_d(const tgt_node_attention_args& a, bool bwd, hipStream_t st, NC... nc) {
     switch (a.D) {
-        case 8: return launch<T, HG, 8>(a, bwd, st);
-        case 12: return launch<T, HG, 12>(a, bwd, st);
-        case 16: return launch<T, HG, 16>(a, bwd, st);
+        case 8: return launch<T, HG, 8>(a, bwd, st, nc...);
+        case 12: return launch<T, HG, 12>(a, bwd, st, nc...);
+        case 16: return launch<T, HG, 16>(a, bwd, st, nc...);
         default: return -1;
     }
 }
@@ -623,9 +649,9 @@ static int heads_per_group(const tgt_node_attention_args& a, bool bwd) {
     return 8;
 }
 
-template <typename T>
-static int dispatch(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
-    return heads_per_group(a, bwd) == 16 ? dispatch_d<T, 16>(a, bwd, st) : dispatch_d<T, 8>(a, bwd, st);
+template <typename T, typename... NC>
+static int dispatch(const tgt_node_attention_args& a, bool bwd, hipStream_t st, NC... nc) {
+    return heads_per_group(a, bwd) == 16 ? dispatch_d<T, 16>(a, bwd, st, nc...) : dispatch_d<T, 8>(a, bwd, st, nc...);
 }
 
 }  // namespace nmf
@@ -643,9 +669,12 @@ bool node_attention_mfma_eligible(const tgt_node_attention_args& a, bool bwd) {
     return true;
 }
 
-// returns TGT_OK / an error; call only when node_attention_mfma_eligible()
-int node_attention_mfma_run(const tgt_node_attention_args& a, bool bwd, hipStream_t st) {
-    int e = a.dtype == TGT_BF16 ? nmf::dispatch<bf16_t>(a, bwd, st) : nmf::dispatch<f16_t>(a, bwd, st);
+// returns TGT_OK / an error; call only when node_attention_mfma_eligible().  node_counts: those of a *_counts call or nullptr; the
+// backward honours them, the forward (H % 32 != 0 only: the key-blocked forward comes first) accepts and ignores them
+int node_attention_mfma_run(const tgt_node_attention_args& a, const int32_t* node_counts, bool bwd, hipStream_t st) {
+    int e;
+    if (bwd && node_counts) e = a.dtype == TGT_BF16 ? nmf::dispatch<bf16_t>(a, bwd, st, node_counts) : nmf::dispatch<f16_t>(a, bwd, st, node_counts);
+    else e = a.dtype == TGT_BF16 ? nmf::dispatch<bf16_t>(a, bwd, st) : nmf::dispatch<f16_t>(a, bwd, st);
     if (e < 0) return set_error(TGT_ERR_UNSUPPORTED, "node attention (matrix core): unsupported D=%d", a.D);
     return e;
 }

@@ -71,6 +71,11 @@ __device__ __forceinline__ float qmax(float v) {
 }
 
 constexpr uint32_t kOob = 0x7ffffff0u;
+// Ragged batches (tgt_hip.h, tgt_node_attention_*_counts): the loaders below have a compile-time flag RG (of the class) and take the graph's node
+// count n as a last argument.  With RG, rows and pairs at or past n are not loaded (offset kOob: zeros come back, no memory is
+// touched) and their mask entries are the -inf of the keys past N; N keeps every stride.  Without RG (the default: every caller
+// without counts) n does not appear in the code at all -- the task's row and pair indices come from an opaque thread index, so a
+// comparison with a constant would NOT fold away.
 
 __device__ __forceinline__ uint4 buf_ld16(__amdgpu_buffer_rsrc_t r, uint32_t off) {
     const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
@@ -129,13 +134,14 @@ struct Unit { int b, hg; };
 // ---- pair planes.  A staging task = (plane, query l, key quad mq): the 16-byte records of pairs (16 qb + l, m0 + 4 mq + i), i < 4
 // (m0: the first key of the staged key range; 0 where the planes hold every key).
 // `chan[plane]` = element offset of this head group's 8 channels inside a pair's row of the tensor (ld elements per pair).
-template <typename T, int NQ, int PLANES>
+template <typename T, int NQ, int PLANES, bool RG = false>
 struct PairIO {
     static constexpr int NK = 16 * NQ, MQ = NK / 4, kPerPlane = 16 * MQ, kTasks = PLANES * kPerPlane;
     static constexpr int kIters = (kTasks + kThreads - 1) / kThreads;
     uint4 v[kIters][4];
 
-    __device__ __forceinline__ void issue(const void* x, int64_t ld, const int (&chan)[PLANES], int N, int b, int qb, int tid, int m0 = 0) {
+    __device__ __forceinline__ void issue(const void* x, int64_t ld, const int (&chan)[PLANES], int N, int b, int qb, int tid, int m0 = 0,
+                                          int n = 0) {
         asm volatile("" : "+v"(tid));            // (opaque: the task's addresses are recomputed here, not kept live across the query-block walk)
         const __amdgpu_buffer_rsrc_t rs = graph_rsrc(x, (int64_t)N * N * ld * sizeof(T), b);
 #pragma unroll
@@ -147,7 +153,9 @@ struct PairIO {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int m = m0 + 4 * mq + i;
-                const bool ok = x && task < kTasks && q < N && m < N;
+                bool ok;
+                if constexpr (RG) ok = x && task < kTasks && q < n && m < n;         // (n <= N)
+                else ok = x && task < kTasks && q < N && m < N;
                 v[it][i] = buf_ld16(rs, ok ? (uint32_t)(((int64_t)(q * N + m) * ld + ch) * (int64_t)sizeof(T)) : kOob);
             }
         }
@@ -195,7 +203,7 @@ struct PairIO {
 
 // ---- node rows.  A staging task = (segment, row, d quad dq): the 16-byte (8 heads) records of (row, d = 4 dq + i), i < 4, of a
 // (B, N, ld) tensor whose row holds [d][H heads] from element `off[segment]`.  Segment s covers `rows[s]` rows from row0[s] into region[s].
-template <typename T, int D, int SEGS, int MAXROWS>
+template <typename T, int D, int SEGS, int MAXROWS, bool RG = false>
 struct NodeIO {
     static constexpr int DQ = D / 4, kTasks = MAXROWS * DQ, kIters = (kTasks + kThreads - 1) / kThreads;
     uint4 v[kIters][4];
@@ -210,7 +218,7 @@ struct NodeIO {
         row = r;
     }
     __device__ __forceinline__ void issue(const void* x, int64_t ld, const int (&off)[SEGS], const int (&rows)[SEGS], const int (&row0)[SEGS], int N,
-                                          int H, const Unit& u, int tid) {
+                                          int H, const Unit& u, int tid, int n = 0) {
         asm volatile("" : "+v"(tid));            // (opaque: the task's addresses are recomputed here, not kept live across the query-block walk)
         const __amdgpu_buffer_rsrc_t rs = graph_rsrc(x, (int64_t)N * ld * sizeof(T), u.b);
 #pragma unroll
@@ -220,7 +228,9 @@ struct NodeIO {
             int o = off[0], r0 = row0[0], nr = rows[0];
 #pragma unroll
             for (int s = 1; s < SEGS; ++s) { o = seg == s ? off[s] : o; r0 = seg == s ? row0[s] : r0; nr = seg == s ? rows[s] : nr; }
-            const bool ok = x && row < nr && r0 + row < N;
+            bool ok;
+            if constexpr (RG) ok = x && row < nr && r0 + row < n;                    // (n <= N)
+            else ok = x && row < nr && r0 + row < N;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 v[it][i] = buf_ld16(rs, ok ? (uint32_t)(((int64_t)(r0 + row) * ld + o + (4 * dq + i) * H + u.hg * HG) * (int64_t)sizeof(T)) : kOob);
@@ -271,8 +281,8 @@ struct NodeIO {
 };
 
 // mask tile of the query block (keys from m0): pairs past N get -inf (weight exactly 0, gate sigmoid(-inf) = 0)
-template <int NQ, int PITCH>
-__device__ __forceinline__ void mask_load(char* lds_m, const tgt_node_attention_args& a, int b, int qb, int tid, int m0 = 0) {
+template <int NQ, int PITCH, bool RG = false>
+__device__ __forceinline__ void mask_load(char* lds_m, const tgt_node_attention_args& a, int b, int qb, int tid, int m0 = 0, int n = 0) {
     constexpr int NK = 16 * NQ, MQ = NK / 4;
     const int N = a.N;
     asm volatile("" : "+v"(tid));
@@ -283,7 +293,9 @@ __device__ __forceinline__ void mask_load(char* lds_m, const tgt_node_attention_
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int m = m0 + 4 * mq + i;
-            const bool ok = q < N && m < N;
+            bool ok;
+            if constexpr (RG) ok = q < n && m < n;                                   // (n <= N)
+            else ok = q < N && m < N;
             const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, ok ? (q * N + m) * 4 : (int)kOob, 0, 0));
             mk[i] = ok ? v : -INFINITY;
         }

@@ -25,6 +25,7 @@ _SPEC = {
     'tri_ragged': ('TGT_TRI_RAGGED', False, 'flag', 'triplet attention skips the padded nodes of every graph (N <= 64): per-graph node counts from the mask, once per forward; padded positions of the edge stream then hold other finite values'),
     'tri_ragged_kb': ('TGT_TRI_RAGGED_KB', False, 'flag', 'the key-blocked triplet attention kernels (65..128 nodes) use the node counts they are given (TGT_TRI_COUNTS_KB): padded units, query tiles and key blocks are skipped; needs tri_ragged in the model'),
     'edge_ragged': ('TGT_EDGE_RAGGED', False, 'flag', 'the persistent edge row kernels skip the 32-row tiles that hold padded rows only (tgt_edge_linear_live): one live tile list per forward from the node counts; needs tri_ragged, and a model whose triplet modules all take node counts (the attention family)'),
+    'node_ragged': ('TGT_NODE_RAGGED', False, 'flag', 'node attention skips the padded nodes of every graph (tgt_node_attention_*_counts: the key-blocked forward, the backwards up to 64 nodes); the count then bounds rows as well as columns of the mask (two more small launches per forward); needs tri_ragged, and a model whose triplet modules all take node counts (the attention family)'),
     'defer_sums': ('TGT_DEFER_SUMS', False, 'flag', 'closing sums of the backward collected into one launch (measured slower)'),
     'defer_max': ('TGT_DEFER_MAX', 56, 'int', 'sums per queue before it flushes itself'),
     'epi_ln_bwd': ('TGT_EPI_LN_BWD', True, 'flag', 'LayerNorm backward as the epilogue of the data-gradient GEMM'),
@@ -81,6 +82,7 @@ class Knobs:
     tri_ragged: bool
     tri_ragged_kb: bool
     edge_ragged: bool
+    node_ragged: bool
     defer_sums: bool
     defer_max: int
     epi_ln_bwd: bool

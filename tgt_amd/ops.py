@@ -1089,12 +1089,13 @@ def _node_args(qkv, eg, mask3, H, scale_degree, logits_only):
 
 class _NodeAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, eg, mask3, H, scale_degree, want_edges, hhat_scale=None):
-        _dev(qkv, eg, mask3, hhat_scale)
+    def forward(ctx, qkv, eg, mask3, H, scale_degree, want_edges, hhat_scale=None, node_counts=None):
+        _dev(qkv, eg, mask3, hhat_scale, node_counts)
         qkv, eg = qkv.contiguous(), eg.contiguous()
         if eg.dtype != qkv.dtype:
             eg = eg.to(qkv.dtype)
         B, N = qkv.shape[0], qkv.shape[1]
+        _check_per_graph(node_counts, B, torch.int32, 'node attention: node_counts')
         a, W = _node_args(qkv, eg, mask3, H, scale_degree, False)
         D = W // H
         tiles = qkv.dtype != torch.float32 and H % 8 == 0 and D in (8, 12, 16)       # the shapes the matrix-core families take at all
@@ -1118,8 +1119,11 @@ class _NodeAttention(torch.autograd.Function):
         gsum = torch.empty(B, N, H, dtype=torch.float32, device=qkv.device)
         a.vatt, a.hhat, a.lse, a.gsum = vatt.data_ptr(), _ptr(hhat), lse.data_ptr(), gsum.data_ptr()
         a.hhat_scale = _ptr(hhat_scale)
-        _launch('tgt_node_attention_fwd', C.byref(a), prof='tgt_node_attention_fwd')
-        ctx.save_for_backward(qkv, eg, mask3, lse, gsum, vatt, hhat_scale)
+        if node_counts is None:
+            _launch('tgt_node_attention_fwd', C.byref(a), prof='tgt_node_attention_fwd')
+        else:              # (ragged: tgt_hip.h, tgt_node_attention_fwd_counts -- the backward below gets the same counts)
+            _launch('tgt_node_attention_fwd_counts', C.byref(a), _ptr(node_counts), prof='tgt_node_attention_fwd')
+        ctx.save_for_backward(qkv, eg, mask3, lse, gsum, vatt, hhat_scale, node_counts)
         ctx.cfg = (H, scale_degree, want_edges)
         if want_edges:
             return vatt, hhat
@@ -1127,7 +1131,7 @@ class _NodeAttention(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_vatt, d_hhat):
-        qkv, eg, mask3, lse, gsum, vatt, hhat_scale = ctx.saved_tensors
+        qkv, eg, mask3, lse, gsum, vatt, hhat_scale, node_counts = ctx.saved_tensors
         H, scale_degree, want_edges = ctx.cfg
         a, W = _node_args(qkv, eg, mask3, H, scale_degree, False)
         d_vatt = torch.zeros_like(qkv[..., :W]).contiguous() if d_vatt is None else d_vatt.contiguous()
@@ -1137,17 +1141,24 @@ class _NodeAttention(torch.autograd.Function):
         a.lse, a.gsum, a.vatt = lse.data_ptr(), gsum.data_ptr(), vatt.data_ptr()
         a.d_vatt, a.d_hhat, a.d_qkv, a.d_eg = d_vatt.data_ptr(), _ptr(d_hhat), d_qkv.data_ptr(), d_eg.data_ptr()
         a.hhat_scale = _ptr(hhat_scale)
-        _launch('tgt_node_attention_bwd', C.byref(a), prof='tgt_node_attention_bwd')
-        return d_qkv, d_eg, None, None, None, None, None
+        if node_counts is None:
+            _launch('tgt_node_attention_bwd', C.byref(a), prof='tgt_node_attention_bwd')
+        else:
+            _launch('tgt_node_attention_bwd_counts', C.byref(a), _ptr(node_counts), prof='tgt_node_attention_bwd')
+        return d_qkv, d_eg, None, None, None, None, None, None
 
 
-def node_attention(qkv, eg, mask3, num_heads, scale_degree=True, want_edges=True, hhat_scale=None):
+def node_attention(qkv, eg, mask3, num_heads, scale_degree=True, want_edges=True, hhat_scale=None, node_counts=None):
     """qkv (B,N,3W) and eg (B,N,N,2H) in the reference's head-minor layout (channel = d*H + h);
     returns V_att (B,N,W) and H_hat (B,N,N,H) (or None).
     hhat_scale (B,) float32: H_hat is returned multiplied by hhat_scale[b] (the DropPath factor of the edge branch it
     feeds, folded in: linear_residual_layer_norm(prescaled=True)).
+    node_counts (B,) int32 on the device: ragged batches -- the kernel families that honour the count (tgt_hip.h,
+    tgt_node_attention_fwd_counts: the key-blocked forward, the backwards up to 64 nodes) neither load nor compute the nodes
+    >= node_counts[b]: V_att rows and H_hat pairs of padded nodes are zeros, their cotangents are taken as zero.  Exact on the real
+    block when the mask closes every pair with a padded node; the other families ignore the count.
     Reference arithmetic: lib/tgt/layers/layers.py:62-77."""
-    return _NodeAttention.apply(qkv, eg, mask3, num_heads, scale_degree, want_edges, hhat_scale)
+    return _NodeAttention.apply(qkv, eg, mask3, num_heads, scale_degree, want_edges, hhat_scale, node_counts)
 
 
 class _EdgeLogits(torch.autograd.Function):

@@ -98,11 +98,13 @@ class EGT_Attention(nn.Module):
         v_att, e = self.attend(h, e_hat, mask, e, qkv)
         return self.lin_O_h(v_att), e
 
-    def attend(self, h, e_hat, mask, e=None, qkv=None, project_edges=True, hhat_scale=None):
+    def attend(self, h, e_hat, mask, e=None, qkv=None, project_edges=True, hhat_scale=None, node_counts=None):
         """(V_att before lin_O_h, updated edge channels): forward_normed without the node output
         projection, which TGT_Layer runs on the node stream together with the node FFN.
         project_edges=False: return H_hat itself; the caller fuses lin_O_e with what follows it (hhat_scale: H_hat
-        comes back multiplied by that per-graph factor, the DropPath of the branch it feeds)"""
+        comes back multiplied by that per-graph factor, the DropPath of the branch it feeds)
+        node_counts (B,) int32: ragged batches (ops.node_attention) -- every pair with a node >= node_counts[b] must be closed by
+        the mask"""
         B, N = h.shape[0], h.shape[1]
         if qkv is None:
             qkv = self.project_nodes(h)
@@ -113,7 +115,7 @@ class EGT_Attention(nn.Module):
             # caller's mask is left untouched (the triplet module sees it un-dropped)
             mask3 = mask3 + ops.source_drop_mask(B, N, self.source_dropout, torch.finfo(mask.dtype).min, h.device)
         v_att, h_hat = ops.node_attention(qkv, eg, mask3, self.num_heads,
-                                          self.scale_degree, self.edge_update, hhat_scale=hhat_scale)
+                                          self.scale_degree, self.edge_update, hhat_scale=hhat_scale, node_counts=node_counts)
         if self.edge_update:
             e = self.lin_O_e(h_hat) if project_edges else h_hat
         return v_att, e
@@ -293,8 +295,10 @@ class TGT_Layer(nn.Module):
         sc_oe = ops.drop_path_scale(e_hat, dp, tr) if fuse_oe else None      # (drawn here whether it is folded or not)
         fold_oe = sc_oe is not None and ops.can_prescale(pair_rows, self.update.num_heads, e_hat.shape[-1], cd)
         if self.node_update:
+            # (ragged batches under TGT_NODE_RAGGED: TGT_Encoder marks the graph when the counts bound rows and columns of the mask)
             v_att, e = self.update.attend(h, e_hat, mask, e, qkv, project_edges=not fuse_oe,
-                                          hhat_scale=sc_oe if fold_oe else None)   # lin_O_h follows on the node stream
+                                          hhat_scale=sc_oe if fold_oe else None,   # lin_O_h follows on the node stream
+                                          node_counts=g.get('node_counts') if g.get('node_ragged') else None)
         else:
             h, e = self.update.forward_normed(h, e_hat, mask, e, qkv)
         # Each residual add is fused with the LayerNorm that opens the next sub-block

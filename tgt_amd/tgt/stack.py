@@ -1,6 +1,7 @@
 """The layer stack (`TGT_Encoder`) and the attribute-style batch container (`Graph`).
 Same public behaviour and state_dict prefixes (`TGT_layers.{i}.`) as the reference's
 lib/tgt/encoder.py."""
+import torch
 from torch import nn
 
 from .. import ops
@@ -12,6 +13,7 @@ from .layers.blocks import PendingResidual
 _DEFER_EDGE = K.defer_edge      # A/B knob (tgt_amd/knobs.py)
 _TRI_RAGGED = K.tri_ragged      # triplet attention skips the padded nodes of every graph (default off)
 _EDGE_RAGGED = K.edge_ragged    # the edge row kernels skip the tiles of padded rows (default off; needs _TRI_RAGGED)
+_NODE_RAGGED = K.node_ragged    # node attention skips the padded nodes too (default off; needs _TRI_RAGGED)
 
 
 class Graph(dict):
@@ -73,19 +75,39 @@ class TGT_Encoder(nn.Module):
         """may the edge row kernels leave the padded rows out?  Only when no layer lets a padded row reach a real one: a triplet
         module must take the node counts (the attention family: every key of a padded node is masked).  The aggregate family's
         gated outward direction is unmasked (quirk Q2), so its padded rows DO reach real outputs: such a model computes everything."""
+        return self._padding_is_unread('edge_ragged', 'TGT_EDGE_RAGGED has no effect on this model: a triplet module that does not take '
+                                       'node counts (the aggregate family) reads padded rows; every edge row is computed')
+
+    def _padding_is_unread(self, key, notice):
+        """does every triplet module take the node counts?  (one predicate for every switch that changes padded rows of the edge
+        stream; `notice` is said once, under `key`, when it does not hold)"""
         ok = all(getattr(layer.tria, 'takes_node_counts', False) for layer in self.TGT_layers if hasattr(layer, 'tria'))
         if not ok:
-            ops._slow_path_notice('edge_ragged', 'TGT_EDGE_RAGGED has no effect on this model: a triplet module that does not take '
-                                  'node counts (the aggregate family) reads padded rows; every edge row is computed')
+            ops._slow_path_notice(key, notice)
         return ok
+
+    def _node_ragged_ok(self):
+        """may node attention leave the padded nodes out?  Its H_hat is then zero at padded pairs instead of a finite value, which
+        is the edge stream's padded rows: the gate of _edge_ragged_ok, for the same reason (an aggregate-family model reads them)."""
+        return self._padding_is_unread('node_ragged', 'TGT_NODE_RAGGED has no effect on this model: a triplet module that does not take '
+                                       'node counts (the aggregate family) reads padded rows; node attention computes every node')
 
     def forward(self, inputs):
         graph = Graph(inputs)
         # ragged batches: the per-graph node counts the triplet attention kernels skip behind, once per forward from the mask
         # (one launch, nothing read on the host); a caller that knows num_nodes may put its own int32 `node_counts` in the inputs
         own_counts = _TRI_RAGGED and graph.get('node_counts') is None and graph.mask.is_cuda
+        # ... which node attention honours too under TGT_NODE_RAGGED; its count must bound the ROWS of the mask as well as the columns
+        # (tgt_mask_node_counts guarantees the column half only): the larger of the counts of the mask and of its transpose -- two
+        # small launches more, still nothing on the host.  The triplet modules get the same, larger, count: always safe.
+        node_ragged = bool(_NODE_RAGGED and _TRI_RAGGED and graph.mask.is_cuda and self._node_ragged_ok())
         if own_counts:
-            graph['node_counts'] = ops.mask_node_counts(ops.as_mask3(graph.mask, graph.e.shape[0], graph.e.shape[1]))
+            mask3 = ops.as_mask3(graph.mask, graph.e.shape[0], graph.e.shape[1])
+            graph['node_counts'] = ops.mask_node_counts(mask3)
+            if node_ragged:
+                graph['node_counts'] = torch.maximum(graph['node_counts'], ops.mask_node_counts(mask3.transpose(1, 2).contiguous()))
+        if node_ragged and graph.get('node_counts') is not None:
+            graph['node_ragged'] = True
         # ... and the live tile list the persistent edge row kernels walk (TGT_EDGE_RAGGED): one more launch per forward, carried
         # by an ops context around the layer loop; the padded rows of the edge stream are then zeros in whole dead tiles
         live = None
@@ -102,4 +124,5 @@ class TGT_Encoder(nn.Module):
             side.join(graph.h)
         if own_counts:
             graph.pop('node_counts', None)
+        graph.pop('node_ragged', None)
         return graph
