@@ -99,7 +99,9 @@ typedef struct tgt_triplet_attention_args {
     /* attention dropout on the gated weights (reference triplet.py:223-225, :242-244); 0 = off.
      * Counter-based: the backward must be called with the forward's (p, seed).  Generator:
      * csrc/triplet_common.hpp (tri_drop_bits), unit = ((b*2 + dir)*H + h)*N + j; the hash word of element (i, k) inside a
-     * unit is (i*64 + k) >> 1 for N <= 64 and (i*128 + k) >> 1 for N > 64 (no two pairs of a unit share a 16-bit field). */
+     * unit is (i*64 + k) >> 1 for N <= 64 and (i*128 + k) >> 1 for N > 64 (no two pairs of a unit share a 16-bit field).
+     * With a step counter registered (tgt_set_seed_counter) and dropout_p > 0 the kernels use dropout_seed + *counter *
+     * 0x9E3779B97F4A7C15 (mod 2^64), forward and backward alike; dropout_p == 0 never reads the counter. */
     float    dropout_p;
     uint32_t _pad1;
     uint64_t dropout_seed;
@@ -230,7 +232,8 @@ typedef struct tgt_triplet_aggregate_args {
     void*   d_v[2];
     void*   d_eg[2];
     /* attention dropout on the gated weights (reference triplet.py:59-60, :66-67); 0 = off;
-     * unit = (b*2 + dir)*H + h, otherwise as tgt_triplet_attention_args: word (i*128 + k) >> 1 for N > 64. */
+     * unit = (b*2 + dir)*H + h, otherwise as tgt_triplet_attention_args: word (i*128 + k) >> 1 for N > 64, and the registered
+     * step counter (tgt_set_seed_counter) enters the seed in the same way (tgt_triplet_aggregate_proj*_fwd included). */
     float    dropout_p;
     uint32_t _pad1;
     uint64_t dropout_seed;
@@ -698,11 +701,14 @@ typedef struct tgt_transpose_item { const void* src; void* dst; int32_t rows, co
 typedef struct tgt_sum_item { const float* src; float* dst; int32_t planes; int32_t _pad; int64_t n; } tgt_sum_item;
 int tgt_sum_many(const tgt_sum_item* items, int32_t n, void* stream);
 
-/* ABI 29.  A device-resident 64-bit step counter mixed into every dropout seed of tgt_gelu_dropout_* and tgt_edge_linear
- * (seed' = seed + *counter * 0x9E3779B97F4A7C15): a training step captured in a hipGraph bakes the seeds its host drew into the
+/* ABI 29.  A device-resident 64-bit step counter mixed into every dropout seed of tgt_gelu_dropout_*, tgt_glu_dropout_*,
+ * tgt_edge_linear and -- where dropout_p > 0 -- tgt_triplet_attention_* / tgt_triplet_aggregate_*
+ * (seed' = seed + *counter * 0x9E3779B97F4A7C15 mod 2^64): a step captured in a hipGraph bakes the seeds its host drew into the
  * graph; the counter -- incremented by the graph itself once per replay -- gives each replay its own drop patterns, forward and
- * backward of one step seeing the same value.  Process-wide, read at launch time; NULL (the default) = seeds as given.  The
- * attention-dropout seeds of tgt_triplet_attention_* / tgt_node_attention_* are NOT covered (the captured step refuses p > 0 there).
+ * backward of one step seeing the same value.  Process-wide; the POINTER is read at launch time, the value by the kernels (an
+ * ordinary load, nothing is stored through it); NULL (the default) = seeds as given, bit for bit.  The triplet kernels that
+ * require dropout_p == 0 (tgt_triplet_attention_proj*_fwd, the 16-wide tiles, tri_att_bwd2) and tgt_node_attention_* (no dropout
+ * inside) do not take it.
  * Replaces nothing in the reference: torch's own graph-safe Philox offsets play this role for its dropout under CUDA graphs. */
 int tgt_set_seed_counter(const void* device_counter);
 int tgt_transpose_many(const tgt_transpose_item* items, int32_t n, int32_t blocks_per_item, void* stream);

@@ -31,7 +31,7 @@ __device__ __forceinline__ void agg_weights(const AggCtx& c, int N, int wave, in
 }
 
 template <typename T, int D, int HG, int NT, typename... GS>
-__global__ void __launch_bounds__(HG * 64) tri_agg_fwd_kernel(const tgt_triplet_aggregate_args a, GS... gs) {
+__global__ void __launch_bounds__(HG * 64) tri_agg_fwd_kernel(const tgt_triplet_aggregate_args a, const uint64_t* seed_ctr, GS... gs) {
     using G = TriGeo<T, D, HG>;
     using F = frag_t<T>;
     constexpr int KR = 32 * NT;
@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_fwd_kernel(const tgt_triplet_
     }
     F ident_d[G::kDC];
     make_ident_d<T, G::kDC>(ident_d, r, hi);
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
     const uint32_t drop_unit = (uint32_t)((c.b * 2 + c.dir) * a.H + c.h);
     const SlabBuf bV = agg_v_slab<T, D, HG>(a.v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);
     const SlabBuf bO = agg_o_slab<T, D, HG>(a.out, a.ld_out, a.o_off[c.dir], c);
@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_fwd_kernel(const tgt_triplet_
 }
 
 template <typename T, int D, int HG, int NT, typename... GS>
-__global__ void __launch_bounds__(HG * 64) tri_agg_bwd_kernel(const tgt_triplet_aggregate_args a, GS... gs) {
+__global__ void __launch_bounds__(HG * 64) tri_agg_bwd_kernel(const tgt_triplet_aggregate_args a, const uint64_t* seed_ctr, GS... gs) {
     using G = TriGeo<T, D, HG>;
     using F = frag_t<T>;
     constexpr int KR = 32 * NT;
@@ -130,7 +130,7 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_bwd_kernel(const tgt_triplet_
 
     F ident_d[G::kDC];
     make_ident_d<T, G::kDC>(ident_d, r, hi);
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
     const uint32_t drop_unit = (uint32_t)((c.b * 2 + c.dir) * a.H + c.h);
     const SlabBuf bV = agg_v_slab<T, D, HG>(a.v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);
     const SlabBuf dV = agg_v_slab<T, D, HG>(a.d_v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);      // d_v mirrors v
@@ -266,8 +266,8 @@ static int launch_agg_nt(const tgt_triplet_aggregate_args& a, bool bwd, hipStrea
     const int grid = a.B * 2 * (a.H / HG);
     constexpr int kArm = ArmStage<T, HG, NT>::kBytes;
     constexpr int kLds = 2 * (NT + 1) * G::kSlabBytes > kArm ? 2 * (NT + 1) * G::kSlabBytes : kArm;
-    if (!bwd) hipLaunchKernelGGL((tri_agg_fwd_kernel<T, D, HG, NT, GS...>), dim3(grid), dim3(G::kThreads), kLds, st, a, gs...);
-    else      hipLaunchKernelGGL((tri_agg_bwd_kernel<T, D, HG, NT, GS...>), dim3(grid), dim3(G::kThreads), kLds, st, a, gs...);
+    if (!bwd) hipLaunchKernelGGL((tri_agg_fwd_kernel<T, D, HG, NT, GS...>), dim3(grid), dim3(G::kThreads), kLds, st, a, seed_counter(), gs...);
+    else      hipLaunchKernelGGL((tri_agg_bwd_kernel<T, D, HG, NT, GS...>), dim3(grid), dim3(G::kThreads), kLds, st, a, seed_counter(), gs...);
     return check_launch(bwd ? "tri_agg_bwd_kernel" : "tri_agg_fwd_kernel");
 }
 template <typename T, int D, int HG, typename... GS>

@@ -58,7 +58,7 @@ __device__ __forceinline__ f32x16 agg_kb_dropped(const float (&p)[16], const flo
 // forward
 // ---------------------------------------------------------------------------
 template <typename T, int HG, typename... GS>
-__global__ void __launch_bounds__(HG * 64) tri_agg_kb_fwd_kernel(const tgt_triplet_aggregate_args a, GS... gs) {
+__global__ void __launch_bounds__(HG * 64) tri_agg_kb_fwd_kernel(const tgt_triplet_aggregate_args a, const uint64_t* seed_ctr, GS... gs) {
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
     // two LDS sets {V (128 rows) | O (32)}: set j&1 is computed on while slab j+1 lands in the other one -> ONE barrier per j
@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_fwd_kernel(const tgt_tripl
     }
     F ident_d[1];
     make_ident_d<T, 1>(ident_d, r, hi);
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
     const uint32_t drop_unit = (uint32_t)((c.b * 2 + c.dir) * a.H + c.h);
     const SlabBuf bV = agg_v_slab<T, 16, HG>(a.v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);
     const SlabBuf bO = agg_o_slab<T, 16, HG>(a.out, a.ld_out, a.o_off[c.dir], c);
@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_fwd_kernel(const tgt_tripl
 // backward, A sweep: dE / dG of (query tile, all keys)
 // ---------------------------------------------------------------------------
 template <typename T, int HG, typename... GS>
-__global__ void __launch_bounds__(HG * 64) tri_agg_kb_bwd_a_kernel(const tgt_triplet_aggregate_args a, GS... gs) {
+__global__ void __launch_bounds__(HG * 64) tri_agg_kb_bwd_a_kernel(const tgt_triplet_aggregate_args a, const uint64_t* seed_ctr, GS... gs) {
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_bwd_a_kernel(const tgt_tri
             arm_stage_zero_grad<T, HG, 1>(c.ta, a.d_eg[c.dir], c.b, c.dir, c.g, N, i0, smem, wave, tid, r, hi, 32 * kt);
         return;
     }
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
     const uint32_t drop_unit = (uint32_t)((c.b * 2 + c.dir) * a.H + c.h);
     const SlabBuf bV = agg_v_slab<T, 16, HG>(a.v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);
     const SlabBuf dO = agg_o_slab<T, 16, HG>(a.d_out, a.ld_out, a.o_off[c.dir], c);
@@ -224,7 +224,7 @@ __global__ void __launch_bounds__(HG * 64) tri_agg_kb_bwd_a_kernel(const tgt_tri
 // tiles of them spill, so fp32 takes 2 and twice the workgroups.
 // ---------------------------------------------------------------------------
 template <typename T, int HG, int KT, typename... GS>
-__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_agg_kb_bwd_v_kernel(const tgt_triplet_aggregate_args a, GS... gs) {
+__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_agg_kb_bwd_v_kernel(const tgt_triplet_aggregate_args a, const uint64_t* seed_ctr, GS... gs) {
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     }
     F ident_d[1];
     make_ident_d<T, 1>(ident_d, r, hi);
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
     const uint32_t drop_unit = (uint32_t)((c.b * 2 + c.dir) * a.H + c.h);
     const SlabBuf dV = agg_v_slab<T, 16, HG>(a.d_v[c.dir], a.ld_v[c.dir], a.v_off[c.dir], c);      // d_v mirrors v
     const SlabBuf dO = agg_o_slab<T, 16, HG>(a.d_out, a.ld_out, a.o_off[c.dir], c);
@@ -335,13 +335,13 @@ static int launch_agg_kb(const tgt_triplet_aggregate_args& a, bool bwd, hipStrea
     constexpr int kArm = ArmStage<T, HG, 1>::kBytes;
     constexpr int kWalkLds = cmax(10 * G::kSlabBytes, kArm), kVLds = cmax(8 * G::kSlabBytes, kArm);
     static_assert(kWalkLds <= 160 * 1024 && kVLds <= 160 * 1024, "LDS of a CU");
-    if (!bwd) return launch_lds<tri_agg_kb_fwd_kernel<T, HG, GS...>>("tri_agg_kb_fwd_kernel", dim3(grid), dim3(G::kThreads), kWalkLds, st, a, gs...);
+    if (!bwd) return launch_lds<tri_agg_kb_fwd_kernel<T, HG, GS...>>("tri_agg_kb_fwd_kernel", dim3(grid), dim3(G::kThreads), kWalkLds, st, a, seed_counter(), gs...);
     constexpr int KT = sizeof(T) == 2 ? 4 : 2;
     // (both reservations before the first launch: a failed one leaves nothing half-written)
     if (int rc = reserve_lds<tri_agg_kb_bwd_a_kernel<T, HG, GS...>>("tri_agg_kb_bwd_a_kernel", kWalkLds)) return rc;
     if (int rc = reserve_lds<tri_agg_kb_bwd_v_kernel<T, HG, KT, GS...>>("tri_agg_kb_bwd_v_kernel", kVLds)) return rc;
-    if (int rc = launch_lds<tri_agg_kb_bwd_a_kernel<T, HG, GS...>>("tri_agg_kb_bwd_a_kernel", dim3(grid), dim3(G::kThreads), kWalkLds, st, a, gs...)) return rc;
-    return launch_lds<tri_agg_kb_bwd_v_kernel<T, HG, KT, GS...>>("tri_agg_kb_bwd_v_kernel", dim3(grid, 4 / KT), dim3(G::kThreads), kVLds, st, a, gs...);
+    if (int rc = launch_lds<tri_agg_kb_bwd_a_kernel<T, HG, GS...>>("tri_agg_kb_bwd_a_kernel", dim3(grid), dim3(G::kThreads), kWalkLds, st, a, seed_counter(), gs...)) return rc;
+    return launch_lds<tri_agg_kb_bwd_v_kernel<T, HG, KT, GS...>>("tri_agg_kb_bwd_v_kernel", dim3(grid, 4 / KT), dim3(G::kThreads), kVLds, st, a, seed_counter(), gs...);
 }
 // graph_scale NULL: the kernels' instantiations without the argument (triplet_common.hpp, agg_dead)
 template <typename T>

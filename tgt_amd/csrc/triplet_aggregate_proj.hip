@@ -39,7 +39,7 @@ struct Geo : TriGeo<T, kD, kH> {
 
 template <typename T, typename... GS>
 __global__ void __launch_bounds__(aggproj::kThreads, 4) tri_agg_proj_fwd_kernel(const tgt_triplet_aggregate_args a, const T* x, const T* w,
-                                                                             const T* bias, GS... gs) {
+                                                                             const T* bias, const uint64_t* seed_ctr, GS... gs) {
     using namespace aggproj;
     using G = Geo<T>;
     using F = frag_t<T>;
@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(aggproj::kThreads, 4) tri_agg_proj_fwd_kernel(
         slab_zero_units<G>(0, N, 0, N, tid, agg_o_slab<T, kD, kH>(a.out, a.ld_out, a.o_off[dir], c));
         return;
     }
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
 
     // ---- the weights A[i,k] of the two heads, once (the stage aliases the walk's buffers).
     // INVARIANT (part of the entry point's contract, include/tgt_hip.h): ALL of this direction's E/G is read here, and the barrier
@@ -175,7 +175,7 @@ static int launch_agg_proj(const tgt_triplet_aggregate_args& a, const void* x, c
     constexpr int kArm = ArmStage<T, aggproj::kH, 1>::kBytes;
     constexpr int kLds = cmax(aggproj::kWalk, kArm);
     return launch_lds<tri_agg_proj_fwd_kernel<T, GS...>>("tri_agg_proj_fwd_kernel", dim3(a.B * 2), dim3(aggproj::kThreads), kLds, st, a,
-                                                         reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias), gs...);
+                                                         reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias), seed_counter(), gs...);
 }
 
 int triplet_aggregate_proj_run(const tgt_triplet_aggregate_args* a, const float* graph_scale, const void* x, int C, const void* w, const void* bias,

@@ -44,7 +44,7 @@ struct Geo : TriGeo<T, kD, kH> {
 
 template <typename T, typename... GS>
 __global__ void __launch_bounds__(aggproj64::kThreads, 2) tri_agg_proj64_fwd_kernel(const tgt_triplet_aggregate_args a, const T* x, const T* w,
-                                                                                 const T* bias, GS... gs) {
+                                                                                 const T* bias, const uint64_t* seed_ctr, GS... gs) {
     using namespace aggproj64;
     using G = Geo<T>;
     using F = frag_t<T>;
@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(aggproj64::kThreads, 2) tri_agg_proj64_fwd_ker
         for (int i0 = 0; i0 < N; i0 += 32) slab_zero_units<G>(0, N, i0, N, tid, zO);
         return;
     }
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
 
     // ---- the weights A[i,k] of the two heads, both query tiles x both key tiles, once (the stage aliases the walk's buffers; it
     // holds one 32-row query pass, so two passes).
@@ -201,7 +201,7 @@ static int launch_agg_proj64(const tgt_triplet_aggregate_args& a, const void* x,
     constexpr int kLds = cmax(aggproj64::kWalk, kArm);
     static_assert(kLds <= 160 * 1024, "one workgroup must fit the LDS of a CU");
     return launch_lds<tri_agg_proj64_fwd_kernel<T, GS...>>("tri_agg_proj64_fwd_kernel", dim3(a.B * 2), dim3(aggproj64::kThreads), kLds, st, a,
-                                                           reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias), gs...);
+                                                           reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(w), reinterpret_cast<const T*>(bias), seed_counter(), gs...);
 }
 
 // (check order and words: triplet_aggregate_proj_run)

@@ -40,7 +40,7 @@ namespace tgt {
 // per query tile `it`; inside a pass the key axis spans all NT tiles.
 // ---------------------------------------------------------------------------
 template <typename T, int D, int HG, int NT, int PF, bool DROP, bool RG>
-__global__ void __launch_bounds__(HG * 64, (NT == 1 && sizeof(T) == 2) ? 4 : (sizeof(T) == 2 ? 2 : 1)) tri_att_fwd_kernel(const tgt_triplet_attention_args a, const int32_t* node_counts) {
+__global__ void __launch_bounds__(HG * 64, (NT == 1 && sizeof(T) == 2) ? 4 : (sizeof(T) == 2 ? 2 : 1)) tri_att_fwd_kernel(const tgt_triplet_attention_args a, const int32_t* node_counts, const uint64_t* seed_ctr) {
     using G = TriGeo<T, D, HG>;
     using F = frag_t<T>;
     constexpr int KR = 32 * NT;
@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(HG * 64, (NT == 1 && sizeof(T) == 2) ? 4 : (si
     const ThirdArm ta = tri_third_arm(a, c.dir);
     F ident_d[G::kDC];
     make_ident_d<T, G::kDC>(ident_d, r, hi);
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
     const uint32_t drop_unit0 = (uint32_t)(((c.b * 2 + c.dir) * a.H + c.h) * N);
 
     // buffer-addressed slabs (triplet_common.hpp): scalar offsets along j, no vector address arithmetic
@@ -230,7 +230,7 @@ __device__ __forceinline__ unsigned long long probe_now() {
 // per-element selects); FL < 0: read from the arguments.
 template <typename T, int D, int HG, int NT, int OCC, bool CS, int FL, bool DROP, bool RG>
 // (waves_per_eu(1,1) for the one-wave variants: lets the allocator park values in the 256 AGPRs instead of scratch)
-__global__ void __launch_bounds__(HG * 64, OCC) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) tri_att_bwd_kernel(const tgt_triplet_attention_args a, const int32_t* node_counts) {
+__global__ void __launch_bounds__(HG * 64, OCC) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) tri_att_bwd_kernel(const tgt_triplet_attention_args a, const int32_t* node_counts, const uint64_t* seed_ctr) {
     using G = TriGeo<T, D, HG>;
     using F = frag_t<T>;
     constexpr int KR = 32 * NT;
@@ -250,7 +250,7 @@ __global__ void __launch_bounds__(HG * 64, OCC) __attribute__((amdgpu_waves_per_
     const int N = c.N;
     const ThirdArm ta = tri_third_arm(a, c.dir);
     const bool biased = FL >= 0 ? (FL & TGT_TRI_BIASED) != 0 : ta.biased, gated = FL >= 0 ? (FL & TGT_TRI_GATED) != 0 : ta.gated;
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
     const uint32_t drop_unit0 = (uint32_t)(((c.b * 2 + c.dir) * a.H + c.h) * N);
     constexpr float kLog2e = 1.4426950408889634f;
     const float scale2 = a.scale * kLog2e;          // logits in the log2 domain: exp2 without the per-element multiply
@@ -655,10 +655,10 @@ static int launch_tri_rg(const tgt_triplet_attention_args& a_in, const int32_t* 
     if (!bwd) {
         // (a prefetch depth of 2 was measured neutral in round 1 and is gone)
         if (drop)
-            hipLaunchKernelGGL((tri_att_fwd_kernel<T, D, HG, NT, 1, true, RG>), dim3(grid), dim3(G::kThreads), kFwdLds, st, a, nc);
+            hipLaunchKernelGGL((tri_att_fwd_kernel<T, D, HG, NT, 1, true, RG>), dim3(grid), dim3(G::kThreads), kFwdLds, st, a, nc, seed_counter());
         else
             hipLaunchKernelGGL((tri_att_fwd_kernel<T, D, HG, NT, 1, false, RG>), dim3(grid), dim3(G::kThreads),
-                               kFwdLds, st, a, nc);
+                               kFwdLds, st, a, nc, seed_counter());
     } else {
         // one node tile: registers capped for 2 waves per SIMD (kOcc)
         const bool cs = a.d_qkv_colsum[0] != nullptr;
@@ -668,29 +668,29 @@ static int launch_tri_rg(const tgt_triplet_attention_args& a_in, const int32_t* 
         if (drop) {                 // attention dropout (p = 0 in every shipped config): one generic variant each
             if (cs)
                 hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, true, -1, true, RG>), dim3(grid), dim3(G::kThreads),
-                                   kBwdLds + kCs, st, a, nc);
+                                   kBwdLds + kCs, st, a, nc, seed_counter());
             else
                 hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, false, -1, true, RG>), dim3(grid), dim3(G::kThreads),
-                                   kBwdLds, st, a, nc);
+                                   kBwdLds, st, a, nc, seed_counter());
         } else if (NT == 1) {
             if (cs && HG == 8 && (a.flags & kBG) == kBG)         // the training hot path: flags compiled in
                 hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, true, (HG == 8 ? kBG : -1), false, RG>), dim3(grid),
-                                   dim3(G::kThreads), kBwdLds + kCs, st, a, nc);
+                                   dim3(G::kThreads), kBwdLds + kCs, st, a, nc, seed_counter());
             else if (cs)
                 hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, true, -1, false, RG>), dim3(grid),
-                                   dim3(G::kThreads), kBwdLds + kCs, st, a, nc);
+                                   dim3(G::kThreads), kBwdLds + kCs, st, a, nc, seed_counter());
             else
                 hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc, false, -1, false, RG>), dim3(grid),
-                                   dim3(G::kThreads), kBwdLds, st, a, nc);
+                                   dim3(G::kThreads), kBwdLds, st, a, nc, seed_counter());
         } else {
             // two node tiles (N in 33..64): TGT_NT2_OCC waves per SIMD (register cap 512 / TGT_NT2_OCC)
             constexpr int kOcc2 = NT == 2 ? TGT_NT2_OCC : 1;
             if (cs)
                 hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc2, true, -1, false, RG>), dim3(grid), dim3(G::kThreads),
-                                   kBwdLds + kCs, st, a, nc);
+                                   kBwdLds + kCs, st, a, nc, seed_counter());
             else
                 hipLaunchKernelGGL((tri_att_bwd_kernel<T, D, HG, NT, kOcc2, false, -1, false, RG>), dim3(grid), dim3(G::kThreads),
-                                   kBwdLds, st, a, nc);
+                                   kBwdLds, st, a, nc, seed_counter());
         }
     }
     return check_launch(bwd ? "tri_att_bwd_kernel" : "tri_att_fwd_kernel");

@@ -49,7 +49,7 @@ __device__ __forceinline__ float* kb_stats(const tgt_triplet_attention_args& a, 
 // forward
 // ---------------------------------------------------------------------------
 template <typename T, int HG, bool PF, typename... NC>
-__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_fwd_kernel(const tgt_triplet_attention_args a, NC... nc) {
+__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_fwd_kernel(const tgt_triplet_attention_args a, const uint64_t* seed_ctr, NC... nc) {
     constexpr bool RG = sizeof...(NC) > 0;          // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     const ThirdArm ta = tri_third_arm(a, c.dir);
     F ident_d[1];
     make_ident_d<T, 1>(ident_d, r, hi);
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
     const uint32_t drop_unit0 = (uint32_t)(((c.b * 2 + c.dir) * a.H + c.h) * N);
 
     const int64_t sz = sizeof(T), Nl = N;
@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
 // backward, E sweep (EG = true): statistics, dE / dG;  Q sweep (EG = false): dQ from the E sweep's statistics
 // ---------------------------------------------------------------------------
 template <typename T, int HG, bool PF, bool EG, typename... NC>
-__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_bwd_q_kernel(const tgt_triplet_attention_args a, NC... nc) {
+__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_bwd_q_kernel(const tgt_triplet_attention_args a, const uint64_t* seed_ctr, NC... nc) {
     constexpr bool RG = sizeof...(NC) > 0;          // ragged: as tri_kb_fwd_kernel
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
@@ -198,7 +198,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     const ThirdArm ta = tri_third_arm(a, c.dir);
     F ident_d[1];
     make_ident_d<T, 1>(ident_d, r, hi);
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
     const uint32_t drop_unit0 = (uint32_t)(((c.b * 2 + c.dir) * a.H + c.h) * N);
 
     const int64_t sz = sizeof(T), Nl = N;
@@ -390,7 +390,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
 // backward, K sweep: dK, dV.  Lane = key k of the owned tile, register q <-> query i = 32*it + acc_row(q, hi).
 // ---------------------------------------------------------------------------
 template <typename T, int HG, bool PF, typename... NC>
-__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_bwd_k_kernel(const tgt_triplet_attention_args a, NC... nc) {
+__global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) tri_kb_bwd_k_kernel(const tgt_triplet_attention_args a, const uint64_t* seed_ctr, NC... nc) {
     constexpr bool RG = sizeof...(NC) > 0;          // ragged: as tri_kb_fwd_kernel, with the roles of query and key tiles exchanged
     using G = TriGeo<T, 16, HG>;
     using F = frag_t<T>;
@@ -408,7 +408,7 @@ __global__ void __launch_bounds__(HG * 64, 1) __attribute__((amdgpu_waves_per_eu
     const ThirdArm ta = tri_third_arm(a, c.dir);
     F ident_d[1];
     make_ident_d<T, 1>(ident_d, r, hi);
-    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed);
+    const TriDrop drop = tri_drop(a.dropout_p, a.dropout_seed, seed_ctr);
     const uint32_t drop_unit0 = (uint32_t)(((c.b * 2 + c.dir) * a.H + c.h) * N);
 
     const int64_t sz = sizeof(T), Nl = N;
@@ -556,14 +556,14 @@ static int launch_kb(const tgt_triplet_attention_args& a, bool bwd, hipStream_t 
     const int grid = a.B * 2 * (a.H / HG) * ((a.N + 31) / 32);
     constexpr int kFwdLds = 9 * G::kSlabBytes, kBwdQLds = 10 * G::kSlabBytes, kBwdKLds = 10 * G::kSlabBytes + HG * 384 * 4;
     const dim3 blocks(grid), threads(G::kThreads);
-    if (!bwd) return launch_lds<tri_kb_fwd_kernel<T, HG, kPF, NC...>>("tri_kb_fwd_kernel", blocks, threads, kFwdLds, st, a, nc...);
+    if (!bwd) return launch_lds<tri_kb_fwd_kernel<T, HG, kPF, NC...>>("tri_kb_fwd_kernel", blocks, threads, kFwdLds, st, a, seed_counter(), nc...);
     // (all three reservations before the first launch: a failed one leaves nothing half-written)
     if (int rc = reserve_lds<tri_kb_bwd_q_kernel<T, HG, kPF, true, NC...>>("tri_kb_bwd_e_kernel", kBwdQLds)) return rc;
     if (int rc = reserve_lds<tri_kb_bwd_q_kernel<T, HG, kPF, false, NC...>>("tri_kb_bwd_q_kernel", kBwdQLds)) return rc;
     if (int rc = reserve_lds<tri_kb_bwd_k_kernel<T, HG, kPF, NC...>>("tri_kb_bwd_k_kernel", kBwdKLds)) return rc;
-    if (int rc = launch_lds<tri_kb_bwd_q_kernel<T, HG, kPF, true, NC...>>("tri_kb_bwd_e_kernel", blocks, threads, kBwdQLds, st, a, nc...)) return rc;    // E sweep: statistics first
-    if (int rc = launch_lds<tri_kb_bwd_q_kernel<T, HG, kPF, false, NC...>>("tri_kb_bwd_q_kernel", blocks, threads, kBwdQLds, st, a, nc...)) return rc;
-    return launch_lds<tri_kb_bwd_k_kernel<T, HG, kPF, NC...>>("tri_kb_bwd_k_kernel", blocks, threads, kBwdKLds, st, a, nc...);
+    if (int rc = launch_lds<tri_kb_bwd_q_kernel<T, HG, kPF, true, NC...>>("tri_kb_bwd_e_kernel", blocks, threads, kBwdQLds, st, a, seed_counter(), nc...)) return rc;    // E sweep: statistics first
+    if (int rc = launch_lds<tri_kb_bwd_q_kernel<T, HG, kPF, false, NC...>>("tri_kb_bwd_q_kernel", blocks, threads, kBwdQLds, st, a, seed_counter(), nc...)) return rc;
+    return launch_lds<tri_kb_bwd_k_kernel<T, HG, kPF, NC...>>("tri_kb_bwd_k_kernel", blocks, threads, kBwdKLds, st, a, seed_counter(), nc...);
 }
 template <typename T>
 static int dispatch_kb(const tgt_triplet_attention_args& a, const int32_t* nc, bool bwd, hipStream_t st) {

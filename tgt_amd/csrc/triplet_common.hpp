@@ -502,6 +502,11 @@ __device__ __forceinline__ TriDrop tri_drop(float p, uint64_t seed) {
     d.scale = d.on ? 1.f / (1.f - p) : 1.f;
     return d;
 }
+// The same with the registered device step counter (common.hpp, step_seed; the launchers pass seed_counter()) mixed into the seed:
+// a replayed hipGraph draws a new pattern per replay, and forward and backward of one step agree.  p == 0: the counter is not read.
+__device__ __forceinline__ TriDrop tri_drop(float p, uint64_t seed, const uint64_t* ctr) {
+    return tri_drop(p, p > 0.f ? step_seed(seed, ctr) : seed);
+}
 __device__ __forceinline__ uint32_t tri_drop_bits(const TriDrop& d, uint32_t unit, int i, int kt, int hi, int stride = 64) {
     const uint32_t base = mix32(d.seed_lo ^ mix32(unit)) + d.seed_hi;
     uint32_t bits = 0;

@@ -387,6 +387,12 @@ def bump_seed_counter():
         _seed_counter[0].add_(1)
 
 
+def step_seed(seed, counter_value):
+    """the seed a kernel uses for `seed` while the registered device counter holds `counter_value` (csrc/common.hpp, step_seed):
+    seed + counter * 0x9E3779B97F4A7C15 mod 2^64"""
+    return (int(seed) + int(counter_value) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+
 def _host_seed():
     """a 64-bit dropout seed: from torch's CPU generator (no device sync; torch.manual_seed makes it reproducible), or -- graph-safe
     mode -- the position of this call inside the step, spread over 64 bits"""

@@ -14,6 +14,14 @@ Difference in mechanics, not in results: the reference asks the host after EVERY
 was finite; here that accept/skip decision is device state (tgt_sample_commit), and the host reads the sample count once
 after the S forwards it certainly needs (further tries only while samples are missing, at most 2S in total).
 No CPU path: CPU tensors raise.
+
+Graphed form (opt-in, `graphed=`): predict_bins, predict_probs, gap_prediction_step -- and through them prediction_step4eval,
+prediction_step4savebins and two_stage_predict -- take a pcqm.graphed.GraphedSampler captured for the same model, batch shape and
+nb_samples.  One graph replay is then one complete try: the stochastic forward (every dropout of the model draws anew per replay)
+plus the bookkeeping kernels below.  That works because a try never reads device state on the host: accepting or skipping a
+sample (tgt_sample_commit / tgt_gap_commit), the slot it is written to and the gap predictor's input choice
+(`state[0] % num_dist_inputs`, an index_select on a device index) are all evaluated on the device; the host's reads of the valid
+count stay where _sample_loop has them.  The batch is copied into the graph's inputs once per call, not once per sample.
 """
 import json
 import os
@@ -58,24 +66,42 @@ def _sample_loop(nb_samples, one_try, state, what, need_all):
     return valid
 
 
-def predict_bins(model, batch, nb_samples):
-    """(B, S, N, N) bins of S valid stochastic forwards of a distance predictor: argmax of the softmax symmetrised over
-    the pair axes (dist_pred/scheme.py:181-205).  uint8 for <= 256 bins, else uint16 (the reference's saved types)."""
+def _bins_try(logits, out, st, nb_samples):
+    """the bookkeeping of one predict_bins try: the sample's bins into its slot of `out`, then accept / skip (device state only)"""
     L = _lib.lib()
+    _dev(logits)
+    logits = logits.contiguous()
+    B, N, _, NB = logits.shape
+    _lib.check(L.tgt_dist_bins_argmax(_ptr(logits), _DT[logits.dtype], B, N, NB, _ptr(out), out.element_size(),
+                                      nb_samples * N * N, nb_samples, _ptr(st), _stream()), 'tgt_dist_bins_argmax')
+    _lib.check(L.tgt_sample_commit(_ptr(st), nb_samples, _stream()), 'tgt_sample_commit')
+
+
+def _graphed_loop(graphed, model, batch, nb_samples, kind, need_all):
+    """_sample_loop with one graph replay per try: one copy of the batch into the static inputs, empty accumulators, S replays"""
+    graphed.check(model, nb_samples, kind)
+    graphed.load(batch)
+    graphed.reset()
+    return _sample_loop(nb_samples, graphed.sample, graphed.state, kind, need_all=need_all)
+
+
+def predict_bins(model, batch, nb_samples, graphed=None):
+    """(B, S, N, N) bins of S valid stochastic forwards of a distance predictor: argmax of the softmax symmetrised over
+    the pair axes (dist_pred/scheme.py:181-205).  uint8 for <= 256 bins, else uint16 (the reference's saved types).
+    graphed: a GraphedSampler(model, example, nb_samples, 'bins') -- every try is one graph replay (module docstring)."""
+    if graphed is not None:
+        _graphed_loop(graphed, model, batch, nb_samples, 'bins', need_all=True)
+        return graphed.out.clone()
     st, out = None, None
 
     def one_try():
         nonlocal st, out
         logits = model(batch)
-        _dev(logits)
-        logits = logits.contiguous()
-        B, N, _, NB = logits.shape
         if out is None:
+            B, N, _, NB = logits.shape
             st = _state(logits.device)
             out = torch.empty(B, nb_samples, N, N, dtype=bins_dtype(NB), device=logits.device)
-        _lib.check(L.tgt_dist_bins_argmax(_ptr(logits), _DT[logits.dtype], B, N, NB, _ptr(out), out.element_size(),
-                                          nb_samples * N * N, nb_samples, _ptr(st), _stream()), 'tgt_dist_bins_argmax')
-        _lib.check(L.tgt_sample_commit(_ptr(st), nb_samples, _stream()), 'tgt_sample_commit')
+        _bins_try(logits, out, st, nb_samples)
 
     _sample_loop(nb_samples, one_try, _LazyState(lambda: st), 'bins', need_all=True)
     return out
@@ -91,26 +117,37 @@ class _LazyState:
         return self._get()[i]
 
 
-def predict_probs(model, batch, nb_samples, as_log_eps=None):
+def _probs_try(logits, acc, st, nb_samples):
+    """the bookkeeping of one predict_probs try: softmax into the accumulator, then accept / skip (device state only)"""
+    L = _lib.lib()
+    _dev(logits)
+    logits = logits.contiguous()
+    NB = logits.shape[-1]
+    _lib.check(L.tgt_softmax_accumulate(_ptr(logits), _DT[logits.dtype], logits.numel() // NB, NB, _ptr(acc), _ptr(st),
+                                        nb_samples, _stream()), 'tgt_softmax_accumulate')
+    _lib.check(L.tgt_sample_commit(_ptr(st), nb_samples, _stream()), 'tgt_sample_commit')
+
+
+def predict_probs(model, batch, nb_samples, as_log_eps=None, graphed=None):
     """mean symmetrised bin probabilities over the valid samples, (B,N,N,bins) float32 (dist_pred/scheme.py:139-167);
-    as_log_eps: return log(probs + eps) instead (what prediction_step4eval feeds the cross entropy, :173)"""
+    as_log_eps: return log(probs + eps) instead (what prediction_step4eval feeds the cross entropy, :173).
+    graphed: a GraphedSampler(model, example, nb_samples, 'probs') -- every try is one graph replay (module docstring)."""
     L = _lib.lib()
     st, acc = None, None
 
     def one_try():
         nonlocal st, acc
         logits = model(batch)
-        _dev(logits)
-        logits = logits.contiguous()
         if acc is None:
             st = _state(logits.device)
             acc = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
-        NB = logits.shape[-1]
-        _lib.check(L.tgt_softmax_accumulate(_ptr(logits), _DT[logits.dtype], logits.numel() // NB, NB, _ptr(acc), _ptr(st),
-                                            nb_samples, _stream()), 'tgt_softmax_accumulate')
-        _lib.check(L.tgt_sample_commit(_ptr(st), nb_samples, _stream()), 'tgt_sample_commit')
+        _probs_try(logits, acc, st, nb_samples)
 
-    _sample_loop(nb_samples, one_try, _LazyState(lambda: st), 'probs', need_all=False)
+    if graphed is not None:
+        _graphed_loop(graphed, model, batch, nb_samples, 'probs', need_all=False)
+        st, acc = graphed.state, graphed.acc
+    else:
+        _sample_loop(nb_samples, one_try, _LazyState(lambda: st), 'probs', need_all=False)
     B, N, _, NB = acc.shape
     out = torch.empty_like(acc)
     _lib.check(L.tgt_probs_finish(_ptr(acc), B, N, NB, _ptr(st), 0 if as_log_eps is None else 1,
@@ -118,10 +155,11 @@ def predict_probs(model, batch, nb_samples, as_log_eps=None):
     return out
 
 
-def prediction_step4eval(model, batch, nb_samples, num_dist_bins, range_dist_bins=8):
-    """per-graph cross entropy of log(mean probs + 1e-9) against the binned DFT distances (dist_pred/scheme.py:170-179)"""
+def prediction_step4eval(model, batch, nb_samples, num_dist_bins, range_dist_bins=8, graphed=None):
+    """per-graph cross entropy of log(mean probs + 1e-9) against the binned DFT distances (dist_pred/scheme.py:170-179);
+    graphed: as predict_probs"""
     from ..training.step import coords2dist
-    logp = predict_probs(model, batch, nb_samples, as_log_eps=1e-9)
+    logp = predict_probs(model, batch, nb_samples, as_log_eps=1e-9, graphed=graphed)
     B = logp.shape[0]
     target = (coords2dist(batch['dft_coords']) * ((num_dist_bins - 1) / range_dist_bins)).long().clamp_(0, num_dist_bins - 1)
     xent = ops.cross_entropy_rows(logp.view(-1, num_dist_bins), target.view(-1)).view(B, -1)
@@ -147,9 +185,10 @@ def pack_bins(bins, num_nodes):
     return flat, offsets
 
 
-def prediction_step4savebins(model, batch, nb_samples):
-    """dict(idx, bins): per graph the flat packed bins (numpy), as the reference hands them to pyarrow (:208-229)"""
-    bins = predict_bins(model, batch, nb_samples)
+def prediction_step4savebins(model, batch, nb_samples, graphed=None):
+    """dict(idx, bins): per graph the flat packed bins (numpy), as the reference hands them to pyarrow (:208-229);
+    graphed: as predict_bins"""
+    bins = predict_bins(model, batch, nb_samples, graphed=graphed)
     flat, offsets = pack_bins(bins, batch['num_nodes'])
     flat, off = flat.cpu().numpy(), offsets.cpu().numpy()
     return dict(idx=batch['idx'].cpu().numpy(), bins=[flat[off[i]:off[i + 1]] for i in range(len(off) - 1)])
@@ -180,26 +219,32 @@ def bins2dist(bins, bin_size, shift_half=True, zero_diag=True, num_nodes=None):
     return out
 
 
-def gap_prediction_step(model, batch, nb_samples):
+def _gap_try(model, b, all_d, out, st, nb_samples):
+    """one gap_prediction_step try (device state only): `b` is the batch whose dist_input this try replaces"""
+    B, n_in = all_d.shape[0], all_d.shape[1]
+    slot = (st[0:1] % n_in).long()                                  # device-side `valid_samples % num_dist_inputs`
+    b['dist_input'] = all_d.index_select(1, slot).squeeze(1)
+    g = model(b)
+    g = (g if g.dtype in _DT else g.float()).contiguous()      # (a float64 head: the kernel reads f32/bf16/f16)
+    _lib.check(_lib.lib().tgt_gap_commit(_ptr(g), _DT[g.dtype], B, _ptr(out), nb_samples, _ptr(st), _stream()), 'tgt_gap_commit')
+    return g
+
+
+def gap_prediction_step(model, batch, nb_samples, graphed=None):
     """dict(idx, gap_pred (B, valid samples) float32, gap_target): sample v of the gap predictor runs on
-    dist_input[:, v % num_dist_inputs]; NaN/Inf samples are skipped (gap_pred/scheme.py:78-110)."""
+    dist_input[:, v % num_dist_inputs]; NaN/Inf samples are skipped (gap_pred/scheme.py:78-110).
+    graphed: a GraphedSampler(model, example, nb_samples, 'gap') -- every try is one graph replay (module docstring)."""
     all_d = batch['dist_input']
     assert all_d.ndim == 4
     _dev(all_d)
-    L = _lib.lib()
-    st = _state(all_d.device)
-    B, n_in = all_d.shape[0], all_d.shape[1]
-    out = torch.zeros(B, nb_samples, dtype=torch.float32, device=all_d.device)
-    b = dict(batch)
-
-    def one_try():
-        slot = (st[0:1] % n_in).long()                                  # device-side `valid_samples % num_dist_inputs`
-        b['dist_input'] = all_d.index_select(1, slot).squeeze(1)
-        g = model(b)
-        g = (g if g.dtype in _DT else g.float()).contiguous()      # (a float64 head: the kernel reads f32/bf16/f16)
-        _lib.check(L.tgt_gap_commit(_ptr(g), _DT[g.dtype], B, _ptr(out), nb_samples, _ptr(st), _stream()), 'tgt_gap_commit')
-
-    valid = _sample_loop(nb_samples, one_try, st, 'gap', need_all=False)
+    if graphed is not None:
+        valid = _graphed_loop(graphed, model, batch, nb_samples, 'gap', need_all=False)
+        out = graphed.out.clone()
+    else:
+        st = _state(all_d.device)
+        out = torch.zeros(all_d.shape[0], nb_samples, dtype=torch.float32, device=all_d.device)
+        b = dict(batch)
+        valid = _sample_loop(nb_samples, lambda: _gap_try(model, b, all_d, out, st, nb_samples), st, 'gap', need_all=False)
     res = dict(gap_pred=out[:, :valid], gap_target=batch['target'])
     if 'idx' in batch:
         res['idx'] = batch['idx']
@@ -223,17 +268,24 @@ def prediction_loop(model, batches, prediction_step, predict_in_train=True):
         model.train(was_training)
 
 
-def two_stage_predict(dist_model, gap_model, batch, nb_samples, num_dist_bins, range_dist_bins=8, autocast_dtype=None):
+def two_stage_predict(dist_model, gap_model, batch, nb_samples, num_dist_bins, range_dist_bins=8, autocast_dtype=None, graphed=None):
     """BASELINE config 5 end to end on the device: S sampled bin matrices from the distance predictor
     (predict_bins), turned into the gap predictor's `dist_input` exactly as a save / load round trip through the
     packed-bins files would (triu of the real nodes, bins2dist with the +0.5 shift, commons.py:72-82), then S sampled
-    gap predictions (sample v on bins sample v).  Returns (bins (B,S,N,N), gap_pred (B,S) float32)."""
+    gap predictions (sample v on bins sample v).  Returns (bins (B,S,N,N), gap_pred (B,S) float32).
+    graphed: (GraphedSampler of kind 'bins' on dist_model, GraphedSampler of kind 'gap' on gap_model, sharing one counter: the
+    second is built with counter=first.counter), both captured with this autocast_dtype; the gap sampler's example batch is
+    `batch` with dist_input (B,S,N,N)."""
+    g_bins, g_gap = graphed if graphed is not None else (None, None)
+    for g in (g_bins, g_gap):
+        if g is not None and g.autocast_dtype != autocast_dtype:
+            raise RuntimeError(f'two_stage_predict: a sampler captured under autocast {g.autocast_dtype}, asked for {autocast_dtype}')
     ctx = torch.autocast('cuda', dtype=autocast_dtype) if autocast_dtype is not None else torch.autocast('cuda', enabled=False)
     with torch.no_grad(), ctx:
-        bins = predict_bins(dist_model, batch, nb_samples)
+        bins = predict_bins(dist_model, batch, nb_samples, graphed=g_bins)
         b2 = dict(batch)
         b2['dist_input'] = bins2dist(bins, range_dist_bins / (num_dist_bins - 1), num_nodes=batch['num_nodes'])
-        res = gap_prediction_step(gap_model, b2, nb_samples)
+        res = gap_prediction_step(gap_model, b2, nb_samples, graphed=g_gap)
     return bins, res['gap_pred']
 
 

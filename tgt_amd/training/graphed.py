@@ -8,7 +8,8 @@ it; what a replay must not take from the capture is made a DEVICE value first:
 
   * dropout patterns: the kernels mix a device step counter into their seeds (ops.set_seed_counter, tgt_set_seed_counter); the
     graph starts with `counter += 1`.  DropPath factors and source-dropout masks are drawn by torch inside the graph (its
-    generator is capture-aware).  Attention dropout inside the triplet / node attention kernels is not covered: refused.
+    generator is capture-aware).  Attention dropout inside the triplet kernels (triplet_dropout > 0) reads the same counter; no
+    shipped config trains with it, so a model that has it is still refused unless the caller says `attention_dropout=True`.
   * the learning rate: Adam reads it from the optimizer's control block (Trainer.set_device_lr), refreshed before every replay;
     the bias corrections already use the device-side count of applied steps.
   * the batch: copied into the static tensors the capture saw.
@@ -59,7 +60,8 @@ class GraphedTrainingStep:
     batch will have; warmup: eager steps on it before the capture (allocator, GEMM tuning, autograd hooks) -- they are REAL
     optimizer steps.  The outputs / loss returned by step() are the capture's static tensors (overwritten by the next replay)."""
 
-    def __init__(self, trainer, example_batch, warmup=3, update_losses=False, allow_distributed=False, counter=None):
+    def __init__(self, trainer, example_batch, warmup=3, update_losses=False, allow_distributed=False, counter=None,
+                 attention_dropout=False):
         if not isinstance(trainer, Trainer):
             raise RuntimeError('GraphedTrainingStep: a tgt_amd Trainer is required')
         if trainer.distributed and not allow_distributed:
@@ -71,9 +73,11 @@ class GraphedTrainingStep:
         dev = trainer.flat.param.device
         if dev.type != 'cuda':
             raise RuntimeError('GraphedTrainingStep needs the GPU')
-        if trainer.model.training and _attention_dropout(trainer.model) > 0:
+        if trainer.model.training and _attention_dropout(trainer.model) > 0 and not attention_dropout:
+            # (the triplet kernels mix the step counter into this seed as well: attention_dropout=True lifts the refusal)
             raise RuntimeError('GraphedTrainingStep: attention dropout inside the attention kernels is seeded from the host; '
-                               'a captured step would repeat its pattern (use the eager Trainer)')
+                               'a captured step would repeat its pattern (use the eager Trainer, or pass attention_dropout=True: '
+                               'the kernels then take the pattern from the step counter)')
         self.trainer, self.update_losses = trainer, update_losses
         self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
         # counter given: this graph is one of several on the trainer (GraphedStepCache owns the mode and the counter); warmup may
@@ -183,16 +187,17 @@ class GraphedStepCache:
     graph-safe mode: the same arithmetic a replay performs), the next one is captured and replayed.  Bucket the padding (e.g. to
     multiples of 8 nodes) to keep the number of shapes small -- every graph owns the activations of its shape."""
 
-    def __init__(self, trainer, warmup=2, max_graphs=4, update_losses=False, allow_distributed=False):
+    def __init__(self, trainer, warmup=2, max_graphs=4, update_losses=False, allow_distributed=False, attention_dropout=False):
         if not isinstance(trainer, Trainer):
             raise RuntimeError('GraphedStepCache: a tgt_amd Trainer is required')
         if trainer.distributed and not allow_distributed:
             raise RuntimeError('GraphedStepCache: a single-rank Trainer is required (see GraphedTrainingStep)')
         dev = trainer.flat.param.device
-        if trainer.model.training and _attention_dropout(trainer.model) > 0:
-            raise RuntimeError('GraphedStepCache: attention dropout inside the attention kernels is seeded from the host')
+        if trainer.model.training and _attention_dropout(trainer.model) > 0 and not attention_dropout:
+            raise RuntimeError('GraphedStepCache: attention dropout inside the attention kernels is seeded from the host '
+                               '(attention_dropout=True: see GraphedTrainingStep)')
         self.trainer, self.warmup, self.max_graphs = trainer, max(1, warmup), max(1, max_graphs)
-        self.update_losses, self.allow_distributed = update_losses, allow_distributed
+        self.update_losses, self.allow_distributed, self.attention_dropout = update_losses, allow_distributed, attention_dropout
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)
         ops.graph_safe_rng(True)
         ops.set_seed_counter(self.counter)
@@ -257,7 +262,8 @@ class GraphedStepCache:
                 self.graphs.pop(old_key).close()
                 self.evictions += 1
             gs = GraphedTrainingStep(self.trainer, batch, warmup=0, update_losses=self.update_losses,
-                                     allow_distributed=self.allow_distributed, counter=self.counter)
+                                     allow_distributed=self.allow_distributed, counter=self.counter,
+                                     attention_dropout=self.attention_dropout)
             self.captures += 1
         else:
             self._recent.append(0)

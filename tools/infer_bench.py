@@ -8,7 +8,13 @@ on one MI355X.  One JSON line per configuration.
         predict_in_train) of TGT_Distance -> argmax bins of the symmetrised softmax -> bins2dist on the device ->
         S stochastic forwards of TGT_Gap, one per bins sample (tgt_amd/pcqm/predict.py::two_stage_predict)
 
+  mc    (opt-in: --only mc)  MC-dropout prediction of one small batch: train mode (predict_in_train), bf16 autocast, --mc-graphs
+        graphs of --nodes nodes, predict_bins with --samples stochastic forwards per batch, on TGT-At 24L and TGT-Agx2 12x2 distance
+        predictors: the eager loop against one graph replay per sample (pcqm/graphed.py::GraphedSampler), alternating in one
+        process, --reps repetitions each; median and spread (min..max) of the time per batch
+
 python tools/infer_bench.py [--samples 4] [--batch 512] [--steps 3] [--nodes 32]
+python tools/infer_bench.py --only mc --samples 10 [--mc-graphs 8] [--nodes 32] [--reps 7]
 (--nodes: the padded node count of cfg5's batch; above 32 the aggregate forward is tgt_triplet_aggregate_proj64_fwd,
 TGT_AGG_PROJ64_INFER=0 is the A/B knob and `knobs` in the line says which side ran.  --only tgt_at honours --nodes and --batch
 too: above 32 nodes its triplet forward is tgt_triplet_attention_proj64_fwd, TGT_TRI_PROJ64_INFER=0 is the A/B knob)
@@ -55,11 +61,13 @@ def main():
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--nodes', type=int, default=32, help='padded node count of the cfg5 batch (the BASELINE shape is 32)')
     ap.add_argument('--only', default='')
+    ap.add_argument('--mc-graphs', type=int, default=8, help='graphs of the mc batch')
+    ap.add_argument('--reps', type=int, default=7, help='repetitions per side of the mc comparison')
     a = ap.parse_args()
     gemm_tuning.enable_gemm_tuning(online=True)
     torch.manual_seed(0)
 
-    if not a.only or 'cfg1' in a.only:
+    if not a.only or 'cfg1' in a.only.split(','):
         kw = configs.tgt_agx2_12x2(num_dist_bins=256, embed_3d_type='none')       # coords_input: none (tgt_agx2_dp_nordkit.yaml)
         model = TGT_Distance(**kw).cuda().eval()
         batch = device_batch(8, 32, 11, ragged=True)
@@ -84,7 +92,7 @@ def main():
             print(json.dumps(line), flush=True)
         del model
 
-    if not a.only or 'cfg5' in a.only:
+    if not a.only or 'cfg5' in a.only.split(','):
         S, B = a.samples, a.batch
         dk = configs.tgt_agx2_12x2(num_dist_bins=256, embed_3d_type='none')
         gk = configs.tgt_agx2_12x2(num_dist_bins=256, embed_3d_type='gaussian')
@@ -132,6 +140,47 @@ def main():
         print(json.dumps(dict(metric=f'graphs/sec forward, TGT-At 24L, bf16, batch {B}, N = {Nn}, no autograd', value=round(B / dt, 1),
                               unit='graphs/s', ms_per_forward=round(dt * 1e3, 3), dtype='bf16', n_gpus=1, data='synthetic',
                               launch='eager', kernel_ms=kt, batch=B, nodes=Nn, knobs=K.non_default())), flush=True)
+
+    if 'mc' in a.only.split(','):
+        import statistics
+        from tgt_amd.pcqm.graphed import GraphedSampler
+        S, B, Nn = a.samples, a.mc_graphs, a.nodes
+        for name, kw in (('TGT-At 24L', configs.tgt_at_24l(num_dist_bins=256)), ('TGT-Agx2 12x2', configs.tgt_agx2_12x2(num_dist_bins=256))):
+            model = TGT_Distance(**kw).cuda().train()                                 # predict_in_train: every dropout ON
+            batch = device_batch(B, Nn, 14, ragged=True)
+
+            def eager():
+                with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16):
+                    return pp.predict_bins(model, batch, S)
+            eager()                                                                   # GEMM plans, allocator
+            times = dict(eager=[], graphed=[])
+            with GraphedSampler(model, batch, S, 'bins', autocast_dtype=torch.bfloat16) as gs:
+                def graphed():
+                    return pp.predict_bins(model, batch, S, graphed=gs)
+                bins = graphed()
+                distinct = len({bins[:, s].cpu().numpy().tobytes() for s in range(S)})
+                for _ in range(max(1, a.reps)):                                       # alternating: both sides see the same clocks
+                    times['graphed'].append(timed(graphed, 1, a.steps))
+                    # the eager side as it runs without a sampler: host seeds, pooled DropPath draws (a replay keeps the counter it
+                    # captured, so the mode can be lent out between replays)
+                    ops.set_seed_counter(None)
+                    ops.graph_safe_rng(False)
+                    try:
+                        times['eager'].append(timed(eager, 1, a.steps))
+                    finally:
+                        ops.graph_safe_rng(True)
+                        ops.set_seed_counter(gs.counter)
+            med = {k: statistics.median(v) for k, v in times.items()}
+            print(json.dumps(dict(metric=f'ms per MC-dropout predict_bins batch, {name} distance predictor, train mode, bf16, {B} graphs, '
+                                         f'N = {Nn}, {S} samples', unit='ms', dtype='bf16', n_gpus=1, data='synthetic', graphs=B, nodes=Nn,
+                                  samples=S, reps=len(times['eager']), batches_per_rep=a.steps,
+                                  eager_ms=dict(median=round(med['eager'] * 1e3, 3), min=round(min(times['eager']) * 1e3, 3),
+                                                max=round(max(times['eager']) * 1e3, 3)),
+                                  graphed_ms=dict(median=round(med['graphed'] * 1e3, 3), min=round(min(times['graphed']) * 1e3, 3),
+                                                  max=round(max(times['graphed']) * 1e3, 3)),
+                                  speedup=round(med['eager'] / med['graphed'], 3), distinct_samples=distinct,
+                                  samples_per_s_graphed=round(S * B / med['graphed'], 1), knobs=knobs.K.non_default())), flush=True)
+            del model
 
 
 if __name__ == '__main__':
