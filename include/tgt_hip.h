@@ -439,21 +439,35 @@ int tgt_loss_accumulate(const void* loss, int32_t loss_is_f64, float samples, fl
  *                    TGT_EPI_BIAS launch of the same operands); out (M, 256) = dropout(e * act(g), dropout_p, dropout_seed)
  *                    * row_scale[m / rows_per_sample] (row_scale may be NULL): tgt_glu_dropout_fwd on out2, bit for bit, in the
  *                    store phase of the GEMM.  The kind (TGT_GLU_*) travels in flags: kind << TGT_EDGE_GLU_KIND_SHIFT.
+ *   TGT_EPI_ACT      (N = 256, K in {64,128,256}; csrc/edge_act.hip) out2 = z, the pre-activation as stored (bit-identical to a
+ *                    TGT_EPI_BIAS launch of the same operands); out = dropout(act(z), dropout_p, dropout_seed)
+ *                    * row_scale[m / rows_per_sample] (row_scale may be NULL): tgt_act_dropout_fwd on out2, bit for bit.
+ *                    act = relu / silu / elu: the kind (TGT_ACT_*) travels in flags: kind << TGT_EDGE_ACT_KIND_SHIFT.
+ *   TGT_EPI_ACT_BWD  (N = 256, K in {64,128,256}) the TGT_EPI_GELU_BWD contract with act'(res) of the kind in flags:
+ *                    out = z' * act'(res) * keep / (1-p), z' = z * out_scale[..]; res = the forward's pre-activation; no bias;
+ *                    colsum_partial (tgt_edge_linear_parts(M, N), N) float32 when given, as TGT_EPI_GELU_BWD.
+ *                    Neither takes gamma, TGT_EDGE_BIAS_SCALED or dw_partial (there is no fused weight gradient for them).
  * Element type 16-bit (TGT_BF16 / TGT_F16; bias in the same type); N % 8 == 0; K in {64, 128, 256}.
  * tgt_edge_linear_supported() tells; anything else is the caller's library GEMM + tgt_layer_norm_* path.
  * tgt_edge_linear_set_grid_cap(cap): TEST HOOK -- at most `cap` persistent workgroups per launch (0 = no cap), so that small
  * problems walk several row tiles per workgroup the way the BASELINE-size launches do.
  * ---------------------------------------------------------------------- */
-enum { TGT_EPI_BIAS = 0, TGT_EPI_GELU = 1, TGT_EPI_RESID = 2, TGT_EPI_GELU_BWD = 3, TGT_EPI_LN_BWD = 4, TGT_EPI_GLU = 5 };
+enum { TGT_EPI_BIAS = 0, TGT_EPI_GELU = 1, TGT_EPI_RESID = 2, TGT_EPI_GELU_BWD = 3, TGT_EPI_LN_BWD = 4, TGT_EPI_GLU = 5,
+       TGT_EPI_ACT = 6, TGT_EPI_ACT_BWD = 7 };
 /* the gated activations y = e * act(g) of x = [g | e] (gate half first; reference lib/tgt/layers/activations.py:4-17):
  * geglu act = gelu (erf form), glu act = sigmoid, swiglu act = g * sigmoid(g) */
 enum { TGT_GLU_GEGLU = 0, TGT_GLU_GLU = 1, TGT_GLU_SWIGLU = 2 };
+/* the plain activations an FFN takes besides gelu (reference lib/tgt/layers/activations.py:21-25, `getattr(F, name)`):
+ * relu (NaN propagates, derivative 0 at 0), silu = x * sigmoid(x), elu with alpha = 1 (x > 0 ? x : expm1(x)) */
+enum { TGT_ACT_RELU = 0, TGT_ACT_SILU = 1, TGT_ACT_ELU = 2 };
 /* flags.  TGT_EDGE_BIAS_SCALED (TGT_EPI_RESID, N = 256, K in {64,128,256}): a arrives PRE-SCALED by row_scale (its producer
  * folded the DropPath factor in: tgt_gelu_dropout_scaled_fwd, tgt_node_attention_args.hhat_scale), so
  *     out = res + a W^T + row_scale[row / rows_per_sample] * bias
  * and the backward of the block needs no scaled copy of the stream gradient (tgt_add_layer_norm_bwd with scale and d_x = NULL). */
-/* bits 1-2 (ABI 31, TGT_EPI_GLU only): the activation, TGT_GLU_* << TGT_EDGE_GLU_KIND_SHIFT */
-enum { TGT_EDGE_BIAS_SCALED = 1, TGT_EDGE_GLU_KIND_SHIFT = 1, TGT_EDGE_GLU_KIND_MASK = 6 };
+/* bits 1-2 (ABI 31, TGT_EPI_GLU only): the activation, TGT_GLU_* << TGT_EDGE_GLU_KIND_SHIFT; with TGT_EPI_ACT / TGT_EPI_ACT_BWD the
+ * same two bits hold TGT_ACT_* << TGT_EDGE_ACT_KIND_SHIFT */
+enum { TGT_EDGE_BIAS_SCALED = 1, TGT_EDGE_GLU_KIND_SHIFT = 1, TGT_EDGE_GLU_KIND_MASK = 6,
+       TGT_EDGE_ACT_KIND_SHIFT = 1, TGT_EDGE_ACT_KIND_MASK = 6 };
 typedef struct tgt_edge_linear_args {
     int64_t M;
     int32_t K, N, dtype, epilogue;
@@ -501,7 +515,8 @@ void tgt_edge_linear_set_grid_cap(int32_t cap);
  *   The caller vouches that the dead rows do not matter: forward, a padded row reaches a real one only through keys the mask
  *   closes; backward, its cotangent out of a masked loss is exactly zero -- and zero is what its outputs get here.
  * tgt_edge_linear_live_supported: the launches that take a list -- the 32-row-tile kernels: N = 256 with a whole-row epilogue
- *   (GELU, RESID [+ LayerNorm], GELU_BWD, LN_BWD; K in {64,128,256}), K = 512 -> 256 (RESID), 256 -> 512 plain, TGT_EPI_GLU.
+ *   (GELU, RESID [+ LayerNorm], GELU_BWD, LN_BWD, ACT, ACT_BWD; K in {64,128,256}), K = 512 -> 256 (RESID), 256 -> 512 plain,
+ *   TGT_EPI_GLU.
  *   Not with dw_partial, not the shapes of the 64 / 128-row slice kernel: tgt_edge_linear_live answers those with
  *   TGT_ERR_UNSUPPORTED before any launch. */
 int tgt_edge_live_tiles(const int32_t* node_counts, int32_t B, int32_t N, int32_t* tiles, void* stream);
@@ -579,6 +594,19 @@ int tgt_glu_dropout_fwd(const void* x, void* y, int64_t rows, int32_t cols, int3
                         const float* sample_scale, int64_t elems_per_sample, void* stream);
 int tgt_glu_dropout_bwd(const void* x, const void* dy, void* dx, int64_t rows, int32_t cols, int32_t kind, int32_t dtype, float p,
                         uint64_t seed, const float* sample_scale, int64_t elems_per_sample, void* stream);
+
+/* Fused plain activation + dropout: the middle of an FFN block whose activation is relu / silu / elu (reference
+ * lib/tgt/layers/activations.py:21-25, then the nn.Dropout of lib/tgt/layers/layers.py:158), the arguments of
+ * tgt_gelu_dropout_scaled_fwd / _bwd plus the kind (TGT_ACT_*):
+ *   y  = keep(i) ? act(x) / (1-p) * sample_scale[i / elems_per_sample] : 0
+ *   dx = keep(i) ? dy * act'(x) / (1-p) * sample_scale[i / elems_per_sample] : 0
+ * with the generator of tgt_gelu_dropout_fwd (the seed counter mixed in): no mask is stored, the backward needs x, dy and
+ * the seed.  p = 0 and no scale: the plain activation (relu then equals torch.relu bit for bit, NaN included).  n elements of
+ * `dtype`, contiguous and 16-byte aligned; sample_scale (optional, float32 per sample): elems_per_sample a multiple of 8. */
+int tgt_act_dropout_fwd(const void* x, void* y, int64_t n, int32_t kind, int32_t dtype, float p, uint64_t seed,
+                        const float* sample_scale, int64_t elems_per_sample, void* stream);
+int tgt_act_dropout_bwd(const void* x, const void* dy, void* dx, int64_t n, int32_t kind, int32_t dtype, float p, uint64_t seed,
+                        const float* sample_scale, int64_t elems_per_sample, void* stream);
 
 /* Column sums of a (rows, C) tensor into float32 (C): the bias gradient of a Linear layer
  * (the `grad_output.sum(0)` ATen reduction behind nn.Linear, e.g. reference

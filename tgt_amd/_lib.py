@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, 'libtgt_hip.so')
 LIB_OVERRIDE = os.environ.get('TGT_HIP_LIB')
 CSRC = os.path.join(_HERE, 'csrc')
 # (source, extra flags, object suffix): the triplet attention kernels compile one dtype per translation unit
-SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_live.hip', 'edge_wgrad.hip', 'params.hip', 'loss.hip', 'predict.hip', 'gaussian.hip', 'triplet_attention_proj.hip', 'triplet_attention_proj64.hip',
+SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_act.hip', 'edge_live.hip', 'edge_wgrad.hip', 'params.hip', 'loss.hip', 'predict.hip', 'gaussian.hip', 'triplet_attention_proj.hip', 'triplet_attention_proj64.hip',
            ('triplet_attention_proj64.hip', ['-DTGT_TRI_PROJ64_INST=2'], '.train'),      # (the storing form: a unit of its own)
            ('triplet_attention.hip', ['-DTGT_TRI_INST=9'], '.f32'), ('triplet_attention.hip', ['-DTGT_TRI_INST=2'], '.bf16'),
            ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip', 'triplet_attention_bwd2.hip',
@@ -28,7 +28,7 @@ SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_l
            ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=4'], '.f16'), 'node_attention.hip', 'node_attention_mfma.hip', 'node_attention16.hip', 'node_attention_kb.hip',
            # (the instantiations with node counts: units of their own, so that the plain units hold the kernels they always held -- DESIGN.md 4.zf)
            ('node_attention16.hip', ['-DTGT_NODE_COUNTS_UNIT'], '.counts'), ('node_attention_kb.hip', ['-DTGT_NODE_COUNTS_UNIT'], '.counts'),
-           'node_attention_kb_bwd.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip']
+           'node_attention_kb_bwd.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip', 'act.hip']
 ABI_VERSION = 32
 
 TGT_F32, TGT_BF16, TGT_F16 = 0, 1, 2
@@ -110,11 +110,14 @@ class SumItem(C.Structure):
 
 
 SUM_MANY_MAX = 64
-EPI_BIAS, EPI_GELU, EPI_RESID, EPI_GELU_BWD, EPI_LN_BWD, EPI_GLU = range(6)
+EPI_BIAS, EPI_GELU, EPI_RESID, EPI_GELU_BWD, EPI_LN_BWD, EPI_GLU, EPI_ACT, EPI_ACT_BWD = range(8)
 EDGE_BIAS_SCALED = 1
 EDGE_GLU_KIND_SHIFT = 1            # flags bits 1-2 of an EPI_GLU launch: the activation
 GLU_GEGLU, GLU_GLU, GLU_SWIGLU = range(3)
 GLU_KINDS = {'geglu': GLU_GEGLU, 'glu': GLU_GLU, 'swiglu': GLU_SWIGLU}
+EDGE_ACT_KIND_SHIFT = 1            # ... and of an EPI_ACT / EPI_ACT_BWD launch
+ACT_RELU, ACT_SILU, ACT_ELU = range(3)
+ACT_KINDS = {'relu': ACT_RELU, 'silu': ACT_SILU, 'elu': ACT_ELU}
 
 
 # symbol -> (restype, argtypes); every symbol include/tgt_hip.h declares
@@ -161,6 +164,8 @@ SYMBOLS = {
     'tgt_gelu_dropout_bwd_colsum': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, C.c_uint64, _vp, _i64, _i32, _vp, _vp, _vp]),
     'tgt_glu_dropout_fwd': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _f32, C.c_uint64, _vp, _i64, _vp]),
     'tgt_glu_dropout_bwd': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, C.c_uint64, _vp, _i64, _vp]),
+    'tgt_act_dropout_fwd': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _f32, C.c_uint64, _vp, _i64, _vp]),
+    'tgt_act_dropout_bwd': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _f32, C.c_uint64, _vp, _i64, _vp]),
     'tgt_add_layer_norm_fwd': (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _f32, _vp]),
     'tgt_add_layer_norm_bwd': (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     'tgt_layer_norm_parts': (C.c_int, []),

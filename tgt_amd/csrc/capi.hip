@@ -40,6 +40,8 @@ int gelu_dropout_run(const void* x, const void* dy, void* out, int64_t n, int dt
                      const float* row_scale, int64_t elems_per_sample, hipStream_t st);
 int glu_dropout_run(const void* x, const void* dy, void* out, int64_t rows, int cols, int kind, int dtype, float p, uint64_t seed,
                     bool bwd, const float* sample_scale, int64_t elems_per_sample, hipStream_t st);
+int act_dropout_run(const void* x, const void* dy, void* out, int64_t n, int kind, int dtype, float p, uint64_t seed, bool bwd,
+                    const float* sample_scale, int64_t elems_per_sample, hipStream_t st);
 int triangular_update_run(const void* e4, const void* v4, const float* mask, void* out, const void* d_out, void* d_e4,
                           void* d_v4, int B, int N, int H, int dtype, bool bwd, hipStream_t st);
 int colsum_run(const void* x, int x_dtype, int64_t rows, int C, float* out, float* partial, hipStream_t st);
@@ -184,6 +186,14 @@ int tgt_glu_dropout_bwd(const void* x, const void* dy, void* dx, int64_t rows, i
                         uint64_t seed, const float* sample_scale, int64_t elems_per_sample, void* stream) {
     return glu_dropout_run(x, dy, dx, rows, cols, kind, dtype, p, seed, true, sample_scale, elems_per_sample,
                            reinterpret_cast<hipStream_t>(stream));
+}
+int tgt_act_dropout_fwd(const void* x, void* y, int64_t n, int32_t kind, int32_t dtype, float p, uint64_t seed, const float* sample_scale,
+                        int64_t elems_per_sample, void* stream) {
+    return act_dropout_run(x, nullptr, y, n, kind, dtype, p, seed, false, sample_scale, elems_per_sample, reinterpret_cast<hipStream_t>(stream));
+}
+int tgt_act_dropout_bwd(const void* x, const void* dy, void* dx, int64_t n, int32_t kind, int32_t dtype, float p, uint64_t seed,
+                        const float* sample_scale, int64_t elems_per_sample, void* stream) {
+    return act_dropout_run(x, dy, dx, n, kind, dtype, p, seed, true, sample_scale, elems_per_sample, reinterpret_cast<hipStream_t>(stream));
 }
 int tgt_add_layer_norm_fwd(const void* x, int32_t x_dtype, const void* res, int32_t res_dtype, const float* scale,
                            int64_t rows_per_sample, void* s_out, const float* gamma, const float* beta, void* y,

@@ -6,7 +6,7 @@
 
 namespace tgt {
 
-enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_GELU_BWD = 3, EPI_LN_BWD = 4, EPI_GLU = 5 };
+enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_GELU_BWD = 3, EPI_LN_BWD = 4, EPI_GLU = 5, EPI_ACT = 6, EPI_ACT_BWD = 7 };
 
 struct EgGeo {                    // LDS geometry of the A tile for a given chunk width
     int rowbytes, rpw, mask;

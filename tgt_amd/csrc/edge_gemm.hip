@@ -15,6 +15,7 @@
 //   EPI_LN_BWD     LayerNorm backward of the result + the gradient arriving on the residual stream,
 //                  dgamma / dbeta / bias-gradient column sums as per-workgroup partials
 //   EPI_GLU   pre-activation [g | e] + dropout(e * act(g))   (lin_W1 of an FFN with geglu / glu / swiglu, 256 -> 512: edge_glu.hip)
+//   EPI_ACT / EPI_ACT_BWD   EPI_GELU / EPI_GELU_BWD with relu / silu / elu in place of gelu (N = 256: edge_act.hip)
 // so that the standalone LayerNorm / residual / GELU sweeps over the edge tensor disappear.
 //
 // Two kernels: the weight-resident SLICE kernel (narrow outputs, EPI_BIAS) and the ROW-PHASE kernel (N = 256, whole-row
@@ -1035,6 +1036,8 @@ bool edge_wgrad_eligible(const tgt_edge_linear_args& a);                       /
 int edge_wgrad_run(const tgt_edge_linear_args& a, int grid, hipStream_t st);
 bool edge_glu_eligible(const tgt_edge_linear_args& a);                         // edge_glu.hip (TGT_EPI_GLU: 256 -> 512 + gated activation)
 int edge_glu_run(const tgt_edge_linear_args& a, int grid, hipStream_t st, const int32_t* tiles);
+bool edge_act_eligible(const tgt_edge_linear_args& a);                         // edge_act.hip (TGT_EPI_ACT / _ACT_BWD: N = 256 + relu / silu / elu)
+int edge_act_run(const tgt_edge_linear_args& a, int grid, hipStream_t st, const int32_t* tiles);
 
 // test hook (tgt_edge_linear_set_grid_cap): at most this many persistent workgroups / row groups per launch, so that a small
 // problem walks several tiles per workgroup -- the stage hand-over the BASELINE-size launches (32 tiles each) depend on
@@ -1183,6 +1186,7 @@ int edge_linear_supported(const tgt_edge_linear_args* a) {
     if (a->dtype != TGT_BF16 && a->dtype != TGT_F16) return 0;
     const int K = a->K, N = a->N;
     if (a->epilogue == EPI_GLU) return edge_glu_eligible(*a) ? 1 : 0;              // lin_W1 + geglu / glu / swiglu (K = 256, N = 512)
+    if (a->epilogue == EPI_ACT || a->epilogue == EPI_ACT_BWD) return edge_act_eligible(*a) ? 1 : 0;      // relu / silu / elu (N = 256)
     if (K == 512) return (N == 256 && a->epilogue == EPI_RESID && (!a->gamma || (a->beta && a->y))) ? 1 : 0;      // lin_O + residual [+ LayerNorm]
     if ((K != 64 && K != 128 && K != 256) || N < 8 || N % 8) return 0;
     if (a->gamma && a->epilogue != EPI_RESID && a->epilogue != EPI_LN_BWD) return 0;          // (no LayerNorm prologue)
@@ -1200,7 +1204,7 @@ int edge_linear_supported(const tgt_edge_linear_args* a) {
 // dW planes sum A rows the list says are never read)
 int edge_linear_live_supported(const tgt_edge_linear_args* a) {
     if (!edge_linear_supported(a) || a->dw_partial) return 0;
-    if (a->epilogue == EPI_GLU || a->K == 512) return 1;
+    if (a->epilogue == EPI_GLU || a->epilogue == EPI_ACT || a->epilogue == EPI_ACT_BWD || a->K == 512) return 1;
     return (ew512_eligible(*a) || er_eligible(*a)) ? 1 : 0;
 }
 
@@ -1210,7 +1214,8 @@ int edge_linear_run(const tgt_edge_linear_args* a, hipStream_t st, const int32_t
     if (a->M < 0 || a->K <= 0 || a->N <= 0) return set_error(TGT_ERR_INVALID, "edge linear: bad sizes");
     if (!edge_linear_supported(a))
         return set_error(TGT_ERR_UNSUPPORTED, "edge linear: unsupported shape/dtype (K=%d N=%d dtype=%d epilogue=%d): needs a 16-bit "
-                         "dtype, N %% 8 == 0, K in {64,128,256} (K = 512: residual epilogue, N = 256); row-wise epilogues N <= 256; TGT_EPI_GLU K = 256, N = 512",
+                         "dtype, N %% 8 == 0, K in {64,128,256} (K = 512: residual epilogue, N = 256); row-wise epilogues N <= 256; TGT_EPI_GLU K = 256, N = 512; "
+                         "TGT_EPI_ACT / _ACT_BWD N = 256, a kind in flags, no gamma / dw_partial",
                          a->K, a->N, a->dtype, a->epilogue);
     if (tiles && !edge_linear_live_supported(a))
         return set_error(TGT_ERR_UNSUPPORTED, "edge linear: a live tile list goes with the 32-row-tile kernels only (N = 256 whole-row epilogues, "
@@ -1223,9 +1228,10 @@ int edge_linear_run(const tgt_edge_linear_args* a, hipStream_t st, const int32_t
     if (al % 16 || (a->lda * 2) % 16 || (a->ldw * 2) % 16 || (a->ldo * 2) % 16 || (a->ldo2 * 2) % 16 || (a->ldr * 2) % 16 ||
         (a->ldy * 2) % 16 || (a->ld_ds * 2) % 16)
         return set_error(TGT_ERR_INVALID, "edge linear: tensors and row strides must be 16-byte aligned");
-    if (((a->epilogue == EPI_GELU || a->epilogue == EPI_GLU) && !a->out2) || ((a->epilogue == EPI_RESID || a->epilogue == EPI_GELU_BWD) && !a->res))
+    if (((a->epilogue == EPI_GELU || a->epilogue == EPI_GLU || a->epilogue == EPI_ACT) && !a->out2) ||
+        ((a->epilogue == EPI_RESID || a->epilogue == EPI_GELU_BWD || a->epilogue == EPI_ACT_BWD) && !a->res))
         return set_error(TGT_ERR_INVALID, "edge linear: epilogue operand missing");
-    if ((a->epilogue == EPI_GELU_BWD || a->epilogue == EPI_LN_BWD) && a->bias)
+    if ((a->epilogue == EPI_GELU_BWD || a->epilogue == EPI_LN_BWD || a->epilogue == EPI_ACT_BWD) && a->bias)
         return set_error(TGT_ERR_INVALID, "edge linear: the backward epilogues are data-gradient GEMMs, they take no bias");
     if ((a->row_scale || a->out_scale) && (a->rows_per_sample <= 0 || a->rows_per_sample > 0x7fffffffLL || a->M > 0x7fffffffLL))
         return set_error(TGT_ERR_INVALID, "edge linear: rows_per_sample missing (or more than 2^31 rows with a per-sample scale)");
@@ -1242,6 +1248,7 @@ int edge_linear_run(const tgt_edge_linear_args* a, hipStream_t st, const int32_t
         return edge_wgrad_run(*a, er_grid(*a), st);
     }
     if (a->epilogue == EPI_GLU) return edge_glu_run(*a, er_grid(*a), st, tiles);
+    if (a->epilogue == EPI_ACT || a->epilogue == EPI_ACT_BWD) return edge_act_run(*a, er_grid(*a), st, tiles);
     if (tiles) {
         if (a->K == 512) return a->dtype == TGT_BF16 ? er512_launch<bf16_t>(*a, st, tiles) : er512_launch<f16_t>(*a, st, tiles);
         if (ew512_eligible(*a)) return a->dtype == TGT_BF16 ? ew512_launch<bf16_t>(*a, st, tiles) : ew512_launch<f16_t>(*a, st, tiles);

@@ -39,6 +39,7 @@ _SPEC = {
     'edge_n512': ('TGT_EDGE_N512', True, 'flag', "lin_O's and the narrow data gradients on own kernels"),
     'ffn_gelu_epi': ('TGT_FFN_GELU_EPI', True, 'flag', 'lin_W1 + GELU + dropout as one launch'),
     'ffn_gelu_bwd_epi': ('TGT_FFN_GELU_BWD_EPI', True, 'flag', 'GELU backward as the epilogue of lin_W2 data gradient'),
+    'ffn_act_epi': ('TGT_FFN_ACT_EPI', True, 'flag', 'lin_W1 + relu / silu / elu + dropout as one launch on the edge rows and that activation backward as the epilogue of lin_W2 data gradient (off: library GEMM + one streaming pass each way)'),
     'gelu_bwd_epi_colsum': ('TGT_GELU_BWD_EPI_COLSUM', True, 'flag', "lin_W1's bias gradient from the GELU_BWD epilogue"),
     'edge_k512': ('TGT_EDGE_K512', True, 'flag', 'lin_O (K = 512) + residual + LayerNorm as one launch'),
     'prescale': ('TGT_PRESCALE', True, 'flag', 'DropPath factor folded into the producer of the branch'),
@@ -96,6 +97,7 @@ class Knobs:
     edge_n512: bool
     ffn_gelu_epi: bool
     ffn_gelu_bwd_epi: bool
+    ffn_act_epi: bool
     gelu_bwd_epi_colsum: bool
     edge_k512: bool
     prescale: bool

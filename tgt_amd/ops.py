@@ -1495,6 +1495,67 @@ def glu_dropout(x, kind, p, training, sample_scale=None):
     return _GluDropout.apply(x, kind, p, seed, sample_scale)
 
 
+ACT_KINDS = _lib.ACT_KINDS        # 'relu' / 'silu' / 'elu' -> TGT_ACT_*
+
+
+def _act_kind(kind):
+    if isinstance(kind, str):
+        if kind not in ACT_KINDS:
+            raise RuntimeError(f'act_dropout: unknown activation {kind!r} (one of {sorted(ACT_KINDS)})')
+        return ACT_KINDS[kind]
+    return int(kind)
+
+
+def _act_backward(pre, d_act, kind, p, seed, sample_scale, eps_):
+    """d_pre of y = dropout(act(pre), p) * sample_scale: one streaming pass, the drop pattern recomputed"""
+    d_act = d_act.contiguous()
+    if d_act.dtype != pre.dtype:
+        d_act = d_act.to(pre.dtype)
+    d_pre = torch.empty_like(pre)
+    _launch('tgt_act_dropout_bwd', _ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel(), kind, _DT[pre.dtype], p, seed, _ptr(sample_scale),
+            eps_, prof='tgt_act_dropout_bwd')
+    return d_pre
+
+
+class _ActDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kind, p, seed, sample_scale):
+        _dev(x, sample_scale)
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        eps_ = x.numel() // sample_scale.numel() if sample_scale is not None else 0
+        _launch('tgt_act_dropout_fwd', _ptr(x), _ptr(y), x.numel(), kind, _DT[x.dtype], float(p), seed, _ptr(sample_scale), eps_,
+                prof='tgt_act_dropout_fwd')
+        ctx.save_for_backward(x, sample_scale)
+        ctx.meta = (kind, float(p), seed, eps_)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, sample_scale = ctx.saved_tensors
+        return _act_backward(x, dy, *ctx.meta[:3], sample_scale, ctx.meta[3]), None, None, None, None
+
+
+def _act_check(numel, dtype, sample_scale, what):
+    if dtype not in _DT:
+        raise RuntimeError(f'{what}: no kernel for dtype {dtype} (float32 / bfloat16 / float16)')
+    if sample_scale is not None:
+        if sample_scale.dtype != torch.float32 or numel % sample_scale.numel() or (numel // sample_scale.numel()) % 8:
+            raise RuntimeError(f'{what}: sample_scale must be float32 with a multiple of 8 elements per sample')
+
+
+def act_dropout(x, kind, p, training, sample_scale=None):
+    """dropout(act(x), p) in one pass each way: kind 'relu', 'silu' or 'elu' (alpha = 1) -- the names besides gelu that reference
+    lib/tgt/layers/activations.py:21-25 looks up in torch.nn.functional, followed by the nn.Dropout of lib/tgt/layers/layers.py:158.
+    Only x is kept for the backward; the drop pattern comes from a per-call seed (no mask tensor).
+    sample_scale (B,) float32: the result is multiplied by sample_scale[b] (the branch's DropPath factor, see gelu_dropout)."""
+    kind = _act_kind(kind)
+    p, seed = draw_dropout(p, training)
+    _dev(x, sample_scale)
+    _act_check(x.numel(), x.dtype, sample_scale, 'act_dropout')
+    return _ActDropout.apply(x, kind, p, seed, sample_scale)
+
+
 class _MultiHotEmbed(torch.autograd.Function):
     """sum_f W[idx[..., f]]  as  counts(idx) @ W: both directions are small GEMMs
     instead of a gather and a sort-based scatter (the ATen embedding backward spends
@@ -2449,6 +2510,59 @@ def linear_glu_dropout(x, weight, bias, kind, p, training, sample_scale=None):
     return _LinearGluDropout.apply(x, weight, bias, cd, kind, p, seed, sample_scale)
 
 
+# A/B knob: lin_W1 + relu / silu / elu + dropout as one launch on the edge rows and the activation's backward as the epilogue of
+# lin_W2's data-gradient GEMM (TGT_EPI_ACT / TGT_EPI_ACT_BWD), against library GEMM + one streaming pass each way
+_FFN_ACT_EPI = K.ffn_act_epi
+
+
+class _LinearActDropout(torch.autograd.Function):
+    """act = dropout(activation(x W^T + b), p) * sample_scale[b] for relu / silu / elu as ONE launch (tgt_edge_linear, TGT_EPI_ACT:
+    reference FFN, lib/tgt/layers/layers.py:155-158).  As _LinearGeluDropout: two outputs, the activation and the pre-activation
+    as a differentiable value of its own, so that linear_residual_layer_norm can take over the activation's backward
+    (TGT_EPI_ACT_BWD); otherwise the backward is tgt_act_dropout_bwd on the stored pre-activation followed by the Linear's."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, cd, kind, p, seed, sample_scale, lazy=False):
+        ctx.set_materialize_grads(False)
+        ctx.kind = kind
+        return _linear_act_forward(ctx, x, weight, bias, cd, _lib.EPI_ACT, weight.shape[0], p, seed, sample_scale, lazy,
+                                   flags=kind << _lib.EDGE_ACT_KIND_SHIFT)
+
+    @staticmethod
+    def backward(ctx, d_act, d_pre_in):
+        x2, w, pre, sample_scale = ctx.saved_tensors
+        d_pre = handed = None
+        if d_act is not None:
+            d_pre = _act_backward(pre, d_act, ctx.kind, ctx.p, ctx.seed, sample_scale, ctx.eps_)
+        if d_pre_in is not None:
+            if d_pre is None:
+                handed = d_pre_in                                      # (the ACT_BWD epilogue that wrote it summed its columns)
+            d_pre = d_pre_in.contiguous() if d_pre is None else d_pre + d_pre_in
+        if d_pre is None:
+            return _grads(_LINEAR_ACT_ARGS)
+        return _grads(_LINEAR_ACT_ARGS, *_linear_backward_db(ctx, x2, w, d_pre.view(-1, d_pre.shape[-1]), None, handed))
+
+
+_LINEAR_ACT_ARGS = _forward_args(_LinearActDropout, _XWB)
+
+
+def linear_act_dropout_ok(x, weight, sample_scale=None):
+    """whether linear_act_dropout takes this call: edge rows (many of them), 16-bit compute dtype, 256 outputs, K in {64,128,256}"""
+    return bool(_FFN_ACT_EPI) and _linear_act_ok(x, weight, sample_scale, 256, (64, 128, 256), _lib.EPI_ACT)
+
+
+def linear_act_dropout(x, weight, bias, kind, p, training, sample_scale=None):
+    """dropout(act(linear(x, weight, bias)), p) [* sample_scale per graph] in one launch; kind as in act_dropout; see
+    linear_act_dropout_ok"""
+    kind = _act_kind(kind)
+    cd = _compute_dtype(x, on_cpu=True)
+    p, seed = draw_dropout(p, training)
+    act, pre = _LinearActDropout.apply(x, weight, bias, cd, kind, p, seed, sample_scale, _lazy_ok(x, weight, cd))
+    # the record of linear_gelu_dropout with the kind behind it: what a consumer needs to take over the activation's backward
+    act._tgt_gelu = (pre, p, seed, sample_scale, kind)
+    return act
+
+
 # ---------------------------------------------------------------------------
 # residual entry of a pre-norm block: s = res + x*scale ; y = LN(s)   (one pass each way)
 # ---------------------------------------------------------------------------
@@ -2505,8 +2619,9 @@ class _LinearResidualLN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, res, scale, ln_w, ln_b, eps, cd, out_dtype, prescaled=False, pre=None, gelu=None, col_perm=None):
-        # pre / gelu = (p, seed, sample_scale): x is dropout(gelu(pre)) * sample_scale, handed in DETACHED; this node then owns the
-        # activation's derivative and returns the gradient of `pre` (GELU backward as the epilogue of the data-gradient GEMM)
+        # pre / gelu = (p, seed, sample_scale[, kind]): x is dropout(gelu(pre)) * sample_scale, handed in DETACHED; this node then owns
+        # the activation's derivative and returns the gradient of `pre` (GELU backward as the epilogue of the data-gradient GEMM).
+        # kind (TGT_ACT_*): the activation is relu / silu / elu instead (linear_act_dropout; TGT_EPI_ACT_BWD)
         _dev(x, weight, res, ln_w, ln_b)
         ctx.lin = _LinearSaved.of(x, weight, bias)
         xs = ctx.lin.xs
@@ -2527,9 +2642,10 @@ class _LinearResidualLN(torch.autograd.Function):
         edge_linear_raw(x2, w, b, _lib.EPI_RESID, out=s.view(rows, N), res=res2, row_scale=scale, rows_per_sample=rps,
                         ln=(g, be, eps), stats=(mean, rstd), y=y.view(rows, N),
                         flags=_lib.EDGE_BIAS_SCALED if (prescaled and scale is not None) else 0, live=ctx.lin.live)
-        ctx.gelu = None
+        ctx.gelu = ctx.act_kind = None
         if pre is not None:
             ctx.gelu = (float(gelu[0]), gelu[1], gelu[2] is not None)
+            ctx.act_kind = gelu[3] if len(gelu) > 3 else None
             ctx.save_for_backward(x2, w, s, g, mean, rstd, scale, pre, gelu[2])
         else:
             ctx.save_for_backward(x2, w, s, g, mean, rstd, scale)
@@ -2567,17 +2683,19 @@ class _LinearResidualLN(torch.autograd.Function):
                 # (256 outputs = the row-phase kernel: it also returns the column sums of d_pre, lin_W1's bias gradient)
                 # the weight gradient of THIS Linear rides on the same launch (TGT_EDGE_WGRAD): dW = d_z^T x with x = the activation
                 # recomputed from `pre` in the row phase -- neither d_z nor x is read again by a weight-gradient GEMM
+                kind = ctx.act_kind                     # (relu / silu / elu: the same launch with TGT_EPI_ACT_BWD; no fused weight gradient)
                 fuse_dw = (_EDGE_WGRAD and need_dw and ctx.col_inv is None and N == 256 and pre.shape[-1] == 256 and
-                           x2.shape[1] == 256 and wdt == torch.float32)
+                           x2.shape[1] == 256 and wdt == torch.float32 and kind is None)
                 parts = _lib.lib().tgt_edge_linear_parts(rows, 256)
                 if fuse_dw and parts > 2 * _EDGE_WGRAD_SPARE > 0:
                     parts -= _EDGE_WGRAD_SPARE          # (the fused launch owns every CU it runs on -- all 160 KB of LDS: leave some to the node side stream)
                 part = torch.empty(parts, 256, dtype=torch.float32, device=pre.device) \
                     if (pre.shape[-1] == 256 and _GELU_BWD_EPI_COLSUM) else None
                 dw_part = torch.empty(parts, 256, 256, dtype=torch.float32, device=pre.device) if fuse_dw else None
-                edge_linear_raw(d_z.reshape(rows, N), weight_t(w), None, _lib.EPI_GELU_BWD, out=d_pre.view(rows, -1),
-                                res=pre.view(rows, -1), out_scale=g_scale, rows_per_sample=rps, dropout=(ctx.gelu[0], ctx.gelu[1]),
-                                colsum_partial=part, dw_partial=dw_part, live=live)
+                edge_linear_raw(d_z.reshape(rows, N), weight_t(w), None, _lib.EPI_GELU_BWD if kind is None else _lib.EPI_ACT_BWD,
+                                out=d_pre.view(rows, -1), res=pre.view(rows, -1), out_scale=g_scale, rows_per_sample=rps,
+                                dropout=(ctx.gelu[0], ctx.gelu[1]), colsum_partial=part, dw_partial=dw_part, live=live,
+                                flags=0 if kind is None else kind << _lib.EDGE_ACT_KIND_SHIFT)
                 if part is not None:
                     with _on_stream(_terminal_fork(rows, part)):
                         _hand_colsum(d_pre, sum_rows(part))
@@ -2631,9 +2749,12 @@ def linear_residual_layer_norm(x, weight, bias, res, scale, ln_weight, ln_bias, 
     itself to the Linear's gradient GEMMs instead of writing a scaled copy of it (one pass over the rows less)."""
     cd = _compute_dtype(x)
     # x = the FFN's activation out of linear_gelu_dropout: take over its backward when the data gradient runs on the row-phase kernel
-    gelu = getattr(x, '_tgt_gelu', None) if _FFN_GELU_BWD_EPI else None
+    gelu = getattr(x, '_tgt_gelu', None)
+    if gelu is not None and not (_FFN_ACT_EPI if len(gelu) > 4 else _FFN_GELU_BWD_EPI):      # (the record of linear_act_dropout ends with a kind)
+        gelu = None
     if gelu is not None and not (weight.shape[0] == 256 and weight.shape[1] == 256 and gelu[0].dtype == cd and
-                                 _residual_fusable(x, weight, res, cd) and edge_linear_supported(256, 256, cd, _lib.EPI_GELU_BWD)):
+                                 _residual_fusable(x, weight, res, cd) and
+                                 edge_linear_supported(256, 256, cd, _lib.EPI_ACT_BWD if len(gelu) > 4 else _lib.EPI_GELU_BWD)):
         gelu = None
     extra = () if gelu is None else (gelu[0], gelu[1:])
     if gelu is not None:

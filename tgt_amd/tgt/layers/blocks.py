@@ -202,6 +202,13 @@ class FFN(nn.Module):
                 return ops.linear_glu_dropout(x, self.lin_W1.weight, self.lin_W1.bias, self.activation, self.act_dropout,
                                               self.training, sample_scale)
             return ops.glu_dropout(self.lin_W1(x), self.activation, self.act_dropout, self.training, sample_scale)
+        if self.activation in ops.ACT_KINDS:
+            # relu / silu / elu: the same two forms -- one launch on the edge rows (K in {64,128,256} -> 256, 16-bit), else the library
+            # GEMM and one streaming pass each way (the node FFN of width 768, fp32); the drop pattern is the kernels' own
+            if ops.linear_act_dropout_ok(x, self.lin_W1.weight, sample_scale):
+                return ops.linear_act_dropout(x, self.lin_W1.weight, self.lin_W1.bias, self.activation, self.act_dropout,
+                                              self.training, sample_scale)
+            return ops.act_dropout(self.lin_W1(x), self.activation, self.act_dropout, self.training, sample_scale)
         x = self.lin_W1(x)
         if self.activation == 'gelu' and x.dtype in (torch.float32, torch.bfloat16, torch.float16):
             return ops.gelu_dropout(x, self.act_dropout, self.training, sample_scale)      # one pass each way, no mask tensor

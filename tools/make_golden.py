@@ -65,6 +65,25 @@ def op_cases():
         save('op_' + name, flatten(res, full))
 
 
+# the plain activations an FFN takes besides gelu: the reference FFN on the inputs of op_ffn_geglu_small (same geometry and seed;
+# lin_W1 is 32 x 32 here), forward and every gradient -> op_ffn_relu_small / op_ffn_silu_small / op_ffn_elu_small
+ACT_KINDS = ('relu', 'silu', 'elu')
+
+
+def act_case_args(kind):
+    """(class name, kwargs, geometry, seed) of op_ffn_<kind>_small; tests/test_act_golden.py rebuilds the case from the same"""
+    _, kwargs, geom = gu.OP_CASES['ffn_geglu_small']
+    return 'FFN', dict(kwargs, activation=kind), geom, 100 + list(gu.OP_CASES).index('ffn_geglu_small')
+
+
+def act_cases():
+    for kind in ACT_KINDS:
+        cls_name, kwargs, geom, seed = act_case_args(kind)
+        res = gu.run_op_case(REF_CLASSES[cls_name], kwargs, geom, seed=seed)
+        print(f'ffn_{kind}_small: {cls_name}')
+        save(f'op_ffn_{kind}_small', flatten(res, True))
+
+
 def pretrain_loss(outputs, batch, num_bins, range_bins=8, weight=0.1):
     """reference lib/training_schemes/pcqm/pretrain/scheme.py:78-88"""
     gap, logits = outputs
@@ -360,9 +379,11 @@ def bf16_drift_cases():
 
 
 if __name__ == '__main__':
-    which = sys.argv[2:] or ['op', 'model', 'misc', 'full', 'full_agx2', 'full_n32', 'full_n48', 'full_n48_b8', 'full_gap_agx2', 'drift', 'predict']
+    which = sys.argv[2:] or ['op', 'act', 'model', 'misc', 'full', 'full_agx2', 'full_n32', 'full_n48', 'full_n48_b8', 'full_gap_agx2', 'drift', 'predict']
     if 'op' in which:
         op_cases()
+    if 'act' in which:
+        act_cases()
     if 'model' in which:
         model_cases()
     if 'misc' in which:
