@@ -266,6 +266,25 @@ int tgt_triangular_update_bwd(const void* e4, const void* v4, const float* mask,
                               void* d_e4, void* d_v4, int32_t B, int32_t N, int32_t H, int32_t dtype,
                               void* stream);
 
+/* The same core on staged matrix-core tiles (csrc/triangular_update_tiled.hip): every operand element is gated once, in the
+ * element type, while it is staged into LDS; both contractions and the four of the backward are 32 x 32 x 16 matrix-core tiles
+ * with fp32 accumulation.  No atomics: results are bit-reproducible run to run.  16-bit results differ from
+ * tgt_triangular_update_* by the rounding of the gated operands (within the project's 16-bit bars against float64).
+ * e4 / v4: rows of ld_e / ld_v ELEMENTS whose first 4H columns are [in_gate | in_lin | out_gate | out_lin] -- with ld = 8H the two
+ * halves of one (B*N*N, 8H) projection output; d_e4 / d_v4 (ld_de / ld_dv) likewise the two halves of one gradient buffer, columns
+ * [0, 4H) of every row written.  out / d_out: contiguous (B,N,N,2H).  Row strides at least 4H and a multiple of 8, e4 / v4 / out /
+ * d_out / d_e4 / d_v4 16-byte aligned.
+ * Supported (tgt_triangular_update_tiled_supported, host only, 1 / 0): bf16 / fp16, 1 <= N <= 64, H a multiple of 4 up to 64.
+ * Checks before any launch, in this order: sizes and dtype (TGT_ERR_INVALID), the predicate (TGT_ERR_UNSUPPORTED: fp32, N > 64
+ * and other H stay on tgt_triangular_update_*), B == 0 or N == 0 (TGT_OK), null tensors, row strides, alignment
+ * (TGT_ERR_INVALID).  Nothing is read on the host: capturable. */
+int tgt_triangular_update_tiled_supported(int32_t N, int32_t H, int32_t dtype);
+int tgt_triangular_update_tiled_fwd(const void* e4, int64_t ld_e, const void* v4, int64_t ld_v, const float* mask,
+                                    void* out, int32_t B, int32_t N, int32_t H, int32_t dtype, void* stream);
+int tgt_triangular_update_tiled_bwd(const void* e4, int64_t ld_e, const void* v4, int64_t ld_v, const float* mask,
+                                    const void* d_out, void* d_e4, int64_t ld_de, void* d_v4, int64_t ld_dv,
+                                    int32_t B, int32_t N, int32_t H, int32_t dtype, void* stream);
+
 /* ------------------------------------------------------------------------
  * Node attention with edge bias + gate (EGT_Attention) and the logits-only
  * EdgeUpdate.  Replaces reference lib/tgt/layers/layers.py:62-77 (and
@@ -498,6 +517,49 @@ int tgt_edge_linear_supported(const tgt_edge_linear_args* a);
 int tgt_edge_linear_parts(int64_t M, int32_t N);
 int tgt_edge_linear(const tgt_edge_linear_args* a, void* stream);
 void tgt_edge_linear_set_grid_cap(int32_t cap);
+
+/* ------------------------------------------------------------------------
+ * Gated output stage of TriangularUpdate on the edge rows (csrc/edge_gated.hip): lin_O + gate (reference
+ * lib/tgt/layers/triplet.py:174-175), DropPath + residual (layers.py:284-287) and the edge FFN's LayerNorm (layers.py:150) as
+ * ONE launch, its backward (without the LayerNorm's: tgt_add_layer_norm_bwd) as one more.
+ *   a (M, K = 2H) rows of lda elements; w (2C, K) rows of ldw elements, rows [gate (C) | linear (C)]; bias (2C), element type.
+ *   z = a w^T + bias = [z_g | z_l]      (fp32, never stored)
+ *   t = sigmoid(z_g) * z_l
+ *   s = res + row_scale[row / rows_per_sample] * t       (row_scale (samples) float32, may be NULL; res / s / y contiguous (M, C))
+ *   y = LayerNorm(s as stored; gamma, beta, eps);  mean, rstd (M) float32; gamma / beta (C) float32
+ * tgt_edge_gated_out_bwd, given dt (M, C) = the gradient at t (already times row_scale):
+ *   z and sigma = sigmoid(z_g) recomputed;  dz = [dt z_l sigma (1 - sigma) | dt sigma], rounded once to the element type
+ *   d_a (M, K) rows of ld_da elements = dz w
+ *   dw_partial (parts, 2C, K) float32 = per persistent workgroup dz^T a, db_partial (parts, 2C) float32 = its column sums of dz:
+ *   every plane / row written; finish with tgt_sum_planes / tgt_sum_rows.  parts = the planes provided = the grid
+ *   (tgt_edge_gated_out_parts(M), at most the number of 32-row tiles).
+ * Nothing of width 2C is written to memory in either direction.  The kernels walk 32-row tiles persistently and honour
+ * tgt_edge_linear_set_grid_cap.  No atomics: bit-reproducible run to run.
+ * Supported (tgt_edge_gated_out_supported, host only, 1 / 0): C = 256, K in {16, 32, 64}, bf16 / fp16.  Checks before any launch, in
+ * this order: null args, sizes (TGT_ERR_INVALID), the predicate (TGT_ERR_UNSUPPORTED), M == 0 (TGT_OK), null tensors, lda / ldw /
+ * ld_da below K or not a multiple of 8, tensors not 16-byte aligned, parts outside [1, row tiles] (TGT_ERR_INVALID).
+ * ---------------------------------------------------------------------- */
+typedef struct tgt_edge_gated_args {
+    int64_t M;
+    int32_t K, C, dtype;
+    int32_t parts;                    /* backward: planes of dw_partial / rows of db_partial provided */
+    const void* a;    int64_t lda;
+    const void* w;    int64_t ldw;
+    const void* bias;
+    const void* res;  void* s;  void* y;
+    const float* gamma;  const float* beta;
+    float   eps;
+    int32_t _pad0;
+    float*  mean;  float* rstd;
+    const float* row_scale;  int64_t rows_per_sample;
+    /* backward */
+    const void* dt;  void* d_a;  int64_t ld_da;
+    float*  dw_partial;  float* db_partial;
+} tgt_edge_gated_args;
+int tgt_edge_gated_out_supported(const tgt_edge_gated_args* a);
+int tgt_edge_gated_out_parts(int64_t M);
+int tgt_edge_gated_out_fwd(const tgt_edge_gated_args* a, void* stream);
+int tgt_edge_gated_out_bwd(const tgt_edge_gated_args* a, void* stream);
 
 /* Ragged batches: the padded rows of the edge tensors are not computed (csrc/edge_live.hip; no reference counterpart -- the
  * reference computes every padded position).  Row r of a (B*N*N, C) edge tensor is the pair (b, i, j) = (r / N^2, (r % N^2) / N,

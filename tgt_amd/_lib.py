@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, 'libtgt_hip.so')
 LIB_OVERRIDE = os.environ.get('TGT_HIP_LIB')
 CSRC = os.path.join(_HERE, 'csrc')
 # (source, extra flags, object suffix): the triplet attention kernels compile one dtype per translation unit
-SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_act.hip', 'edge_live.hip', 'edge_wgrad.hip', 'params.hip', 'loss.hip', 'predict.hip', 'gaussian.hip', 'triplet_attention_proj.hip', 'triplet_attention_proj64.hip',
+SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_gated.hip', 'edge_glu.hip', 'edge_act.hip', 'edge_live.hip', 'edge_wgrad.hip', 'params.hip', 'loss.hip', 'predict.hip', 'gaussian.hip', 'triplet_attention_proj.hip', 'triplet_attention_proj64.hip',
            ('triplet_attention_proj64.hip', ['-DTGT_TRI_PROJ64_INST=2'], '.train'),      # (the storing form: a unit of its own)
            ('triplet_attention.hip', ['-DTGT_TRI_INST=9'], '.f32'), ('triplet_attention.hip', ['-DTGT_TRI_INST=2'], '.bf16'),
            ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip', 'triplet_attention_bwd2.hip',
@@ -28,7 +28,7 @@ SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_glu.hip', 'edge_a
            ('triplet_aggregate_kb.hip', ['-DTGT_AGGKB_INST=4'], '.f16'), 'node_attention.hip', 'node_attention_mfma.hip', 'node_attention16.hip', 'node_attention_kb.hip',
            # (the instantiations with node counts: units of their own, so that the plain units hold the kernels they always held -- DESIGN.md 4.zf)
            ('node_attention16.hip', ['-DTGT_NODE_COUNTS_UNIT'], '.counts'), ('node_attention_kb.hip', ['-DTGT_NODE_COUNTS_UNIT'], '.counts'),
-           'node_attention_kb_bwd.hip', 'layernorm.hip', 'triangular_update.hip', 'elementwise.hip', 'glu.hip', 'act.hip']
+           'node_attention_kb_bwd.hip', 'layernorm.hip', 'triangular_update.hip', 'triangular_update_tiled.hip', 'elementwise.hip', 'glu.hip', 'act.hip']
 ABI_VERSION = 32
 
 TGT_F32, TGT_BF16, TGT_F16 = 0, 1, 2
@@ -105,6 +105,16 @@ class EdgeLinearArgs(C.Structure):
     ]
 
 
+class EdgeGatedArgs(C.Structure):
+    _fields_ = [
+        ('M', _i64), ('K', _i32), ('C', _i32), ('dtype', _i32), ('parts', _i32),
+        ('a', _vp), ('lda', _i64), ('w', _vp), ('ldw', _i64), ('bias', _vp),
+        ('res', _vp), ('s', _vp), ('y', _vp), ('gamma', _vp), ('beta', _vp), ('eps', _f32), ('_pad0', _i32),
+        ('mean', _vp), ('rstd', _vp), ('row_scale', _vp), ('rows_per_sample', _i64),
+        ('dt', _vp), ('d_a', _vp), ('ld_da', _i64), ('dw_partial', _vp), ('db_partial', _vp),
+    ]
+
+
 class SumItem(C.Structure):
     _fields_ = [('src', _vp), ('dst', _vp), ('planes', _i32), ('_pad', _i32), ('n', _i64)]
 
@@ -156,6 +166,9 @@ SYMBOLS = {
     'tgt_node_attention_family': (C.c_int, [C.POINTER(NodeAttentionArgs), _i32]),
     'tgt_triangular_update_fwd': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     'tgt_triangular_update_bwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    'tgt_triangular_update_tiled_supported': (C.c_int, [_i32, _i32, _i32]),
+    'tgt_triangular_update_tiled_fwd': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    'tgt_triangular_update_tiled_bwd': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     'tgt_gelu_dropout_fwd': (C.c_int, [_vp, _vp, _i64, _i32, _f32, C.c_uint64, _vp]),
     'tgt_gelu_dropout_bwd': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, C.c_uint64, _vp]),
     'tgt_gelu_dropout_scaled_fwd': (C.c_int, [_vp, _vp, _i64, _i32, _f32, C.c_uint64, _vp, _i64, _vp]),
@@ -186,6 +199,10 @@ SYMBOLS = {
     'tgt_edge_linear_parts': (C.c_int, [_i64, _i32]),
     'tgt_edge_linear': (C.c_int, [C.POINTER(EdgeLinearArgs), _vp]),
     'tgt_edge_linear_set_grid_cap': (None, [_i32]),
+    'tgt_edge_gated_out_supported': (C.c_int, [C.POINTER(EdgeGatedArgs)]),
+    'tgt_edge_gated_out_parts': (C.c_int, [_i64]),
+    'tgt_edge_gated_out_fwd': (C.c_int, [C.POINTER(EdgeGatedArgs), _vp]),
+    'tgt_edge_gated_out_bwd': (C.c_int, [C.POINTER(EdgeGatedArgs), _vp]),
     'tgt_edge_live_tiles': (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     'tgt_edge_linear_live_supported': (C.c_int, [C.POINTER(EdgeLinearArgs)]),
     'tgt_edge_linear_live': (C.c_int, [C.POINTER(EdgeLinearArgs), _vp, _vp]),

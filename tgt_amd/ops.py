@@ -1075,6 +1075,65 @@ def triangular_update(e4, v4, mask3, num_heads):
     return _TriangularUpdate.apply(e4, v4, mask3, num_heads)
 
 
+_TRIUPD_TILED = K.triupd_tiled       # A/B knob: the core on staged matrix-core tiles (csrc/triangular_update_tiled.hip)
+
+
+def _triupd_tiled_ok(N, H, dtype):
+    return bool(_TRIUPD_TILED and dtype in (torch.bfloat16, torch.float16) and
+                _lib.lib().tgt_triangular_update_tiled_supported(N, H, _DT[dtype]))
+
+
+class _TriangularUpdatePacked(torch.autograd.Function):
+    """ops.triangular_update on the two halves of ONE projection output ev = [lin_E | lin_V] (B,N,N,8H); the backward writes one
+    (B,N,N,8H) gradient.  Tiled kernels where they take the shape (row stride 8H: nothing is copied), else the lane-per-head
+    kernel on contiguous copies of the halves."""
+
+    @staticmethod
+    def forward(ctx, ev, mask3, H):
+        _dev(ev, mask3)
+        ev = ev.contiguous()
+        B, N = ev.shape[0], ev.shape[1]
+        out = torch.empty(B, N, N, 2 * H, dtype=ev.dtype, device=ev.device)
+        ctx.tiled = _triupd_tiled_ok(N, H, ev.dtype)
+        if ctx.tiled:
+            v_ptr = C.c_void_p(ev.data_ptr() + 4 * H * ev.element_size())
+            _launch('tgt_triangular_update_tiled_fwd', _ptr(ev), 8 * H, v_ptr, 8 * H, _ptr(mask3), _ptr(out), B, N, H, _DT[ev.dtype],
+                    prof='tgt_triangular_update_tiled_fwd')
+        else:
+            e4, v4 = ev[..., :4 * H].contiguous(), ev[..., 4 * H:].contiguous()
+            _launch('tgt_triangular_update_fwd', _ptr(e4), _ptr(v4), _ptr(mask3), _ptr(out), B, N, H, _DT[ev.dtype])
+        ctx.save_for_backward(ev, mask3)
+        ctx.H = H
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        ev, mask3 = ctx.saved_tensors
+        H = ctx.H
+        d_out = d_out.contiguous()
+        B, N = ev.shape[0], ev.shape[1]
+        if ctx.tiled:
+            d_ev = torch.empty_like(ev)
+            off = 4 * H * ev.element_size()
+            _launch('tgt_triangular_update_tiled_bwd', _ptr(ev), 8 * H, C.c_void_p(ev.data_ptr() + off), 8 * H, _ptr(mask3), _ptr(d_out),
+                    _ptr(d_ev), 8 * H, C.c_void_p(d_ev.data_ptr() + off), 8 * H, B, N, H, _DT[ev.dtype],
+                    prof='tgt_triangular_update_tiled_bwd')
+            return d_ev, None, None
+        e4, v4 = ev[..., :4 * H].contiguous(), ev[..., 4 * H:].contiguous()
+        d_e4, d_v4 = torch.empty_like(e4), torch.empty_like(v4)
+        _launch('tgt_triangular_update_bwd', _ptr(e4), _ptr(v4), _ptr(mask3), _ptr(d_out), _ptr(d_e4), _ptr(d_v4), B, N, H, _DT[ev.dtype])
+        return torch.cat((d_e4, d_v4), dim=-1), None, None
+
+
+def triangular_update_packed(ev, mask3, num_heads):
+    """ev: (B,N,N,8H) = [lin_E | lin_V] outputs of one fused projection -> (B,N,N,2H): ops.triangular_update without the two
+    separate operands.  TGT_TRIUPD_TILED and a shape the tiled kernels take (16-bit, N <= 64, H a multiple of 4): the core on
+    matrix-core tiles; otherwise the existing kernel on the two halves."""
+    if ev.shape[-1] != 8 * num_heads:
+        raise ValueError(f'triangular_update_packed: ev has {ev.shape[-1]} columns, expected 8 * num_heads = {8 * num_heads}')
+    return _TriangularUpdatePacked.apply(ev, mask3, num_heads)
+
+
 # ---------------------------------------------------------------------------
 # node attention (EGT_Attention core) and EdgeUpdate logits
 # ---------------------------------------------------------------------------
@@ -2774,6 +2833,108 @@ def linear_residual_layer_norm(x, weight, bias, res, scale, ln_weight, ln_bias, 
     if _residual_fusable(x, weight, res, cd):
         return _offer_lazy(*_LinearResidualLN.apply(x, weight, bias, res, scale, ln_weight, ln_bias, eps, cd, cd, False, *extra))
     return add_layer_norm(linear(x, weight, bias), res, scale, ln_weight, ln_bias, eps)
+
+
+_TRIUPD_GATED = K.triupd_gated       # A/B knob: TriangularUpdate's lin_O + gate + residual + LayerNorm as one launch (csrc/edge_gated.hip)
+
+
+def _gated_args(x2, w, b, C_):
+    a = _lib.EdgeGatedArgs()
+    a.M, a.K, a.C, a.dtype = x2.shape[0], x2.shape[1], C_, _DT[x2.dtype]
+    a.a, a.lda, a.w, a.ldw, a.bias = x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), b.data_ptr()
+    return a
+
+
+class _GatedLinearResidualLN(torch.autograd.Function):
+    """s = res + scale * (sigmoid(z_g) * z_l), [z_g | z_l] = x W^T + b;  y = LayerNorm(s): TriangularUpdate's output projection
+    and gate (reference triplet.py:174-175), the residual add (+ DropPath) and the LayerNorm that opens the edge FFN in ONE launch
+    (tgt_edge_gated_out_fwd); z is never written.  Backward: the add + LayerNorm backward (_ln_backward), then ONE launch that
+    recomputes z and yields the data gradient and per-workgroup partials of the weight and bias gradients."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, res, scale, ln_w, ln_b, eps, cd):
+        _dev(x, weight, bias, res, ln_w, ln_b)
+        ctx.lin = _LinearSaved.of(x, weight, bias)
+        xs = ctx.lin.xs
+        x2, w, b = _linear_operands(x, weight, bias, cd, x_contiguous=True, wb_contiguous=True)
+        C_, rows = weight.shape[0] // 2, x2.shape[0]
+        g, be = ln_w.detach().float().contiguous(), ln_b.detach().float().contiguous()
+        s = torch.empty(*xs[:-1], C_, dtype=cd, device=x.device)
+        y = torch.empty(*xs[:-1], C_, dtype=cd, device=x.device)
+        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+        rps = rows // xs[0]
+        a = _gated_args(x2, w, b, C_)
+        a.res, a.s, a.y, a.gamma, a.beta, a.eps = res.data_ptr(), s.data_ptr(), y.data_ptr(), g.data_ptr(), be.data_ptr(), float(eps)
+        a.mean, a.rstd = mean.data_ptr(), rstd.data_ptr()
+        a.row_scale, a.rows_per_sample = (None if scale is None else scale.data_ptr()), rps
+        _launch('tgt_edge_gated_out_fwd', C.byref(a), prof='tgt_edge_gated_out_fwd')
+        ctx.save_for_backward(x2, w, b, s, g, mean, rstd, scale)
+        ctx.lndt, ctx.rdt, ctx.rps = ln_w.dtype, res.dtype, rps
+        ctx.live = _edge_live
+        return s, y
+
+    @staticmethod
+    def backward(ctx, ds, dy):
+        x2, w, b, s, g, mean, rstd, scale = ctx.saved_tensors
+        lin, rdt = ctx.lin, ctx.rdt
+        C_ = s.shape[-1]
+        rows, K_ = x2.shape
+        if dy is None:                                  # the LayerNorm branch was not used
+            d_res, d_t = _ln_unused_backward(ds, scale)
+            dg = dbeta = None
+        else:
+            d_res, d_t, dg, dbeta, _ = _ln_backward(dy, s, g, mean, rstd, ds, scale, ctx.rps, scale is not None, live=ctx.live)
+            if d_t is None:
+                d_t = d_res
+        d_t = d_t.reshape(rows, C_).contiguous()
+        if d_t.dtype != x2.dtype:
+            d_t = d_t.to(x2.dtype)
+        parts = _lib.lib().tgt_edge_gated_out_parts(rows)
+        d_a = torch.empty(rows, K_, dtype=x2.dtype, device=x2.device)
+        dw_part = torch.empty(parts, 2 * C_, K_, dtype=torch.float32, device=x2.device)
+        db_part = torch.empty(parts, 2 * C_, dtype=torch.float32, device=x2.device)
+        a = _gated_args(x2, w, b, C_)
+        a.parts, a.dt, a.d_a, a.ld_da = parts, d_t.data_ptr(), d_a.data_ptr(), K_
+        a.dw_partial, a.db_partial = dw_part.data_ptr(), db_part.data_ptr()
+        _launch('tgt_edge_gated_out_bwd', C.byref(a), prof='tgt_edge_gated_out_bwd')
+        need = ctx.needs_input_grad
+        dw = db = None
+        with _on_stream(_terminal_fork(rows, dw_part, db_part)):
+            if need[_GATED_LN_ARGS.index('weight')]:
+                dst = _grad_dst(lin.wptr, (2 * C_, K_), torch.float32) if lin.wdt == torch.float32 else None
+                dw = sum_planes(dw_part, dst if dst is not None else torch.empty(2 * C_, K_, dtype=torch.float32, device=x2.device))
+            if lin.bdt is not None and need[_GATED_LN_ARGS.index('bias')]:
+                db = sum_rows(db_part)
+        dx = d_a.view(lin.xs)
+        return _grads(_GATED_LN_ARGS, dx if dx.dtype == lin.xdt else dx.to(lin.xdt), _param_grad(dw, lin.wdt), _param_grad(db, lin.bdt),
+                      d_res if rdt == d_res.dtype else d_res.to(rdt), ln_w=_param_grad(dg, ctx.lndt), ln_b=_param_grad(dbeta, ctx.lndt))
+
+
+_GATED_LN_ARGS = _forward_args(_GatedLinearResidualLN, _XWB)
+
+
+def _gated_fusable(x, weight, bias, res, cd):
+    x2 = x.reshape(-1, x.shape[-1])
+    if not (_TRIUPD_GATED and _EDGE_GEMM and x.is_cuda and res.is_cuda and bias is not None and cd in (torch.bfloat16, torch.float16) and
+            weight.shape[0] == 512 and res.dtype == cd and res.is_contiguous() and x2.shape[0] >= _EDGE_MIN_ROWS):
+        return False
+    a = _lib.EdgeGatedArgs()
+    a.K, a.C, a.dtype = weight.shape[1], weight.shape[0] // 2, _DT[cd]
+    return bool(_lib.lib().tgt_edge_gated_out_supported(C.byref(a)))
+
+
+def gated_linear_residual_layer_norm(va, weight, bias, res, scale, ln_weight, ln_bias, eps=1e-5):
+    """(s, y): [g | l] = linear(va, weight, bias) (weight (2C, K): gate rows, then linear rows), s = res + scale[graph] *
+    (sigmoid(g) * l) (scale: per-sample DropPath factors or None), y = LayerNorm(s) -- the output stage of TriangularUpdate inside a
+    TGT_Layer (reference triplet.py:174-175, layers.py:284-287, :150).  One fused launch each way under TGT_TRIUPD_GATED when the
+    shape qualifies (16-bit compute dtype, C = 256, K in {16, 32, 64}, contiguous `res` of the compute dtype, >= 65536 rows);
+    otherwise the composition of ops.linear, the eager gate and ops.add_layer_norm (16-bit results of the two differ by rounding)."""
+    cd = _compute_dtype(va)
+    if _gated_fusable(va, weight, bias, res, cd):
+        return _offer_lazy(*_GatedLinearResidualLN.apply(va, weight, bias, res, scale, ln_weight, ln_bias, eps, cd))
+    gate, lin = linear(va, weight, bias).chunk(2, dim=-1)
+    return add_layer_norm(torch.sigmoid(gate) * lin, res, scale, ln_weight, ln_bias, eps)
 
 
 _side_streams = {}

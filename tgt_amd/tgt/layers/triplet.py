@@ -208,6 +208,10 @@ class TriangularUpdate(_TripletBase):
         self.lin_V = Linear(edge_width, num_heads * 4)
         self.lin_E = Linear(edge_width, num_heads * 4)
         self.lin_O = Linear(num_heads * 2, edge_width * 2)
+        # fused projection rows of attend(): [lin_E (4H) | lin_V (4H)], in the parameters' own order (a plain attribute, as the
+        # tables of the other modules: state_dict keys stay the reference's)
+        rows = torch.arange(num_heads * 4)
+        self._table = self._param_table([(0, rows), (1, rows)], num_heads * 8)
 
     def forward(self, e, mask):
         return self.forward_normed(self.tri_ln_e(e), mask)
@@ -217,6 +221,19 @@ class TriangularUpdate(_TripletBase):
         va = ops.triangular_update(self.lin_E(x), self.lin_V(x), ops.as_mask3(mask, B, N), self.num_heads)
         gate, lin = self.lin_O(va).chunk(2, dim=-1)
         return torch.sigmoid(gate) * lin
+
+    def attend(self, x, mask):
+        """the block after tri_ln_e without lin_O and the gate: lin_E and lin_V as ONE projection, then the core on its two
+        halves (ops.triangular_update_packed) -> (B,N,N,2H) = [O_in | O_out] (TGT_Layer fuses what follows: out_proj_residual_ln)"""
+        B, N = x.shape[0], x.shape[1]
+        ev = ops.fused_linear(x, self._table, (self.lin_E.weight, self.lin_E.bias, self.lin_V.weight, self.lin_V.bias))
+        return ops.triangular_update_packed(ev, ops.as_mask3(mask, B, N), self.num_heads)
+
+    def out_proj_residual_ln(self, va, res, scale, ln):
+        """(s, LayerNorm(s)), s = res + scale * (sigmoid(g) * l), [g | l] = lin_O(va): lin_O here is 2H -> 2C in the reference's own
+        column order and gated (reference triplet.py:174-175) -- not the base's head-major K = 512 Linear.  One launch where the
+        shape qualifies (ops.gated_linear_residual_layer_norm)"""
+        return ops.gated_linear_residual_layer_norm(va, self.lin_O.weight, self.lin_O.bias, res, scale, ln.weight, ln.bias, ln.eps)
 
 
 _LAYERS = {
