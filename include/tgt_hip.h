@@ -130,6 +130,17 @@ typedef struct tgt_triplet_attention_args {
 int64_t tgt_triplet_attention_workspace_bytes(const tgt_triplet_attention_args* a, int32_t bwd);
 int tgt_triplet_attention_fwd(const tgt_triplet_attention_args* a, void* stream);
 int tgt_triplet_attention_bwd(const tgt_triplet_attention_args* a, void* stream);
+/* Host only: the kernel family tgt_triplet_attention_fwd (bwd = 0) / _bwd (bwd != 0) launches for this call.  Judges sizes, dtype,
+ * flags, dropout_p, row lengths, offsets and pointer ALIGNMENT; dereferences nothing, touches no device.  A negative value: the
+ * entry point refuses the call (null tensors are its own, later check).  Attention dropout (dropout_p > 0) at N <= 32 stays on
+ * TGT_TRI_FAMILY_BWD2 (TGT_TRI_DROP_FAST=0 in the environment: GENERAL, the routing before that kernel had dropout); at 33..64
+ * nodes it leaves the 16-wide tiles for GENERAL. */
+enum { /* B == 0 or N == 0: nothing is launched */                                                TGT_TRI_FAMILY_NONE = 0,
+       /* 32-wide tiles, N <= 64, every dtype (csrc/triplet_attention.hip) */                     TGT_TRI_FAMILY_GENERAL = 1,
+       /* backward of 16-bit, D = 16, N <= 32, H % 8 == 0 (csrc/triplet_attention_bwd2.hip) */    TGT_TRI_FAMILY_BWD2 = 2,
+       /* 16-wide tiles, 33..64 nodes, 16-bit, D = 16, p == 0 (csrc/triplet_attention16.hip) */   TGT_TRI_FAMILY_TILES16 = 3,
+       /* key-blocked kernels, 65 <= N <= 128, D = 16 (csrc/triplet_attention_kb.hip) */          TGT_TRI_FAMILY_KB = 4 };
+int tgt_triplet_attention_family(const tgt_triplet_attention_args* a, int32_t bwd);
 
 /* Ragged batches: skip the padded nodes of every graph.  As tgt_triplet_attention_fwd / _bwd /
  * tgt_triplet_attention_proj_fwd (below), plus node_counts: (B) int32 DEVICE memory, or NULL (= the entry point without
@@ -687,7 +698,8 @@ int tgt_colsum(const void* x, int32_t x_dtype, int64_t rows, int32_t C, float* o
  *          through a->qkv[dir]: the pointers may be NULL, ld_qkv is not read, and q_off/k_off/v_off only select the rows
  *          of w / bias.  `out` is bit-identical with and without the flag.  tgt_triplet_attention_proj64_fwd (below) REQUIRES
  *          the bit; every other entry point ignores it.
- * Supported: N <= 32, D = 16, H % 8 == 0, bf16/fp16, C = 256
+ * Supported: N <= 32, D = 16, H % 8 == 0, bf16/fp16, C = 256, dropout_p == 0 (attention dropout: project with a GEMM and call
+ * tgt_triplet_attention_fwd; the backward of such a call still runs on the round-4 kernel, tgt_triplet_attention_family)
  * (tgt_triplet_attention_proj_supported() tells; otherwise tgt_triplet_attention_proj64_fwd, below, where it applies, or
  * project with a GEMM and call tgt_triplet_attention_fwd). */
 int tgt_triplet_attention_proj_supported(const tgt_triplet_attention_args* a, int32_t C);
@@ -797,8 +809,8 @@ int tgt_sum_many(const tgt_sum_item* items, int32_t n, void* stream);
  * graph; the counter -- incremented by the graph itself once per replay -- gives each replay its own drop patterns, forward and
  * backward of one step seeing the same value.  Process-wide; the POINTER is read at launch time, the value by the kernels (an
  * ordinary load, nothing is stored through it); NULL (the default) = seeds as given, bit for bit.  The triplet kernels that
- * require dropout_p == 0 (tgt_triplet_attention_proj*_fwd, the 16-wide tiles, tri_att_bwd2) and tgt_node_attention_* (no dropout
- * inside) do not take it.
+ * require dropout_p == 0 (tgt_triplet_attention_proj*_fwd, the 16-wide tiles) and tgt_node_attention_* (no dropout
+ * inside) do not take it; tri_att_bwd2 (the backward at N <= 32) reads it in its dropout_p > 0 kernels.
  * Replaces nothing in the reference: torch's own graph-safe Philox offsets play this role for its dropout under CUDA graphs. */
 int tgt_set_seed_counter(const void* device_counter);
 int tgt_transpose_many(const tgt_transpose_item* items, int32_t n, int32_t blocks_per_item, void* stream);

@@ -21,6 +21,7 @@ SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_gated.hip', 'edge
            ('triplet_attention_proj64.hip', ['-DTGT_TRI_PROJ64_INST=2'], '.train'),      # (the storing form: a unit of its own)
            ('triplet_attention.hip', ['-DTGT_TRI_INST=9'], '.f32'), ('triplet_attention.hip', ['-DTGT_TRI_INST=2'], '.bf16'),
            ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip', 'triplet_attention_bwd2.hip',
+           ('triplet_attention_bwd2.hip', ['-DTGT_BWD2_DROP_UNIT'], '.drop'),       # (its attention-dropout instantiations: a unit of their own)
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=9'], '.f32'), ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=2'], '.bf16'),
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=4'], '.f16'), ('triplet_aggregate.hip', ['-DTGT_AGG_INST=1'], '.plain'),
            ('triplet_aggregate.hip', ['-DTGT_AGG_INST=2'], '.skip'), 'triplet_aggregate_proj.hip', 'triplet_aggregate_proj64.hip',
@@ -35,6 +36,8 @@ TGT_F32, TGT_BF16, TGT_F16 = 0, 1, 2
 TRI_BIASED, TRI_GATED, TRI_MASK_OUT = 1, 2, 4
 # tgt_node_attention_family(): the kernel family behind tgt_node_attention_fwd / _bwd for a call
 NODE_FAMILY_NONE, NODE_FAMILY_LANE, NODE_FAMILY_MFMA32, NODE_FAMILY_TILES16, NODE_FAMILY_KB_FWD, NODE_FAMILY_KB_BWD = range(6)
+# tgt_triplet_attention_family(): the kernel family behind tgt_triplet_attention_fwd / _bwd for a call
+TRI_FAMILY_NONE, TRI_FAMILY_GENERAL, TRI_FAMILY_BWD2, TRI_FAMILY_TILES16, TRI_FAMILY_KB = range(5)
 TRI_NO_QKV_STORE = 8              # tgt_triplet_attention_proj_fwd / _proj64_fwd: the projected Q/K/V rows are not written
 TRI_COUNTS_KB = 16                # tgt_triplet_attention_fwd_counts / _bwd_counts only: the kernels for N > 64 use the node counts
 
@@ -141,6 +144,7 @@ SYMBOLS = {
     'tgt_triplet_attention_proj_fwd_counts': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _vp, _i32, _vp, _vp, _vp]),
     'tgt_mask_node_counts': (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     'tgt_triplet_attention_workspace_bytes': (_i64, [C.POINTER(TripletAttentionArgs), _i32]),
+    'tgt_triplet_attention_family': (C.c_int, [C.POINTER(TripletAttentionArgs), _i32]),
     'tgt_triplet_attention_proj_supported': (C.c_int, [C.POINTER(TripletAttentionArgs), _i32]),
     'tgt_triplet_attention_proj_fwd': (C.c_int, [C.POINTER(TripletAttentionArgs), _vp, _i32, _vp, _vp, _vp]),
     'tgt_triplet_attention_proj64_supported': (C.c_int, [C.POINTER(TripletAttentionArgs), _i32]),

@@ -23,6 +23,7 @@ int check_launch(const char* what) {
 }
 
 int triplet_attention_run(const tgt_triplet_attention_args* a, const int32_t* node_counts, bool bwd, hipStream_t st);
+int triplet_attention_family(const tgt_triplet_attention_args* a, bool bwd);
 int mask_node_counts_run(const float* mask, int B, int N, int32_t* counts, hipStream_t st);
 int64_t tri_att_kb_workspace_bytes(const tgt_triplet_attention_args* a, int bwd);
 int triplet_aggregate_run(const tgt_triplet_aggregate_args* a, const float* graph_scale, bool bwd, hipStream_t st);
@@ -134,6 +135,7 @@ int tgt_mask_node_counts(const float* mask, int32_t B, int32_t N, int32_t* count
     return mask_node_counts_run(mask, B, N, counts, reinterpret_cast<hipStream_t>(stream));
 }
 int64_t tgt_triplet_attention_workspace_bytes(const tgt_triplet_attention_args* a, int32_t bwd) { return tri_att_kb_workspace_bytes(a, bwd); }
+int tgt_triplet_attention_family(const tgt_triplet_attention_args* a, int32_t bwd) { return triplet_attention_family(a, bwd != 0); }
 int tgt_triplet_aggregate_fwd(const tgt_triplet_aggregate_args* a, void* stream) { return tgt_triplet_aggregate_fwd_skip(a, nullptr, stream); }
 int tgt_triplet_aggregate_bwd(const tgt_triplet_aggregate_args* a, void* stream) { return tgt_triplet_aggregate_bwd_skip(a, nullptr, stream); }
 int tgt_triplet_aggregate_fwd_skip(const tgt_triplet_aggregate_args* a, const float* graph_scale, void* stream) {

@@ -783,6 +783,23 @@ int mask_node_counts_run(const float* mask, int B, int N, int32_t* counts, hipSt
     return check_launch("mask_node_counts_kernel");
 }
 
+// Which family triplet_attention_run() launches for this call (TGT_TRI_FAMILY_*; negative: the call is refused).  Host logic on
+// sizes, dtype, flags, dropout_p, row lengths, offsets and pointer alignment only -- nothing is dereferenced, no device is touched;
+// null tensors are the entry point's own check.  triplet_attention_run() routes by it.
+int triplet_attention_family(const tgt_triplet_attention_args* a, bool bwd) {
+    if (!a || a->B < 0 || a->N < 0 || a->H <= 0) return -1;
+    if (a->B == 0 || a->N == 0) return TGT_TRI_FAMILY_NONE;
+    if (a->N > 128 || !(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return -1;
+    if (a->dtype != TGT_F32 && a->dtype != TGT_BF16 && a->dtype != TGT_F16) return -1;
+    if (a->N > 64) return a->D == 16 ? TGT_TRI_FAMILY_KB : -1;                   // key-blocked kernels (triplet_attention_kb.hip)
+    if (bwd ? tri_att16_bwd_eligible(*a) : tri_att16_fwd_eligible(*a)) return TGT_TRI_FAMILY_TILES16;      // 33 <= N <= 64, p == 0
+    if (bwd && tri_att_bwd2_eligible(*a)) return TGT_TRI_FAMILY_BWD2;            // N <= 32; p > 0 under TGT_TRI_DROP_FAST
+    if (a->D != 8 && a->D != 16 && a->D != 32) return -1;
+    const int esz = a->dtype == TGT_F32 ? 4 : 2;
+    if (a->H % 4 != 0 && a->D * esz < 16) return -1;                             // (dispatch_hg: one head per workgroup needs 16-byte rows)
+    return TGT_TRI_FAMILY_GENERAL;
+}
+
 // nc: per-graph node counts (tgt_hip.h, the *_counts entry points) or nullptr; DEVICE memory, never read here
 int triplet_attention_run(const tgt_triplet_attention_args* a, const int32_t* nc, bool bwd, hipStream_t st) {
     if (!a) return set_error(TGT_ERR_INVALID, "triplet attention: null args");
@@ -811,9 +828,11 @@ int triplet_attention_run(const tgt_triplet_attention_args* a, const int32_t* nc
         }
     }
     if (a->N > 64) return tri_att_kb_run(*a, nc, bwd, st);                         // key-blocked kernels; checks D and the workspace before any launch (node counts: used with TGT_TRI_COUNTS_KB only)
-    if (!bwd && tri_att16_fwd_eligible(*a)) return tri_att16_fwd_run(*a, nc, st);      // 33 <= N <= 64: 16-wide tiles (triplet_attention16.hip)
-    if (bwd && tri_att16_bwd_eligible(*a)) return tri_att16_bwd_run(*a, nc, st);
-    if (bwd && tri_att_bwd2_eligible(*a)) return tri_att_bwd2_run(*a, nc, st);
+    switch (triplet_attention_family(a, bwd)) {
+        case TGT_TRI_FAMILY_TILES16: return bwd ? tri_att16_bwd_run(*a, nc, st) : tri_att16_fwd_run(*a, nc, st);      // 33 <= N <= 64: 16-wide tiles (triplet_attention16.hip)
+        case TGT_TRI_FAMILY_BWD2: return tri_att_bwd2_run(*a, nc, st);
+        default: break;                                    // the general kernels, or a dtype / D / H they refuse below
+    }
     switch (a->dtype) {
         case TGT_F32: return tri_att_run_f32(*a, nc, bwd, st);
         case TGT_BF16: return tri_att_run_bf16(*a, nc, bwd, st);

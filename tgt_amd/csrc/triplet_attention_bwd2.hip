@@ -1,4 +1,5 @@
-// Triplet attention backward for the hot shapes (16-bit, D = 16, N <= 32, H % 8 == 0, no attention dropout) -- round-4 rebuild.
+// Triplet attention backward for the hot shapes (16-bit, D = 16, N <= 32, H % 8 == 0; attention dropout: the DROP instantiations,
+// TGT_TRI_DROP_FAST) -- round-4 rebuild.
 //
 // Same math and the same workgroup decomposition as tri_att_bwd_kernel (triplet_attention.hip: workgroup = (graph, direction,
 // 8 heads), wave = head, walk over the shared node j, slabs {Q | dO | K | V} of 32 rows x 256 B in two LDS sets, third-arm tiles
@@ -152,9 +153,14 @@ __device__ __forceinline__ void zero_grad_rows(__amdgpu_buffer_rsrc_t r_grd, uin
 }
 
 // FL >= 0: BIASED / GATED compiled in (the training instantiation); FL < 0: read from the arguments
-template <typename T, bool CS, int FL, bool DMA, typename... NC>
+// DROP: attention dropout (p > 0); the pack is then (TriSeedCtr[, counts]), and the p == 0 kernels keep their argument list.
+// With the keep mask m in {0, 1/(1-p)} of the forward (recomputed: tri_drop_bits, same unit and element as tri_att_fwd_kernel) and
+// A = softmax * gate, the forward used A m: dA = (V dO^T) m ahead of the softmax / gate backward, and dV^T is fed A m; the softmax
+// statistics, dE, dG, dQ, dK follow from the masked dA with the unmasked softmax and gate (tri_att_bwd_kernel does the same).  S^T
+// and dA^T are accumulator tiles (lane = i, register q <-> key acc_row(q, hi)): the layout the forward masks in.
+template <typename T, bool CS, int FL, bool DMA, bool DROP, typename... NC>
 __global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) tri_att_bwd2_kernel(const tgt_triplet_attention_args a, NC... nc) {
-    constexpr bool RG = sizeof...(NC) > 0;          // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
+    constexpr bool RG = sizeof...(NC) > (DROP ? 1 : 0);      // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
     const int32_t* node_counts = tri_counts_ptr(nc...);
     using F = frag_t<T>;
     constexpr int kOffXch = Lay<DMA>::kOffXch, kOffPart = Lay<DMA>::kOffPart;
@@ -298,6 +304,13 @@ __global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_e
         for (int k = 0; k < 4; ++k) csq[k] = f32x2{0.f, 0.f};
         csk[0] = csk[1] = csv[0] = csv[1] = f32x2{0.f, 0.f};
     }
+    // attention dropout: wave-uniform generator state; unit = (graph, direction, global head, shared node j) with the tensor's N
+    TriDrop drop;
+    uint32_t drop_unit0 = 0;
+    if constexpr (DROP) {
+        drop = tri_drop(a.dropout_p, a.dropout_seed, tri_seed_ptr(nc...));
+        drop_unit0 = (uint32_t)__builtin_amdgcn_readfirstlane(((c.b * 2 + c.dir) * a.H + c.h) * N);
+    }
 
     auto issue = [&](u32x4_t (&pre)[4], int jj) {
         const bool live = jj < n && !(ablate & 1);                      // (scalar: past the end every load is out of range)
@@ -422,6 +435,15 @@ __global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_e
         float sum = sum2.x + sum2.y;
         sum += xhalf(sum);
         const float inv = sum > 0.f ? fast_rcp(sum) : 0.f;
+        uint32_t keep = 0;
+        if constexpr (DROP) {      // the kept weights were scaled by 1/(1-p): dA (and A below) carry the mask
+            keep = tri_drop_bits(drop, drop_unit0 + (uint32_t)j, r, 0, hi);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                da[k].x = (keep >> (2 * k)) & 1u ? da[k].x * drop.scale : 0.f;
+                da[k].y = (keep >> (2 * k + 1)) & 1u ? da[k].y * drop.scale : 0.f;
+            }
+        }
         f32x2 delta2 = {0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -442,7 +464,13 @@ __global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_e
         for (int m = 0; m < 4; ++m) {
             const f32x2 ds0 = s[2 * m] * (da[2 * m] - delta), ds1 = s[2 * m + 1] * (da[2 * m + 1] - delta);
             if (biased) { dE[2 * m] += ds0; dE[2 * m + 1] += ds1; }
-            const f32x2 at0 = s[2 * m] * gate[2 * m], at1 = s[2 * m + 1] * gate[2 * m + 1];
+            f32x2 at0 = s[2 * m] * gate[2 * m], at1 = s[2 * m + 1] * gate[2 * m + 1];
+            if constexpr (DROP) {      // (registers 4m .. 4m + 3 of the tile)
+                at0.x = (keep >> (4 * m)) & 1u ? at0.x * drop.scale : 0.f;
+                at0.y = (keep >> (4 * m + 1)) & 1u ? at0.y * drop.scale : 0.f;
+                at1.x = (keep >> (4 * m + 2)) & 1u ? at1.x * drop.scale : 0.f;
+                at1.y = (keep >> (4 * m + 3)) & 1u ? at1.y * drop.scale : 0.f;
+            }
             const f32x2 e0 = ds0 * a.scale, e1 = ds1 * a.scale;
             const int cc = m & 1, o = 4 * (m >> 1);
             dsf[cc][o] = from_f32<T>(e0.x); dsf[cc][o + 1] = from_f32<T>(e0.y); dsf[cc][o + 2] = from_f32<T>(e1.x); dsf[cc][o + 3] = from_f32<T>(e1.y);
@@ -572,7 +600,7 @@ __global__ void __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_e
     }
 }
 
-template <typename T, bool CS, int FL>
+template <typename T, bool CS, int FL, bool DROP = false>
 static int launch_one(const tgt_triplet_attention_args& a_in, const int32_t* nc, hipStream_t st) {
 #ifdef TGT_PROBES
     tgt_triplet_attention_args a = a_in;
@@ -582,9 +610,26 @@ static int launch_one(const tgt_triplet_attention_args& a_in, const int32_t* nc,
 #endif
     static const bool dma = !(getenv("TGT_TRI_BWD2_DMA") && atoi(getenv("TGT_TRI_BWD2_DMA")) == 0);       // A/B knob
     const dim3 grid(a.B * 2 * (a.H / HG));
-    if (dma) return (nc ? launch_lds<tri_att_bwd2_kernel<T, CS, FL, true, const int32_t*>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<true>::kLds, st, a, nc) : launch_lds<tri_att_bwd2_kernel<T, CS, FL, true>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<true>::kLds, st, a));
-    return (nc ? launch_lds<tri_att_bwd2_kernel<T, CS, FL, false, const int32_t*>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<false>::kLds, st, a, nc) : launch_lds<tri_att_bwd2_kernel<T, CS, FL, false>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<false>::kLds, st, a));
+    if constexpr (DROP) {
+        const TriSeedCtr sc = {seed_counter()};         // the registered step counter, as the general launcher passes it
+        if (dma) return (nc ? launch_lds<tri_att_bwd2_kernel<T, CS, FL, true, true, TriSeedCtr, const int32_t*>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<true>::kLds, st, a, sc, nc) : launch_lds<tri_att_bwd2_kernel<T, CS, FL, true, true, TriSeedCtr>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<true>::kLds, st, a, sc));
+        return (nc ? launch_lds<tri_att_bwd2_kernel<T, CS, FL, false, true, TriSeedCtr, const int32_t*>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<false>::kLds, st, a, sc, nc) : launch_lds<tri_att_bwd2_kernel<T, CS, FL, false, true, TriSeedCtr>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<false>::kLds, st, a, sc));
+    } else {
+        if (dma) return (nc ? launch_lds<tri_att_bwd2_kernel<T, CS, FL, true, false, const int32_t*>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<true>::kLds, st, a, nc) : launch_lds<tri_att_bwd2_kernel<T, CS, FL, true, false>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<true>::kLds, st, a));
+        return (nc ? launch_lds<tri_att_bwd2_kernel<T, CS, FL, false, false, const int32_t*>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<false>::kLds, st, a, nc) : launch_lds<tri_att_bwd2_kernel<T, CS, FL, false, false>>("tri_att_bwd2_kernel", grid, dim3(kThreads), Lay<false>::kLds, st, a));
+    }
 }
+// The dropout instantiations are a translation unit of their own (TGT_BWD2_DROP_UNIT, tgt_amd/_lib.py): the plain unit holds the
+// kernels it always held, in the order and at the offsets it always had them.
+#ifdef TGT_BWD2_DROP_UNIT
+}  // namespace bwd2
+// attention dropout: one generic-flags variant each, as the general launcher has
+int tri_att_bwd2_drop_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
+    const bool cs = a.d_qkv_colsum[0] != nullptr;
+    if (a.dtype == TGT_BF16) return cs ? bwd2::launch_one<bf16_t, true, -1, true>(a, nc, st) : bwd2::launch_one<bf16_t, false, -1, true>(a, nc, st);
+    return cs ? bwd2::launch_one<f16_t, true, -1, true>(a, nc, st) : bwd2::launch_one<f16_t, false, -1, true>(a, nc, st);
+}
+#else
 template <typename T>
 static int launch(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
     constexpr int kBG = TGT_TRI_BIASED | TGT_TRI_GATED;
@@ -596,9 +641,14 @@ static int launch(const tgt_triplet_attention_args& a, const int32_t* nc, hipStr
 
 }  // namespace bwd2
 
+// A/B knob (triplet_common.hpp).  Read per call, not once: only calls with p > 0 ask, and one process can then run both arms
+bool tri_drop_fast() {
+    const char* v = getenv("TGT_TRI_DROP_FAST");
+    return !(v && atoi(v) == 0);
+}
 bool tri_att_bwd2_eligible(const tgt_triplet_attention_args& a) {
     static const bool off = getenv("TGT_TRI_BWD2") && atoi(getenv("TGT_TRI_BWD2")) == 0;      // A/B knob: 0 = the round-1..3 kernel
-    if (off || !((a.dtype == TGT_BF16 || a.dtype == TGT_F16) && a.D == 16 && a.N <= 32 && a.H % 8 == 0 && !(a.dropout_p > 0.f))) return false;
+    if (off || !((a.dtype == TGT_BF16 || a.dtype == TGT_F16) && a.D == 16 && a.N <= 32 && a.H % 8 == 0 && (!(a.dropout_p > 0.f) || tri_drop_fast()))) return false;
     // the third-arm tiles travel as 16-byte pieces (arm_load16 / arm_store16): row lengths and column offsets in whole pieces
     if (a.flags & (TGT_TRI_BIASED | TGT_TRI_GATED))
         for (int dir = 0; dir < 2; ++dir) {
@@ -608,8 +658,11 @@ bool tri_att_bwd2_eligible(const tgt_triplet_attention_args& a) {
         }
     return true;
 }
+int tri_att_bwd2_drop_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st);      // (the TGT_BWD2_DROP_UNIT unit)
 int tri_att_bwd2_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
+    if (a.dropout_p > 0.f) return tri_att_bwd2_drop_run(a, nc, st);
     return a.dtype == TGT_BF16 ? bwd2::launch<bf16_t>(a, nc, st) : bwd2::launch<f16_t>(a, nc, st);
 }
+#endif
 
 }  // namespace tgt

@@ -567,6 +567,20 @@ __device__ __forceinline__ TriCtx tri_ctx(const tgt_triplet_attention_args& a, i
 // so that instantiation has the argument list it always had; `const int32_t*` with them.
 __device__ __forceinline__ const int32_t* tri_counts_ptr() { return nullptr; }
 __device__ __forceinline__ const int32_t* tri_counts_ptr(const int32_t* p) { return p; }
+// The same device for the step counter of attention dropout in tri_att_bwd2_kernel: its DROP instantiations take a TriSeedCtr
+// AHEAD of the counts in that pack, the p == 0 instantiations keep the argument list they had.
+struct TriSeedCtr {
+    const uint64_t* p;
+};
+__device__ __forceinline__ const int32_t* tri_counts_ptr(TriSeedCtr) { return nullptr; }
+__device__ __forceinline__ const int32_t* tri_counts_ptr(TriSeedCtr, const int32_t* p) { return p; }
+__device__ __forceinline__ const uint64_t* tri_seed_ptr() { return nullptr; }
+__device__ __forceinline__ const uint64_t* tri_seed_ptr(const int32_t*) { return nullptr; }
+__device__ __forceinline__ const uint64_t* tri_seed_ptr(TriSeedCtr s) { return s.p; }
+__device__ __forceinline__ const uint64_t* tri_seed_ptr(TriSeedCtr s, const int32_t*) { return s.p; }
+// TGT_TRI_DROP_FAST (A/B): attention dropout inside tri_att_bwd2_kernel (N <= 32); 0: a backward with p > 0 is routed as before
+// that kernel had it, to tri_att_bwd_kernel (triplet_attention_bwd2.hip).  Host logic only.
+bool tri_drop_fast();
 template <bool RG>
 __device__ __forceinline__ int tri_node_count(const int32_t* node_counts, int b, int N) {
     if constexpr (RG) return min(max(node_counts[b], 0), N);

@@ -20,6 +20,7 @@ _SPEC = {
     'agg_proj64_infer': ('TGT_AGG_PROJ64_INFER', True, 'flag', 'the same at 33..64 nodes (tgt_triplet_aggregate_proj64_fwd): every edge row is projected once per shared node, for both query tiles'),
     'tri_proj64_infer': ('TGT_TRI_PROJ64_INFER', True, 'flag', 'a triplet attention forward of 33..64 nodes that no backward follows projects Q/K/V inside the kernel and never writes them (tgt_triplet_attention_proj64_fwd)'),
     'tri_proj64_train': ('TGT_TRI_PROJ64_TRAIN', False, 'flag', 'a triplet attention forward of 33..64 nodes that a backward follows projects Q/K/V inside the kernel and writes them once (tgt_triplet_attention_proj64_train_fwd) instead of a library GEMM + tgt_triplet_attention_fwd; opt-in: profiles/tri_proj64_train_ab.txt'),
+    'tri_drop_fast': ('TGT_TRI_DROP_FAST', True, 'flag', 'a triplet attention backward with attention dropout > 0 at N <= 32 stays on the round-4 kernel tri_att_bwd2 (0: tri_att_bwd_kernel, as before that kernel had dropout); the LIBRARY routes by this variable, the host only words its slow-path notice by it; profiles/tri_drop_fast_ab.txt'),
     'tri_colsum': ('TGT_TRI_COLSUM', True, 'flag', 'bias gradient of the fused projection from the backward kernel'),
     'tri_skip': ('TGT_TRI_SKIP', 1, 'int', 'triplet kernels skip DropPath-dropped graphs: 0 off, 1 forward, 2 backward too'),
     'tri_ragged': ('TGT_TRI_RAGGED', False, 'flag', 'triplet attention skips the padded nodes of every graph (N <= 64): per-graph node counts from the mask, once per forward; padded positions of the edge stream then hold other finite values'),
@@ -80,6 +81,7 @@ class Knobs:
     agg_proj64_infer: bool
     tri_proj64_infer: bool
     tri_proj64_train: bool
+    tri_drop_fast: bool
     tri_colsum: bool
     tri_skip: int
     tri_ragged: bool

@@ -29,6 +29,7 @@ _TRI_PROJ = K.tri_proj
 _TRI_PROJ_INFER = K.tri_proj_infer
 _TRI_PROJ64_INFER = K.tri_proj64_infer
 _TRI_PROJ64_TRAIN = K.tri_proj64_train
+_TRI_DROP_FAST = K.tri_drop_fast       # (the library routes the backward by the same variable; here it words the notice below)
 _AGG_PROJ_INFER = K.agg_proj_infer
 _AGG_PROJ64_INFER = K.agg_proj64_infer
 _TRI_COLSUM = K.tri_colsum
@@ -747,6 +748,10 @@ class _ProjectedTripletAttention(torch.autograd.Function):
                 _slow_path_notice(('tri_proj', why), 'triplet attention: the projection-fused forward / round-4 backward do not take this shape (N > 64); '
                                   'running the projection as library GEMMs + the key-blocked attention kernels (65 <= N <= 128, D = 16: online softmax '
                                   'forward, two-sweep backward, bias gradient by a separate column-sum pass; see DESIGN.md section 4)')
+            elif why == 'attention dropout > 0' and _TRI_DROP_FAST:
+                # (the backward of this call stays on the round-4 kernel, which has the dropout: tgt_triplet_attention_family)
+                _slow_path_notice(('tri_proj', why), 'triplet attention: the projection-fused forward does not take attention dropout > 0; running the '
+                                  'projection as library GEMMs + the general forward kernel (the backward stays on the round-4 kernel: DESIGN.md 4.zi)')
             else:
                 _slow_path_notice(('tri_proj', why), f'triplet attention: the projection-fused forward / round-4 backward do not take this shape ({why}); '
                                   'running the projection as library GEMMs + the general attention kernels (N in 33..64: 16-wide tiles at 0.39-0.45 of '
