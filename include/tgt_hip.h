@@ -134,11 +134,15 @@ int tgt_triplet_attention_bwd(const tgt_triplet_attention_args* a, void* stream)
  * flags, dropout_p, row lengths, offsets and pointer ALIGNMENT; dereferences nothing, touches no device.  A negative value: the
  * entry point refuses the call (null tensors are its own, later check).  Attention dropout (dropout_p > 0) at N <= 32 stays on
  * TGT_TRI_FAMILY_BWD2 (TGT_TRI_DROP_FAST=0 in the environment: GENERAL, the routing before that kernel had dropout); at 33..64
- * nodes it leaves the 16-wide tiles for GENERAL. */
+ * nodes it leaves the 16-wide tiles for GENERAL unless TGT_TRI_DROP16=1 is in the environment (read per call; default off):
+ * then a call that qualifies for TILES16 with p == 0, and whose E / G column blocks start at multiples of H, stays on
+ * TILES16 with p > 0, forward and backward each by its own conditions.  The drop pattern is the same in every family for
+ * N <= 64 (unit ((b*2 + dir)*H + h)*N + j, word (i*64 + k) >> 1), so any forward / backward pairing of GENERAL and TILES16 is
+ * valid, and N keeps its role in the unit index under node counts. */
 enum { /* B == 0 or N == 0: nothing is launched */                                                TGT_TRI_FAMILY_NONE = 0,
        /* 32-wide tiles, N <= 64, every dtype (csrc/triplet_attention.hip) */                     TGT_TRI_FAMILY_GENERAL = 1,
        /* backward of 16-bit, D = 16, N <= 32, H % 8 == 0 (csrc/triplet_attention_bwd2.hip) */    TGT_TRI_FAMILY_BWD2 = 2,
-       /* 16-wide tiles, 33..64 nodes, 16-bit, D = 16, p == 0 (csrc/triplet_attention16.hip) */   TGT_TRI_FAMILY_TILES16 = 3,
+       /* 16-wide tiles, 33..64 nodes, 16-bit, D = 16 (csrc/triplet_attention16.hip) */           TGT_TRI_FAMILY_TILES16 = 3,
        /* key-blocked kernels, 65 <= N <= 128, D = 16 (csrc/triplet_attention_kb.hip) */          TGT_TRI_FAMILY_KB = 4 };
 int tgt_triplet_attention_family(const tgt_triplet_attention_args* a, int32_t bwd);
 

@@ -20,7 +20,9 @@ CSRC = os.path.join(_HERE, 'csrc')
 SOURCES = ['capi.hip', 'optimizer.hip', 'edge_gemm.hip', 'edge_gated.hip', 'edge_glu.hip', 'edge_act.hip', 'edge_live.hip', 'edge_wgrad.hip', 'params.hip', 'loss.hip', 'predict.hip', 'gaussian.hip', 'triplet_attention_proj.hip', 'triplet_attention_proj64.hip',
            ('triplet_attention_proj64.hip', ['-DTGT_TRI_PROJ64_INST=2'], '.train'),      # (the storing form: a unit of its own)
            ('triplet_attention.hip', ['-DTGT_TRI_INST=9'], '.f32'), ('triplet_attention.hip', ['-DTGT_TRI_INST=2'], '.bf16'),
-           ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip', 'triplet_attention_bwd2.hip',
+           ('triplet_attention.hip', ['-DTGT_TRI_INST=4'], '.f16'), 'triplet_attention16.hip',
+           ('triplet_attention16.hip', ['-DTGT_T16_DROP_UNIT'], '.drop'),           # (its attention-dropout instantiations: a unit of their own)
+           'triplet_attention_bwd2.hip',
            ('triplet_attention_bwd2.hip', ['-DTGT_BWD2_DROP_UNIT'], '.drop'),       # (its attention-dropout instantiations: a unit of their own)
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=9'], '.f32'), ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=2'], '.bf16'),
            ('triplet_attention_kb.hip', ['-DTGT_TRIKB_INST=4'], '.f16'), ('triplet_aggregate.hip', ['-DTGT_AGG_INST=1'], '.plain'),

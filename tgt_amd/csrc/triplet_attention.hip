@@ -792,7 +792,7 @@ int triplet_attention_family(const tgt_triplet_attention_args* a, bool bwd) {
     if (a->N > 128 || !(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return -1;
     if (a->dtype != TGT_F32 && a->dtype != TGT_BF16 && a->dtype != TGT_F16) return -1;
     if (a->N > 64) return a->D == 16 ? TGT_TRI_FAMILY_KB : -1;                   // key-blocked kernels (triplet_attention_kb.hip)
-    if (bwd ? tri_att16_bwd_eligible(*a) : tri_att16_fwd_eligible(*a)) return TGT_TRI_FAMILY_TILES16;      // 33 <= N <= 64, p == 0
+    if (bwd ? tri_att16_bwd_eligible(*a) : tri_att16_fwd_eligible(*a)) return TGT_TRI_FAMILY_TILES16;      // 33 <= N <= 64; p > 0 under TGT_TRI_DROP16
     if (bwd && tri_att_bwd2_eligible(*a)) return TGT_TRI_FAMILY_BWD2;            // N <= 32; p > 0 under TGT_TRI_DROP_FAST
     if (a->D != 8 && a->D != 16 && a->D != 32) return -1;
     const int esz = a->dtype == TGT_F32 ? 4 : 2;

@@ -100,6 +100,20 @@ __device__ __forceinline__ frag4_t<T> frag_of(const char* slab, int row, int hw,
     return f;
 }
 
+// the generator state of a call is the same in every lane, but threshold and scale come out of float arithmetic, i.e. in vector
+// registers, and hipcc folds the readfirstlane builtin of a value it knows to be uniform: the empty statement hides that from it.
+// The instruction itself stays the compiler's, which then also places it: inside an asm statement it is opaque to the hazard
+// recognizer and the scheduler.
+__device__ __forceinline__ uint32_t to_sgpr(uint32_t v) {
+    asm("" : "+v"(v));
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+__device__ __forceinline__ TriDrop drop_uniform(TriDrop d) {
+    d.thresh16 = to_sgpr(d.thresh16);
+    d.scale = __uint_as_float(to_sgpr(__float_as_uint(d.scale)));
+    return d;
+}
+
 // third-arm stage: the (x, y) pair records [E of the HG heads | G of the HG heads] of the whole graph + the mask, in memory
 // order (x, y); element (query i, key k) of direction 0 sits at (x, y) = (i, k), of direction 1 at (k, i)
 template <typename T, int HG, int NQ>
@@ -110,9 +124,11 @@ struct Arm16 {
     static constexpr int kBytes = kOffM + R * kMPitch;
 };
 
-template <typename T, int HG, int NQ, typename... NC>
+// DROP: attention dropout (p > 0) on the gated weights, the pattern of tri_att_fwd_kernel bit for bit (tri_drop_bits16); the pack is
+// then (TriSeedCtr[, counts]) and the p == 0 kernels keep their argument list (triplet_common.hpp)
+template <typename T, int HG, int NQ, bool DROP, typename... NC>
 __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_triplet_attention_args a, NC... nc) {
-    constexpr bool RG = sizeof...(NC) > 0;          // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
+    constexpr bool RG = sizeof...(NC) > (DROP ? 1 : 0);          // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
     const int32_t* node_counts = tri_counts_ptr(nc...);
     using G = Geo16<T, HG, NQ>;
     using A = Arm16<T, HG, NQ>;
@@ -140,6 +156,16 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_t
         return;
     }
 
+    // attention dropout: wave-uniform generator state, in scalar registers; unit = (graph, direction, global head, shared node j) with
+    // the tensor's N.  Here and not at the walk: hipcc keeps the sigmoids of the third arm below in flight up to the walk's first
+    // step -- that is the register peak of this kernel -- and the float arithmetic of threshold and scale would sit on top of it.
+    TriDrop drop;
+    uint32_t drop_unit0 = 0;
+    if constexpr (DROP) {
+        drop = drop_uniform(tri_drop(a.dropout_p, a.dropout_seed, tri_seed_ptr(nc...)));
+        drop_unit0 = (uint32_t)__builtin_amdgcn_readfirstlane(((b * 2 + dir) * a.H + grp * HG + hw) * N);
+    }
+
     // ---- third arm of this wave: bias + mask and gate for (query 16 qb + x16, keys 16 kb + 4 g + q) ----
     float biasM[NQ][4], gate[NQ][4];
     {
@@ -164,7 +190,7 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_t
         __syncthreads();
         const int i = 16 * qb + x16;
 #pragma unroll
-        for (int kb = 0; kb < NQ; ++kb)
+        for (int kb = 0; kb < NQ; ++kb) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int k = 16 * kb + 4 * g + q;
@@ -175,7 +201,12 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_t
                 const float m = *reinterpret_cast<const float*>(smem + A::kOffM + xx * A::kMPitch + yy * 4);
                 biasM[kb][q] = k < N ? e + m : -INFINITY;
                 gate[kb][q] = (i < N && k < N) ? (gated ? fast_sigmoid(gl + m) : 1.f) : 0.f;
+                // hipcc sinks these selects into the head of the walk and keeps their inputs (two to three registers per element) in
+                // flight up to there, which is the register peak of this kernel; the DROP kernels, with one more register of state in
+                // the walk, settle the values here instead and stay at the registers of their p == 0 siblings
+                if constexpr (DROP) asm volatile("" : "+v"(biasM[kb][q]), "+v"(gate[kb][q]));
             }
+        }
         __syncthreads();
     }
 
@@ -202,6 +233,11 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_t
     }
     __syncthreads();
 
+    uint32_t drop_lane = 0;
+    if constexpr (DROP) {
+        drop_lane = tri_drop_lane16(16 * qb + x16, g);
+        asm("" : "+v"(drop_lane));         // (one register: hipcc would otherwise keep a copy per hash word)
+    }
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     // one barrier per j: hazards as in triplet_attention.hip (the other set is rewritten at the top of the iteration by the
     // thread that last read those chunks; O goes into this wave's own rows / columns of the Q slab)
@@ -245,12 +281,18 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_fwd_kernel(const tgt_t
             }
         sum = xor16_sum(sum);
         sum += xhalf(sum);
-        const float inv = fast_rcp(sum);
+        const uint32_t drop_base = DROP ? tri_drop_base(drop, drop_unit0 + (uint32_t)j) : 0u;
+        const float inv = DROP ? fast_rcp(sum) * drop.scale : fast_rcp(sum);      // (the 1/(1-p) of the kept weights rides on the normaliser)
         f32x4 o = z;
 #pragma unroll
         for (int kb = 0; kb < NQ; ++kb) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) s[kb][q] = s[kb][q] * inv * gate[kb][q];
+            if constexpr (DROP) {     // attention dropout on the gated weights
+                const uint32_t keep = tri_drop_bits16(drop, drop_base, drop_lane, kb);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) s[kb][q] = (keep >> q) & 1u ? s[kb][q] : 0.f;
+            }
             // V^T of the key block (lane d, keys 4g..4g+3) straight from the slab, transposed by the read (round 4: was V . I on the matrix core + a pack)
             o = mma16(tr_frag<T>(sV + G::lds_elem(16 * kb + 4 * g + (x16 >> 2), hw * 16 + 4 * (x16 & 3))), pack4<T>(s[kb]), o);          // O^T[d][query]
         }
@@ -289,9 +331,12 @@ __device__ __forceinline__ void zero_grad_rows(const SlabBuf& gQ, const SlabBuf&
     }
 }
 
-template <typename T, int HG, int NQ, bool CS, typename... NC>
+// DROP: attention dropout (p > 0), the algebra above tri_att_bwd2_kernel (triplet_attention_bwd2.hip): with the forward's keep factor
+// m in {0, 1/(1-p)} (recomputed: tri_drop_bits16, same unit and element) dA = (V dO^T) m ahead of delta, dS and dG, and phase 2 gets
+// A m for dV; softmax and gate stay unmasked.  The pack is then (TriSeedCtr[, counts]).
+template <typename T, int HG, int NQ, bool CS, bool DROP, typename... NC>
 __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_bwd_kernel(const tgt_triplet_attention_args a, NC... nc) {
-    constexpr bool RG = sizeof...(NC) > 0;          // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
+    constexpr bool RG = sizeof...(NC) > (DROP ? 1 : 0);          // ragged: launched with the node counts as a trailing argument (triplet_common.hpp)
     const int32_t* node_counts = tri_counts_ptr(nc...);
     using G = Geo16<T, HG, NQ>;
     using A = Arm16<T, HG, NQ>;
@@ -382,6 +427,14 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_bwd_kernel(const tgt_t
     // (node_counts): the walk ends at the graph's own n, and the units j >= n get those zero rows ahead of it (n = 0: every load of
     // the walk is out of range).
     const bool dead = a.graph_scale && a.graph_scale[b] == 0.f;          // workgroup-uniform
+    TriDrop drop;
+    uint32_t drop_unit0 = 0, drop_lane = 0;
+    if constexpr (DROP) {
+        drop = drop_uniform(tri_drop(a.dropout_p, a.dropout_seed, tri_seed_ptr(nc...)));
+        drop_unit0 = (uint32_t)__builtin_amdgcn_readfirstlane(((b * 2 + dir) * a.H + grp * HG + hw) * N);
+        drop_lane = tri_drop_lane16(16 * qb + x16, g);
+        asm("" : "+v"(drop_lane));         // (one register: hipcc would otherwise keep a copy per hash word)
+    }
     if (dead) {
         zero_grad_rows<G, R>(gQ, gK, gV, 0, N, tid);
     } else {
@@ -487,6 +540,17 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_bwd_kernel(const tgt_t
             sum = xor16_sum(sum);
             sum += xhalf(sum);
             const float inv = sum > 0.f ? fast_rcp(sum) : 0.f;
+            uint32_t keep = 0;
+            if constexpr (DROP) {      // the kept weights were scaled by 1/(1-p): dA (and A below) carry the mask; bits 4 kb + q
+                const uint32_t drop_base = tri_drop_base(drop, drop_unit0 + (uint32_t)j);
+#pragma unroll
+                for (int kb = 0; kb < NQ; ++kb) {
+                    const uint32_t kp = tri_drop_bits16(drop, drop_base, drop_lane, kb);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) da[kb][q] = (kp >> q) & 1u ? da[kb][q] * drop.scale : 0.f;
+                    keep |= kp << (4 * kb);
+                }
+            }
             float delta = 0.f;
 #pragma unroll
             for (int kb = 0; kb < NQ; ++kb)
@@ -523,6 +587,7 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_bwd_kernel(const tgt_t
                     if (biased) dE[kb][q] += ds;
                     dsv[q] = ds * a.scale;
                     atv[q] = s[kb][q] * gate[kb][q];
+                    if constexpr (DROP) atv[q] = (keep >> (4 * kb + q)) & 1u ? atv[q] * drop.scale : 0.f;
                 }
                 // block[query][key], as the accumulator holds it (lane = query, keys 4g..4g+3): one 8-byte store each; phase 2
                 // reads them transposed
@@ -648,7 +713,7 @@ __global__ void __launch_bounds__(HG * NQ * 64) tri_att16_bwd_kernel(const tgt_t
     }
 }
 
-template <typename T, int HG, int NQ>
+template <typename T, int HG, int NQ, bool DROP = false>
 static int launch_bwd(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
     using G = Geo16<T, HG, NQ>;
     constexpr int E = 16 / (int)sizeof(T);
@@ -659,45 +724,93 @@ static int launch_bwd(const tgt_triplet_attention_args& a, const int32_t* nc, hi
     static_assert(kLds <= 160 * 1024, "LDS");
     const bool cs = a.d_qkv_colsum[0] != nullptr;
     const int grid = a.B * 2 * (a.H / HG);
-    if (cs) return (nc ? launch_lds<tri_att16_bwd_kernel<T, HG, NQ, true, const int32_t*>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a, nc) : launch_lds<tri_att16_bwd_kernel<T, HG, NQ, true>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a));
-    return (nc ? launch_lds<tri_att16_bwd_kernel<T, HG, NQ, false, const int32_t*>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a, nc) : launch_lds<tri_att16_bwd_kernel<T, HG, NQ, false>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a));
+    if constexpr (DROP) {
+        const TriSeedCtr sc = {seed_counter()};         // the registered step counter, as the general launcher passes it
+        if (cs) return (nc ? launch_lds<tri_att16_bwd_kernel<T, HG, NQ, true, true, TriSeedCtr, const int32_t*>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a, sc, nc) : launch_lds<tri_att16_bwd_kernel<T, HG, NQ, true, true, TriSeedCtr>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a, sc));
+        return (nc ? launch_lds<tri_att16_bwd_kernel<T, HG, NQ, false, true, TriSeedCtr, const int32_t*>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a, sc, nc) : launch_lds<tri_att16_bwd_kernel<T, HG, NQ, false, true, TriSeedCtr>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a, sc));
+    } else {
+        if (cs) return (nc ? launch_lds<tri_att16_bwd_kernel<T, HG, NQ, true, false, const int32_t*>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a, nc) : launch_lds<tri_att16_bwd_kernel<T, HG, NQ, true, false>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a));
+        return (nc ? launch_lds<tri_att16_bwd_kernel<T, HG, NQ, false, false, const int32_t*>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a, nc) : launch_lds<tri_att16_bwd_kernel<T, HG, NQ, false, false>>("tri_att16_bwd_kernel", dim3(grid), dim3(G::kThreads), kLds, st, a));
+    }
 }
 
-template <typename T, int HG, int NQ>
+template <typename T, int HG, int NQ, bool DROP = false>
 static int launch(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
     using G = Geo16<T, HG, NQ>;
     constexpr int kArm = Arm16<T, HG, NQ>::kBytes, kSlabs = 2 * 3 * G::kSlabBytes;
     constexpr int kLds = kArm > kSlabs ? kArm : kSlabs;
     static_assert(kLds <= 160 * 1024, "LDS");
-    return (nc ? launch_lds<tri_att16_fwd_kernel<T, HG, NQ, const int32_t*>>("tri_att16_fwd_kernel", dim3(a.B * 2 * (a.H / HG)), dim3(G::kThreads), kLds, st, a, nc) : launch_lds<tri_att16_fwd_kernel<T, HG, NQ>>("tri_att16_fwd_kernel", dim3(a.B * 2 * (a.H / HG)), dim3(G::kThreads), kLds, st, a));
+    if constexpr (DROP) {
+        const TriSeedCtr sc = {seed_counter()};
+        return (nc ? launch_lds<tri_att16_fwd_kernel<T, HG, NQ, true, TriSeedCtr, const int32_t*>>("tri_att16_fwd_kernel", dim3(a.B * 2 * (a.H / HG)), dim3(G::kThreads), kLds, st, a, sc, nc) : launch_lds<tri_att16_fwd_kernel<T, HG, NQ, true, TriSeedCtr>>("tri_att16_fwd_kernel", dim3(a.B * 2 * (a.H / HG)), dim3(G::kThreads), kLds, st, a, sc));
+    } else {
+        return (nc ? launch_lds<tri_att16_fwd_kernel<T, HG, NQ, false, const int32_t*>>("tri_att16_fwd_kernel", dim3(a.B * 2 * (a.H / HG)), dim3(G::kThreads), kLds, st, a, nc) : launch_lds<tri_att16_fwd_kernel<T, HG, NQ, false>>("tri_att16_fwd_kernel", dim3(a.B * 2 * (a.H / HG)), dim3(G::kThreads), kLds, st, a));
+    }
 }
 
-template <typename T>
+template <typename T, bool DROP = false>
 static int run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
-    return a.N <= 48 ? launch<T, 4, 3>(a, nc, st) : launch<T, 4, 4>(a, nc, st);
+    return a.N <= 48 ? launch<T, 4, 3, DROP>(a, nc, st) : launch<T, 4, 4, DROP>(a, nc, st);
+}
+template <typename T, bool DROP = false>
+static int run_bwd(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
+    // four blocks: 2 heads x 4 waves (8 waves, up to 256 registers; 64-byte row pieces) -- 16 waves would leave 128 registers
+    return a.N <= 48 ? launch_bwd<T, 4, 3, DROP>(a, nc, st) : launch_bwd<T, 2, 4, DROP>(a, nc, st);
 }
 
 }  // namespace t16
+
+// The dropout instantiations are a translation unit of their own (TGT_T16_DROP_UNIT, tgt_amd/_lib.py): the plain unit holds the
+// kernels it always held, not co-compiled with them (triplet_common.hpp).
+#ifdef TGT_T16_DROP_UNIT
+int tri_att16_fwd_drop_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
+    return a.dtype == TGT_BF16 ? t16::run<bf16_t, true>(a, nc, st) : t16::run<f16_t, true>(a, nc, st);
+}
+int tri_att16_bwd_drop_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
+    return a.dtype == TGT_BF16 ? t16::run_bwd<bf16_t, true>(a, nc, st) : t16::run_bwd<f16_t, true>(a, nc, st);
+}
+#else
+int tri_att16_fwd_drop_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st);      // (the TGT_T16_DROP_UNIT unit)
+int tri_att16_bwd_drop_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st);
+
+// A/B knob (triplet_common.hpp), default off.  Read per call, not once: only calls with p > 0 ask, and one process can run both arms
+bool tri_drop16() {
+    const char* v = getenv("TGT_TRI_DROP16");
+    return v && atoi(v) != 0;
+}
+// a call with attention dropout: under TGT_TRI_DROP16 only, and only with the third arm laid out as the fused projection row has
+// it -- E and G as blocks of H columns that start at multiples of H.  The kernels read the third arm element by element and would
+// take any offset; this is the set of layouts the DROP instantiations are held to by the tests, any other keeps the general kernels
+static bool tri_att16_drop_ok(const tgt_triplet_attention_args& a) {
+    if (!(a.dropout_p > 0.f)) return true;
+    if (!tri_drop16()) return false;
+    for (int dir = 0; dir < 2; ++dir) {
+        if ((a.flags & TGT_TRI_BIASED) && a.e_off[dir] % a.H) return false;
+        if ((a.flags & TGT_TRI_GATED) && a.g_off[dir] % a.H) return false;
+    }
+    return true;
+}
 
 // backward on 16-wide tiles: as the forward (N <= 48: 4 heads x 3 blocks; 49..64: 2 heads x 4 blocks)
 // The same kernels for 17 <= N <= 32 (two blocks, 8 heads x 2 waves) were measured in round 2 and are gone: forward 254.8 -> 242.5 us
 // but backward 484 -> 617 us (128 registers at 16 waves spill, two barriers per j); N <= 32 stays on the 32-wide kernels.
 bool tri_att16_bwd_eligible(const tgt_triplet_attention_args& a) {
     return (a.dtype == TGT_BF16 || a.dtype == TGT_F16) && a.D == 16 && ((a.N > 32 && a.N <= 48 && a.H % 4 == 0) || (a.N > 48 && a.N <= 64 && a.H % 2 == 0)) &&
-           !(a.dropout_p > 0.f);
+           tri_att16_drop_ok(a);
 }
 int tri_att16_bwd_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
-    // four blocks: 2 heads x 4 waves (8 waves, up to 256 registers; 64-byte row pieces) -- 16 waves would leave 128 registers
-    if (a.N > 48) return a.dtype == TGT_BF16 ? t16::launch_bwd<bf16_t, 2, 4>(a, nc, st) : t16::launch_bwd<f16_t, 2, 4>(a, nc, st);
-    return a.dtype == TGT_BF16 ? t16::launch_bwd<bf16_t, 4, 3>(a, nc, st) : t16::launch_bwd<f16_t, 4, 3>(a, nc, st);
+    if (a.dropout_p > 0.f) return tri_att16_bwd_drop_run(a, nc, st);
+    return a.dtype == TGT_BF16 ? t16::run_bwd<bf16_t>(a, nc, st) : t16::run_bwd<f16_t>(a, nc, st);
 }
 
-// forward on 16-wide tiles: 16-bit, D = 16, 33 <= N <= 64, H a multiple of 4, no attention dropout
+// forward on 16-wide tiles: 16-bit, D = 16, 33 <= N <= 64, H a multiple of 4; attention dropout under TGT_TRI_DROP16
 bool tri_att16_fwd_eligible(const tgt_triplet_attention_args& a) {
-    return (a.dtype == TGT_BF16 || a.dtype == TGT_F16) && a.D == 16 && a.N > 32 && a.N <= 64 && a.H % 4 == 0 && !(a.dropout_p > 0.f);
+    return (a.dtype == TGT_BF16 || a.dtype == TGT_F16) && a.D == 16 && a.N > 32 && a.N <= 64 && a.H % 4 == 0 && tri_att16_drop_ok(a);
 }
 int tri_att16_fwd_run(const tgt_triplet_attention_args& a, const int32_t* nc, hipStream_t st) {
+    if (a.dropout_p > 0.f) return tri_att16_fwd_drop_run(a, nc, st);
     return a.dtype == TGT_BF16 ? t16::run<bf16_t>(a, nc, st) : t16::run<f16_t>(a, nc, st);
 }
+#endif
 
 }  // namespace tgt

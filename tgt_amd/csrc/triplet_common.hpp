@@ -531,6 +531,23 @@ __device__ __forceinline__ uint32_t tri_drop_bits_t(const TriDrop& d, uint32_t u
     }
     return bits;
 }
+// the same elements in the 16 x 16 x 16 accumulator layout of triplet_attention16.hip: lane (query i, g = lane >> 4) holds keys
+// k = 16*blk + 4g + q of key block `blk`, q = 0..3 -- two hash words per block and lane; bit q <-> key q.  N <= 64: stride 64.
+// The word index (i*64 + k) >> 1 = (i*32 + 2g) + (8*blk + w) splits into a part of the lane and a part of the block, and the
+// unit's base is the same in every lane, so a kernel keeps ONE vector register of generator state (tri_drop_lane16: fixed for the
+// whole walk) and everything else in scalar ones (tri_drop_base: once per unit).
+__device__ __forceinline__ uint32_t tri_drop_base(const TriDrop& d, uint32_t unit) { return mix32(d.seed_lo ^ mix32(unit)) + d.seed_hi; }
+__device__ __forceinline__ uint32_t tri_drop_lane16(int i, int g) { return (uint32_t)(i * 32 + 2 * g) * 0x9e3779b9u; }
+__device__ __forceinline__ uint32_t tri_drop_bits16(const TriDrop& d, uint32_t base, uint32_t lane16, int blk) {
+    uint32_t bits = 0;
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+        const uint32_t r = mix32((base + (uint32_t)(8 * blk + w) * 0x9e3779b9u) + lane16);
+        bits |= ((r & 0xffffu) >= d.thresh16 ? 1u : 0u) << (2 * w);
+        bits |= ((r >> 16) >= d.thresh16 ? 1u : 0u) << (2 * w + 1);
+    }
+    return bits;
+}
 
 // ---------------------------------------------------------------------------
 // workgroup coordinates and slab sources of the triplet kernels
@@ -581,6 +598,10 @@ __device__ __forceinline__ const uint64_t* tri_seed_ptr(TriSeedCtr s, const int3
 // TGT_TRI_DROP_FAST (A/B): attention dropout inside tri_att_bwd2_kernel (N <= 32); 0: a backward with p > 0 is routed as before
 // that kernel had it, to tri_att_bwd_kernel (triplet_attention_bwd2.hip).  Host logic only.
 bool tri_drop_fast();
+// TGT_TRI_DROP16 (A/B, default off): attention dropout inside the 16-wide-tile kernels for 33..64 nodes (the DROP instantiations of
+// triplet_attention16.hip, same pack convention as above); unset / 0: a call with p > 0 at those sizes goes to the general kernels.
+// Read per call.  Host logic only.
+bool tri_drop16();
 template <bool RG>
 __device__ __forceinline__ int tri_node_count(const int32_t* node_counts, int b, int N) {
     if constexpr (RG) return min(max(node_counts[b], 0), N);

@@ -21,6 +21,7 @@ _SPEC = {
     'tri_proj64_infer': ('TGT_TRI_PROJ64_INFER', True, 'flag', 'a triplet attention forward of 33..64 nodes that no backward follows projects Q/K/V inside the kernel and never writes them (tgt_triplet_attention_proj64_fwd)'),
     'tri_proj64_train': ('TGT_TRI_PROJ64_TRAIN', False, 'flag', 'a triplet attention forward of 33..64 nodes that a backward follows projects Q/K/V inside the kernel and writes them once (tgt_triplet_attention_proj64_train_fwd) instead of a library GEMM + tgt_triplet_attention_fwd; opt-in: profiles/tri_proj64_train_ab.txt'),
     'tri_drop_fast': ('TGT_TRI_DROP_FAST', True, 'flag', 'a triplet attention backward with attention dropout > 0 at N <= 32 stays on the round-4 kernel tri_att_bwd2 (0: tri_att_bwd_kernel, as before that kernel had dropout); the LIBRARY routes by this variable, the host only words its slow-path notice by it; profiles/tri_drop_fast_ab.txt'),
+    'tri_drop16': ('TGT_TRI_DROP16', False, 'flag', 'triplet attention with attention dropout > 0 at 33..64 nodes runs on the 16-wide-tile kernels tri_att16_fwd_kernel / tri_att16_bwd_kernel (their DROP instantiations) instead of the general 32-wide kernels; forward and backward route independently, the pattern is the same bit for bit; the LIBRARY routes by this variable, per call, the host only words its slow-path notice by it; opt-in: profiles/tri_drop16_ab.txt'),
     'tri_colsum': ('TGT_TRI_COLSUM', True, 'flag', 'bias gradient of the fused projection from the backward kernel'),
     'tri_skip': ('TGT_TRI_SKIP', 1, 'int', 'triplet kernels skip DropPath-dropped graphs: 0 off, 1 forward, 2 backward too'),
     'tri_ragged': ('TGT_TRI_RAGGED', False, 'flag', 'triplet attention skips the padded nodes of every graph (N <= 64): per-graph node counts from the mask, once per forward; padded positions of the edge stream then hold other finite values'),
@@ -72,6 +73,13 @@ def _read(var, default, kind):
     return raw != '0' if default else raw == '1'
 
 
+def library_flag_now(name):
+    """a default-off flag the LIBRARY reads per call (TGT_TRI_DROP16: one process can run both arms), as the library sees it now;
+    `K` keeps the value at import.  Only the wording of a host notice may depend on it.  Read by the rule of every flag here ("1" is
+    on); the library takes any value atoi() gives a non-zero number for -- set it to 0 or 1."""
+    return _read(*_SPEC[name][:3])
+
+
 @dataclass(frozen=True)
 class Knobs:
     tri_split: bool
@@ -82,6 +90,7 @@ class Knobs:
     tri_proj64_infer: bool
     tri_proj64_train: bool
     tri_drop_fast: bool
+    tri_drop16: bool
     tri_colsum: bool
     tri_skip: int
     tri_ragged: bool

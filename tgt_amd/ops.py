@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from . import gemm as _gemm
+from . import knobs as _knobs
 from .knobs import K
 
 _DT = {torch.float32: _lib.TGT_F32, torch.bfloat16: _lib.TGT_BF16, torch.float16: _lib.TGT_F16}
@@ -30,6 +31,7 @@ _TRI_PROJ_INFER = K.tri_proj_infer
 _TRI_PROJ64_INFER = K.tri_proj64_infer
 _TRI_PROJ64_TRAIN = K.tri_proj64_train
 _TRI_DROP_FAST = K.tri_drop_fast       # (the library routes the backward by the same variable; here it words the notice below)
+_TRI_DROP16 = K.tri_drop16             # (33..64 nodes with attention dropout; the library reads TGT_TRI_DROP16 per call, and so does the notice)
 _AGG_PROJ_INFER = K.agg_proj_infer
 _AGG_PROJ64_INFER = K.agg_proj64_infer
 _TRI_COLSUM = K.tri_colsum
@@ -748,6 +750,15 @@ class _ProjectedTripletAttention(torch.autograd.Function):
                 _slow_path_notice(('tri_proj', why), 'triplet attention: the projection-fused forward / round-4 backward do not take this shape (N > 64); '
                                   'running the projection as library GEMMs + the key-blocked attention kernels (65 <= N <= 128, D = 16: online softmax '
                                   'forward, two-sweep backward, bias gradient by a separate column-sum pass; see DESIGN.md section 4)')
+            elif why == 'N > 32' and dropout[0]:
+                # (33..64 nodes with attention dropout: the library routes the attention core by TGT_TRI_DROP16, per call)
+                on = _knobs.library_flag_now('tri_drop16')
+                core = ('the 16-wide-tile kernels tri_att16_fwd_kernel / tri_att16_bwd_kernel, dropout included (TGT_TRI_DROP16=1; each direction '
+                        'where its head count qualifies, the general kernel otherwise)' if on else
+                        'the general 32-wide kernels tri_att_fwd_kernel / tri_att_bwd_kernel (the 16-wide tiles take attention dropout under '
+                        'TGT_TRI_DROP16=1 only)')
+                _slow_path_notice(('tri_proj', why, 'dropout', on), 'triplet attention: the projection-fused forwards do not take attention dropout > 0 '
+                                  f'(N > 32); running the projection as library GEMMs + {core}; see DESIGN.md 4.zj')
             elif why == 'attention dropout > 0' and _TRI_DROP_FAST:
                 # (the backward of this call stays on the round-4 kernel, which has the dropout: tgt_triplet_attention_family)
                 _slow_path_notice(('tri_proj', why), 'triplet attention: the projection-fused forward does not take attention dropout > 0; running the '

@@ -1,11 +1,17 @@
-"""A/B of triplet attention with attention dropout at the headline shape: forward + backward of ops.projected_triplet_attention in
-ONE process, the arms alternating round by round:
+"""A/B of triplet attention with attention dropout: forward + backward of ops.projected_triplet_attention in ONE process, the arms
+alternating round by round.  At the headline shape (`--nodes` <= 32):
 
     new_p        this tree, dropout p: library GEMMs + tri_att_fwd_kernel, backward on tri_att_bwd2_kernel's dropout instantiation
     new_p_off    this tree with TGT_TRI_DROP_FAST=0 (the library asks per call): the backward on tri_att_bwd_kernel, as the parent has it
     new_0        this tree, p = 0: the projection-fused forward + tri_att_bwd2_kernel
     parent_p     a SECOND build of the library (`--parent-lib`, the parent commit built in another checkout), dropout p
     parent_0     the same, p = 0
+
+At 33..64 nodes (`--nodes 48 --batch 128`) the switch of the arms is TGT_TRI_DROP16, which the library also asks per call:
+
+    new_p        TGT_TRI_DROP16=1: library GEMMs + the DROP instantiations of tri_att16_fwd_kernel / tri_att16_bwd_kernel
+    new_p_off    TGT_TRI_DROP16=0, the default: library GEMMs + the general 32-wide kernels, which is the parent's code
+    new_0        p = 0: library GEMMs + the p = 0 kernels of the 16-wide tiles
 
 The host code of the arms is this tree's: the parent's differs from it in the wording of a notice only, so `parent_*` swaps the
 LIBRARY under it (loaded beside this tree's, RTLD_DEEPBIND).  Time: HIP events around `--iters` forward + backward pairs after
@@ -81,13 +87,14 @@ def main():
     def arm(lib, p, fast):
         def run():
             _lib._lib = lib
-            os.environ['TGT_TRI_DROP_FAST'] = '1' if fast else '0'
+            os.environ['TGT_TRI_DROP_FAST'] = os.environ['TGT_TRI_DROP16'] = '1' if fast else '0'
             try:
                 out = ops.projected_triplet_attention(x, w, b, mask3, L, dropout=(p, SEED if p else 0))
                 grads = torch.autograd.grad(out, (x, w, b), d_out)
             finally:
                 _lib._lib = new
                 os.environ.pop('TGT_TRI_DROP_FAST', None)
+                os.environ.pop('TGT_TRI_DROP16', None)
             return (out,) + grads
         return run
 
@@ -139,7 +146,17 @@ def main():
     if parent is not None:
         checks.update({'new_p_off_equals_parent_p_bitwise': same('new_p_off', 'parent_p'), 'new_0_equals_parent_0_bitwise': same('new_0', 'parent_0'),
                        'new_p_vs_parent_p_rel': rel('new_p', 'parent_p')})
-    print(json.dumps({'B': B, 'N': N, 'C': CW, 'H': H, 'dtype': a.dtype, 'p': a.p, 'iters': a.iters, 'rounds': a.rounds,
+    fam = {}
+    for k, on in (('new_p', '1'), ('new_p_off', '0')):         # which kernel family the attention core of the two dropout arms is
+        os.environ['TGT_TRI_DROP_FAST'] = os.environ['TGT_TRI_DROP16'] = on
+        fused = torch.empty(1, N, N, L.width, dtype=dt, device='cuda')
+        out1 = torch.empty(1, N, N, 2 * CW, dtype=dt, device='cuda')
+        cs = ops._colsum_workspace(1, L.width, L.used, fused.device)
+        fam[k] = [new.tgt_triplet_attention_family(C.byref(ops._tri_args(fused, mask3[:1], out1, L, dropout=(a.p, SEED))), 0),
+                  new.tgt_triplet_attention_family(C.byref(ops._tri_args(fused, mask3[:1], out1, L, out1, fused, cs, dropout=(a.p, SEED))), 1)]
+        os.environ.pop('TGT_TRI_DROP_FAST', None)
+        os.environ.pop('TGT_TRI_DROP16', None)
+    print(json.dumps({'B': B, 'N': N, 'family_fwd_bwd': fam, 'C': CW, 'H': H, 'dtype': a.dtype, 'p': a.p, 'iters': a.iters, 'rounds': a.rounds,
                       'mean_nodes': round(float(n_nodes.double().mean()), 2), 'fwd_bwd_ms': {k: stats(v) for k, v in times.items()},
                       'rounds_ms': {k: [round(t, 4) for t in v] for k, v in times.items()}, 'kernel_ms': kernels, 'checks': checks}))
     bad = [k for k, v in checks.items() if k.endswith('bitwise') and not v]
