@@ -272,8 +272,8 @@ def test_gelu_dropout_sample_scale(dtype):
     sc = torch.tensor([0.0, 1.25, 1.25], device='cuda')
     for p in (0.0, 0.2):
         xa, xb = x0.clone().requires_grad_(True), x0.clone().requires_grad_(True)
-        ya = ops._GeluDropout.apply(xa, p, 1234, sc)
-        yb = ops._GeluDropout.apply(xb, p, 1234, None)
+        ya = ops._ActDropout.apply(xa, ops._ACT_FAMILIES['gelu'], None, p, 1234, sc)
+        yb = ops._ActDropout.apply(xb, ops._ACT_FAMILIES['gelu'], None, p, 1234, None)
         ya.backward(dy)
         yb.backward(dy)
         ref, gref = yb.float() * sc.view(-1, 1, 1), xb.grad.float() * sc.view(-1, 1, 1)

@@ -101,6 +101,15 @@ def _launch(entry, *args, prof=None):
     _PROFILE.setdefault(prof, []).append((s, e))
 
 
+def _launch_per_graph(entry, suffix, a, vec, *rest):
+    """`entry`(a, *rest) on argument block a -- or, with a per-graph vector (node counts, DropPath factors: _check_per_graph), the
+    form of that entry that reads it: entry + suffix ('_counts' / '_skip') (a, vec, *rest).  Both report as the plain kernel."""
+    if vec is None:
+        _launch(entry, C.byref(a), *rest, prof=entry)
+    else:
+        _launch(entry + suffix, C.byref(a), _ptr(vec), *rest, prof=entry)
+
+
 def _dev(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
@@ -189,21 +198,11 @@ class _TriSkip(collections.namedtuple('_TriSkip', 'node_counts counts_kb graph_s
         when there are node counts"""
         if self.counts_kb:
             a.flags |= _lib.TRI_COUNTS_KB
-        name = 'tgt_triplet_attention_bwd' if bwd else 'tgt_triplet_attention_fwd'
-        if self.node_counts is None:
-            _launch(name, C.byref(a), prof=name)
-        else:
-            _launch('tgt_triplet_attention_bwd_counts' if bwd else 'tgt_triplet_attention_fwd_counts', C.byref(a), _ptr(self.node_counts),
-                    prof=name)
+        _launch_per_graph('tgt_triplet_attention_bwd' if bwd else 'tgt_triplet_attention_fwd', '_counts', a, self.node_counts)
 
     def launch_aggregate(self, a, bwd=False):
         """tgt_triplet_aggregate_fwd / _bwd on argument block a, through the _skip entry when there are DropPath factors"""
-        name = 'tgt_triplet_aggregate_bwd' if bwd else 'tgt_triplet_aggregate_fwd'
-        if self.graph_scale is None:
-            _launch(name, C.byref(a), prof=name)
-        else:
-            _launch('tgt_triplet_aggregate_bwd_skip' if bwd else 'tgt_triplet_aggregate_fwd_skip', C.byref(a), _ptr(self.graph_scale),
-                    prof=name)
+        _launch_per_graph('tgt_triplet_aggregate_bwd' if bwd else 'tgt_triplet_aggregate_fwd', '_skip', a, self.graph_scale)
 
 
 def mask_node_counts(mask3):
@@ -667,21 +666,27 @@ def _split_projection_ok(x, L):
 _slow_path_said = set()
 
 
-def _slow_path_notice(key, msg):
+def _slow_path_notice(key, msg, stacklevel=3):
     """Say ONCE per process (and reason) that a BASELINE-sized call takes a kernel family that is 2-3x off the hot one, instead of
     doing so silently.  Small problems (tests) never reach the callers' size thresholds."""
     if key not in _slow_path_said:
         _slow_path_said.add(key)
         import warnings
-        warnings.warn('tgt_amd: ' + msg, RuntimeWarning, stacklevel=3)
+        warnings.warn('tgt_amd: ' + msg, RuntimeWarning, stacklevel=stacklevel)
 
 
 def _proj_fused_ok(x, N, L, cd):
     """the projection-fused forward kernel (tgt_triplet_attention_proj_fwd, wave roles: DESIGN.md section 4, profiles/HISTORY_rounds_1-4.md 4.1a): Q/K/V are
     projected inside the attention kernel (still written once, for the backward -- not at all when no backward follows:
     TGT_TRI_PROJ_INFER); TGT_TRI_PROJ=0 is the A/B knob"""
-    return (_TRI_PROJ and N <= 32 and L.D == 16 and L.H % 8 == 0 and L.width == L.used and
-            cd in (torch.bfloat16, torch.float16) and L.C == 256 and x.numel() // L.C >= _SPLIT_MIN_ROWS)
+    return _TRI_PROJ and N <= 32 and L.H % 8 == 0 and _proj_rows_ok(x, L, cd)
+
+
+def _proj_rows_ok(x, L, cd):
+    """what every projection-fused kernel (attention and aggregate, either node range) asks besides its node range and head count:
+    edge width 256 with 16-wide heads, an unpadded fused row, a 16-bit compute dtype and enough edge rows"""
+    return (L.C == 256 and L.D == 16 and L.width == L.used and cd in (torch.bfloat16, torch.float16) and
+            x.numel() // L.C >= _SPLIT_MIN_ROWS)
 
 
 def _proj64_fused_ok(x, N, L, cd):
@@ -689,8 +694,84 @@ def _proj64_fused_ok(x, N, L, cd):
     shape limits (tgt_triplet_attention_proj64_supported, less the flag and the dropout the caller decides), an unpadded fused row
     and enough edge rows (the gate of _proj_fused_ok).  It exists without the Q/K/V store only: a call a backward follows never
     gets here"""
-    return (33 <= N <= 64 and L.D == 16 and L.H == 16 and L.width == L.used and
-            cd in (torch.bfloat16, torch.float16) and L.C == 256 and x.numel() // L.C >= _SPLIT_MIN_ROWS)
+    return 33 <= N <= 64 and L.H == 16 and _proj_rows_ok(x, L, cd)
+
+
+class _TriRoute(collections.namedtuple('_TriRoute', 'kind entry stores_qkv why')):
+    """How ONE _ProjectedTripletAttention.forward runs (_tri_forward_route).  kind: 'proj' / 'proj64' / 'proj64_train' -- the
+    projection-fused kernel `entry` (its node-count form is entry + '_counts'), which writes the Q/K/V rows for a backward
+    (stores_qkv) or not at all (no backward follows: nothing is saved) -- or 'split' / 'gemm': library GEMMs, two or one, write
+    them and `entry` is the plain attention kernel.  why: None, or the word of the notice a BASELINE-sized call gets for falling
+    off the fused forward (_tri_route_notice)."""
+    __slots__ = ()
+
+    @property
+    def projection_fused(self):
+        return self.kind in ('proj', 'proj64', 'proj64_train')
+
+
+# (built once: the route is decided ~50 times a step, and all but the notice's are among these)
+_ROUTE_PROJ = _TriRoute('proj', 'tgt_triplet_attention_proj_fwd', True, None)
+_ROUTE_PROJ_INFER = _ROUTE_PROJ._replace(stores_qkv=False)          # (TRI_NO_QKV_STORE: 2/3 of the kernel's bytes)
+_ROUTE_PROJ64 = _TriRoute('proj64', 'tgt_triplet_attention_proj64_fwd', False, None)
+_ROUTE_PROJ64_TRAIN = _TriRoute('proj64_train', 'tgt_triplet_attention_proj64_train_fwd', True, None)
+_ROUTE_SPLIT = _TriRoute('split', 'tgt_triplet_attention_fwd', False, None)
+_ROUTE_GEMM = _TriRoute('gemm', 'tgt_triplet_attention_fwd', False, None)
+
+
+def _tri_forward_route(x, N, L, cd, p, no_backward):
+    """the _TriRoute of projected_triplet_attention on edge rows x (only x.numel() is read), N nodes, layout L, compute dtype cd,
+    attention dropout p; no_backward: _no_backward().  Pure: the knobs are read here, per call.
+    N <= 32: Q/K/V are projected inside the attention kernel, written once for the backward -- or, when none follows, neither
+    allocated nor written (TGT_TRI_PROJ_INFER=0 is the A/B knob).  33..64 nodes: the same without a backward
+    (tgt_triplet_attention_proj64_fwd, TGT_TRI_PROJ64_INFER=0 is the A/B knob) and, opt-in, with one (TGT_TRI_PROJ64_TRAIN=1,
+    DESIGN.md 4.w-64t: Q/K/V written once, nothing read back).  Neither takes attention dropout; TGT_TRI_PROJ=0 turns all of
+    them off.  Everything else is library GEMMs + the plain kernels: two GEMMs where _split_projection_ok, else one."""
+    if p == 0 and _proj_fused_ok(x, N, L, cd):
+        return _ROUTE_PROJ_INFER if (_TRI_PROJ_INFER and no_backward) else _ROUTE_PROJ
+    if p == 0 and _TRI_PROJ and _proj64_fused_ok(x, N, L, cd):
+        if no_backward and _TRI_PROJ64_INFER:
+            return _ROUTE_PROJ64
+        if not no_backward and _TRI_PROJ64_TRAIN:
+            return _ROUTE_PROJ64_TRAIN
+    route = _ROUTE_SPLIT if _split_projection_ok(x, L) else _ROUTE_GEMM
+    if _TRI_PROJ and x.numel() // L.C >= _SPLIT_MIN_ROWS:             # BASELINE-sized and off the fused forward: say why
+        route = route._replace(why=(
+            'N > 64' if N > 64 else 'N > 32' if N > 32 else 'attention dropout > 0' if p else 'head dim != 16' if L.D != 16 else
+            'heads not a multiple of 8' if L.H % 8 else 'edge width != 256' if L.C != 256 else
+            'fp32' if cd not in (torch.bfloat16, torch.float16) else 'padded / unbiased layout'))
+    return route
+
+
+def _tri_route_notice(route, N, p):
+    """the slow-path notice of a route that has a `why` (once per process and reason)"""
+    why = route.why
+    if why is None:
+        return
+    key = ('tri_proj', why)
+    if N > 64:
+        msg = ('triplet attention: the projection-fused forward / round-4 backward do not take this shape (N > 64); '
+               'running the projection as library GEMMs + the key-blocked attention kernels (65 <= N <= 128, D = 16: online softmax '
+               'forward, two-sweep backward, bias gradient by a separate column-sum pass; see DESIGN.md section 4)')
+    elif why == 'N > 32' and p:
+        # (33..64 nodes with attention dropout: the library routes the attention core by TGT_TRI_DROP16, per call)
+        on = _knobs.library_flag_now('tri_drop16')
+        core = ('the 16-wide-tile kernels tri_att16_fwd_kernel / tri_att16_bwd_kernel, dropout included (TGT_TRI_DROP16=1; each direction '
+                'where its head count qualifies, the general kernel otherwise)' if on else
+                'the general 32-wide kernels tri_att_fwd_kernel / tri_att_bwd_kernel (the 16-wide tiles take attention dropout under '
+                'TGT_TRI_DROP16=1 only)')
+        key = ('tri_proj', why, 'dropout', on)
+        msg = ('triplet attention: the projection-fused forwards do not take attention dropout > 0 '
+               f'(N > 32); running the projection as library GEMMs + {core}; see DESIGN.md 4.zj')
+    elif why == 'attention dropout > 0' and _TRI_DROP_FAST:
+        # (the backward of this call stays on the round-4 kernel, which has the dropout: tgt_triplet_attention_family)
+        msg = ('triplet attention: the projection-fused forward does not take attention dropout > 0; running the '
+               'projection as library GEMMs + the general forward kernel (the backward stays on the round-4 kernel: DESIGN.md 4.zi)')
+    else:
+        msg = (f'triplet attention: the projection-fused forward / round-4 backward do not take this shape ({why}); '
+               'running the projection as library GEMMs + the general attention kernels (N in 33..64: 16-wide tiles at 0.39-0.45 of '
+               'HBM instead of 0.52; see DESIGN.md section 4)')
+    _slow_path_notice(key, msg, stacklevel=4)          # (the warning points where it did when forward itself raised it)
 
 
 # A/B knob (round 5, VERDICT r4 item 3): keep the node side stream's backward chain of a layer off the HBM-bound triplet backward
@@ -734,88 +815,22 @@ class _ProjectedTripletAttention(torch.autograd.Function):
         weight, bias = wb if table is None else _fuse_params(table, wb, cd)
         out = torch.empty(B, N, N, 2 * L.C, dtype=cd, device=x.device)
         eg = None
-        projection_fused = False
-        # 33..64 nodes, no backward: Q/K/V projected inside tgt_triplet_attention_proj64_fwd and never written (TGT_TRI_PROJ64_INFER=0
-        # is the A/B knob: the library GEMMs + tri_att16_fwd_kernel below)
-        infer64 = bool(no_backward and dropout[0] == 0 and _TRI_PROJ and _TRI_PROJ64_INFER and _proj64_fused_ok(x, N, L, cd))
-        # 33..64 nodes, a backward can follow: the same kernel's storing form (tgt_triplet_attention_proj64_train_fwd, DESIGN.md
-        # 4.w-64t) writes Q/K/V once, for the backward, and reads nothing back.  Opt-in (TGT_TRI_PROJ64_TRAIN=1)
-        train64 = bool(not no_backward and dropout[0] == 0 and _TRI_PROJ and _TRI_PROJ64_TRAIN and _proj64_fused_ok(x, N, L, cd))
-        if (x.numel() // L.C >= _SPLIT_MIN_ROWS and not (dropout[0] == 0 and _proj_fused_ok(x, N, L, cd)) and _TRI_PROJ and not infer64 and
-                not train64):
-            why = ('N > 64' if N > 64 else 'N > 32' if N > 32 else 'attention dropout > 0' if dropout[0] else 'head dim != 16' if L.D != 16 else
-                   'heads not a multiple of 8' if L.H % 8 else 'edge width != 256' if L.C != 256 else
-                   'fp32' if cd not in (torch.bfloat16, torch.float16) else 'padded / unbiased layout')
-            if N > 64:
-                _slow_path_notice(('tri_proj', why), 'triplet attention: the projection-fused forward / round-4 backward do not take this shape (N > 64); '
-                                  'running the projection as library GEMMs + the key-blocked attention kernels (65 <= N <= 128, D = 16: online softmax '
-                                  'forward, two-sweep backward, bias gradient by a separate column-sum pass; see DESIGN.md section 4)')
-            elif why == 'N > 32' and dropout[0]:
-                # (33..64 nodes with attention dropout: the library routes the attention core by TGT_TRI_DROP16, per call)
-                on = _knobs.library_flag_now('tri_drop16')
-                core = ('the 16-wide-tile kernels tri_att16_fwd_kernel / tri_att16_bwd_kernel, dropout included (TGT_TRI_DROP16=1; each direction '
-                        'where its head count qualifies, the general kernel otherwise)' if on else
-                        'the general 32-wide kernels tri_att_fwd_kernel / tri_att_bwd_kernel (the 16-wide tiles take attention dropout under '
-                        'TGT_TRI_DROP16=1 only)')
-                _slow_path_notice(('tri_proj', why, 'dropout', on), 'triplet attention: the projection-fused forwards do not take attention dropout > 0 '
-                                  f'(N > 32); running the projection as library GEMMs + {core}; see DESIGN.md 4.zj')
-            elif why == 'attention dropout > 0' and _TRI_DROP_FAST:
-                # (the backward of this call stays on the round-4 kernel, which has the dropout: tgt_triplet_attention_family)
-                _slow_path_notice(('tri_proj', why), 'triplet attention: the projection-fused forward does not take attention dropout > 0; running the '
-                                  'projection as library GEMMs + the general forward kernel (the backward stays on the round-4 kernel: DESIGN.md 4.zi)')
-            else:
-                _slow_path_notice(('tri_proj', why), f'triplet attention: the projection-fused forward / round-4 backward do not take this shape ({why}); '
-                                  'running the projection as library GEMMs + the general attention kernels (N in 33..64: 16-wide tiles at 0.39-0.45 of '
-                                  'HBM instead of 0.52; see DESIGN.md section 4)')
-        if dropout[0] == 0 and _proj_fused_ok(x, N, L, cd):
-            # Q/K/V projected inside the attention kernel (it still writes them once, for the
-            # backward); only the narrow E/G third-arm projection stays a library GEMM, written
-            # straight into its columns of the fused row
+        route = _tri_forward_route(x, N, L, cd, dropout[0], no_backward)
+        _tri_route_notice(route, N, dropout[0])
+        if route.projection_fused:
+            # Q/K/V projected inside the attention kernel; only the narrow E/G third-arm projection stays a library GEMM.  The
+            # Q/K/V rows (written by the kernel, for the backward) and that projection are two tensors, as in the split-GEMM
+            # branch below; a route that does not store them allocates none (TRI_NO_QKV_STORE)
             x2, w, b = _linear_operands(x, weight, bias, cd, x_contiguous=True, wb_contiguous=True)
-            # the Q/K/V rows (written by the kernel, for the backward) and the narrow third-arm E/G projection as two tensors,
-            # as in the split-GEMM path below.  no_backward (torch.no_grad(), or no input requires grad): nothing will read
-            # those rows, so they are neither allocated nor written (TRI_NO_QKV_STORE: 2/3 of the kernel's bytes);
-            # TGT_TRI_PROJ_INFER=0 is the A/B knob
-            infer = _TRI_PROJ_INFER and no_backward
-            fused = None if infer else torch.empty(B, N, N, 6 * L.C, dtype=cd, device=x.device)
+            fused = torch.empty(B, N, N, 6 * L.C, dtype=cd, device=x.device) if route.stores_qkv else None
             if L.biased:                       # (axial: no third arm)
                 eg = _narrow_linear(x2, w[6 * L.C:L.used], b[6 * L.C:L.used], cd).view(B, N, N, L.used - 6 * L.C)
             a = _tri_args(fused, mask3, out, L, eg=eg, graph_scale=graph_scale)
-            if node_counts is None:
-                _launch('tgt_triplet_attention_proj_fwd', C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), prof='tgt_triplet_attention_proj_fwd')
-            else:              # (padded units: no Q/K/V rows either -- the backward below gets the same counts)
-                _launch('tgt_triplet_attention_proj_fwd_counts', C.byref(a), _ptr(node_counts), _ptr(x2), L.C, _ptr(w), _ptr(b),
-                        prof='tgt_triplet_attention_proj_fwd')
-            if infer:
+            # (node counts: padded units get no Q/K/V rows either -- the backward below gets the same counts)
+            _launch_per_graph(route.entry, '_counts', a, node_counts, _ptr(x2), L.C, _ptr(w), _ptr(b))
+            if fused is None:
                 return out                 # (nothing to save: no backward exists)
-            projection_fused = True        # (dropped graphs have NO Q/K/V rows: the backward must skip them too)
-        elif infer64:
-            x2, w, b = _linear_operands(x, weight, bias, cd, x_contiguous=True, wb_contiguous=True)
-            if L.biased:                       # (axial: no third arm)
-                eg = _narrow_linear(x2, w[6 * L.C:L.used], b[6 * L.C:L.used], cd).view(B, N, N, L.used - 6 * L.C)
-            a = _tri_args(None, mask3, out, L, eg=eg, graph_scale=graph_scale)
-            if node_counts is None:
-                _launch('tgt_triplet_attention_proj64_fwd', C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), prof='tgt_triplet_attention_proj64_fwd')
-            else:
-                _launch('tgt_triplet_attention_proj64_fwd_counts', C.byref(a), _ptr(node_counts), _ptr(x2), L.C, _ptr(w), _ptr(b),
-                        prof='tgt_triplet_attention_proj64_fwd')
-            return out                     # (nothing to save: no backward exists)
-        elif train64:
-            # what the N <= 32 branch above does and saves, with the kernel for 33..64 nodes: the Q/K/V rows (written by the
-            # kernel) and the narrow E/G projection as two tensors, as in the split-GEMM branch below
-            x2, w, b = _linear_operands(x, weight, bias, cd, x_contiguous=True, wb_contiguous=True)
-            fused = torch.empty(B, N, N, 6 * L.C, dtype=cd, device=x.device)
-            if L.biased:                       # (axial: no third arm)
-                eg = _narrow_linear(x2, w[6 * L.C:L.used], b[6 * L.C:L.used], cd).view(B, N, N, L.used - 6 * L.C)
-            a = _tri_args(fused, mask3, out, L, eg=eg, graph_scale=graph_scale)
-            if node_counts is None:
-                _launch('tgt_triplet_attention_proj64_train_fwd', C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b),
-                        prof='tgt_triplet_attention_proj64_train_fwd')
-            else:              # (padded units: no Q/K/V rows either -- the backward below gets the same counts)
-                _launch('tgt_triplet_attention_proj64_train_fwd_counts', C.byref(a), _ptr(node_counts), _ptr(x2), L.C, _ptr(w), _ptr(b),
-                        prof='tgt_triplet_attention_proj64_train_fwd')
-            projection_fused = True        # (dropped graphs have NO Q/K/V rows: the backward must skip them too)
-        elif _split_projection_ok(x, L):
+        elif route.kind == 'split':
             # two GEMMs: Q/K/V (6C = 1536 channels: six full 256-wide tile columns, 294 us) and the
             # narrow E/G (39 us) instead of one ragged 1600-wide GEMM (376 us; tools/gemm_probe.py);
             # the backward still writes ONE fused gradient row (ld_dqkv / ld_deg)
@@ -828,7 +843,7 @@ class _ProjectedTripletAttention(torch.autograd.Function):
             skip.launch_attention(_tri_args(fused, mask3, out, L, dropout=dropout, graph_scale=graph_scale))
         ctx.save_for_backward(x2, w, fused, mask3, out, eg if eg is not None else fused.new_empty(0),
                               *(wb if table is not None else ()))
-        ctx.L, ctx.table, ctx.dropout, ctx.skip = L, table, dropout, skip.for_backward(projection_fused)
+        ctx.L, ctx.table, ctx.dropout, ctx.skip = L, table, dropout, skip.for_backward(route.projection_fused)
         ctx.lin = _LinearSaved.of(x, weight, bias, edge=False)
         return out
 
@@ -987,15 +1002,13 @@ def triplet_aggregate(fused, mask3, layout, dropout=(0.0, 0), graph_scale=None):
 def _agg_proj_ok(x, N, L, cd):
     """the projection-fused aggregate forward (tgt_triplet_aggregate_proj_fwd): the kernel's shape limits, an
     unpadded fused row and enough edge rows for a grid of B x 2 workgroups (the gate of _proj_fused_ok)"""
-    return (x.is_cuda and N <= 32 and L.C == 256 and L.D == 16 and L.H == 16 and L.width == L.used and
-            cd in (torch.bfloat16, torch.float16) and x.numel() // L.C >= _SPLIT_MIN_ROWS)
+    return x.is_cuda and N <= 32 and L.H == 16 and _proj_rows_ok(x, L, cd)
 
 
 def _agg_proj64_ok(x, N, L, cd):
     """the same for 33 <= N <= 64 (tgt_triplet_aggregate_proj64_fwd): that kernel's shape limits, an unpadded
     fused row and the row gate of _agg_proj_ok"""
-    return (x.is_cuda and 33 <= N <= 64 and L.C == 256 and L.D == 16 and L.H == 16 and L.width == L.used and
-            cd in (torch.bfloat16, torch.float16) and x.numel() // L.C >= _SPLIT_MIN_ROWS)
+    return x.is_cuda and 33 <= N <= 64 and L.H == 16 and _proj_rows_ok(x, L, cd)
 
 
 def _agg_proj_eg_view(out, L):
@@ -1051,10 +1064,7 @@ def projected_triplet_aggregate(x, params, mask3, layout, table, dropout=(0.0, 0
         egv, _ = _agg_proj_eg_view(out, L)                   # (the E/G rows wait inside `out` for the kernel: no tensor of their own)
         _narrow_linear(x2, w[2 * L.C:L.used], b[2 * L.C:L.used], cd, out=egv)
         a = _agg_proj_args(out, mask3, out, L, dropout)
-        if graph_scale is None:
-            _launch(entry, C.byref(a), _ptr(x2), L.C, _ptr(w), _ptr(b), prof=entry)
-        else:
-            _launch(entry + '_skip', C.byref(a), _ptr(graph_scale), _ptr(x2), L.C, _ptr(w), _ptr(b), prof=entry)
+        _launch_per_graph(entry, '_skip', a, graph_scale, _ptr(x2), L.C, _ptr(w), _ptr(b))
     return out
 
 
@@ -1470,27 +1480,98 @@ def drop_path_add_(x, residual, drop_prob, training):
     return x.add_(residual)
 
 
-class _GeluDropout(torch.autograd.Function):
+GLU_KINDS = _lib.GLU_KINDS        # 'geglu' / 'glu' / 'swiglu' -> TGT_GLU_*
+ACT_KINDS = _lib.ACT_KINDS        # 'relu' / 'silu' / 'elu' -> TGT_ACT_*
+
+
+class _ActFamily(collections.namedtuple('_ActFamily', 'name kinds noun half unit entry shape epilogue kind_shift')):
+    """One family of y = dropout(activation(pre), p) * sample_scale[b] kernels.  name: its public function is <name>_dropout and its
+    profile names are tgt_<name>_dropout_fwd / _bwd; kinds: the names its `kind` argument takes (None: it has none) and what the
+    error calls them (noun); half: pre = [gate | linear] and y has half its channels; unit: what sample_scale must cover a whole
+    number of per sample.  entry + '_fwd' (pre, y, *shape(pre, kind), p, seed, sample_scale, elements per sample) and entry + '_bwd'
+    (pre, dy, d_pre, the same) are the streaming kernels -- the three C signatures differ in `shape` alone.  epilogue / kind_shift:
+    the Linear-fused launch (tgt_edge_linear) and where its flags carry the kind."""
+    __slots__ = ()
+
+
+_ACT_FAMILIES = {
+    'gelu': _ActFamily('gelu', None, None, False, 'a multiple of 8 elements', 'tgt_gelu_dropout_scaled',
+                       lambda pre, kind: (pre.numel(), _DT[pre.dtype]), _lib.EPI_GELU, 0),
+    'glu': _ActFamily('glu', GLU_KINDS, 'gated activation', True, 'a whole number of rows', 'tgt_glu_dropout',
+                      lambda pre, kind: (pre.numel() // pre.shape[-1], pre.shape[-1] // 2, kind, _DT[pre.dtype]),
+                      _lib.EPI_GLU, _lib.EDGE_GLU_KIND_SHIFT),
+    'act': _ActFamily('act', ACT_KINDS, 'activation', False, 'a multiple of 8 elements', 'tgt_act_dropout',
+                      lambda pre, kind: (pre.numel(), kind, _DT[pre.dtype]), _lib.EPI_ACT, _lib.EDGE_ACT_KIND_SHIFT),
+}
+
+
+def _act_kind(fam, kind):
+    """the TGT_GLU_* / TGT_ACT_* constant of a family's activation, given by name or as that constant"""
+    if isinstance(kind, str):
+        if kind not in fam.kinds:
+            raise RuntimeError(f'{fam.name}_dropout: unknown {fam.noun} {kind!r} (one of {sorted(fam.kinds)})')
+        return fam.kinds[kind]
+    return int(kind)
+
+
+def _act_check(fam, x, sample_scale):
+    """the streaming entries' terms on x and sample_scale: a float32 factor per sample over a whole number of fam.unit each"""
+    what = fam.name + '_dropout'
+    if fam.kinds is None:              # (gelu_dropout takes the factor per x.shape[0] and checks no more than this)
+        if sample_scale is not None and (x.numel() // x.shape[0]) % 8:
+            raise RuntimeError(f'{what}: sample_scale needs {fam.unit} per sample')
+        return
+    if x.dtype not in _DT:
+        raise RuntimeError(f'{what}: no kernel for dtype {x.dtype} (float32 / bfloat16 / float16)')
+    if fam.half and x.shape[-1] % 2:
+        raise RuntimeError(f'{what}: the last axis holds [gate | linear] halves, got {x.shape[-1]} channels')
+    if sample_scale is not None:
+        out, unit = (x.numel() // 2, x.shape[-1] // 2) if fam.half else (x.numel(), 8)
+        if sample_scale.dtype != torch.float32 or out % sample_scale.numel() or (out // sample_scale.numel()) % unit:
+            raise RuntimeError(f'{what}: sample_scale must be float32 with {fam.unit} per sample')
+
+
+def _act_backward(fam, pre, d_act, kind, p, seed, sample_scale, eps_):
+    """d_pre of y = dropout(activation(pre), p) * sample_scale ([d_g | d_e] for pre = [g | e]): one streaming pass, the drop
+    pattern recomputed"""
+    d_act = d_act.contiguous()
+    if d_act.dtype != pre.dtype:
+        d_act = d_act.to(pre.dtype)
+    d_pre = torch.empty_like(pre)
+    _launch(fam.entry + '_bwd', _ptr(pre), _ptr(d_act), _ptr(d_pre), *fam.shape(pre, kind), p, seed, _ptr(sample_scale), eps_,
+            prof=f'tgt_{fam.name}_dropout_bwd')
+    return d_pre
+
+
+class _ActDropout(torch.autograd.Function):
+    """y = dropout(activation(x), p) * sample_scale[b] of family fam in one pass each way; only x is kept"""
+
     @staticmethod
-    def forward(ctx, x, p, seed, sample_scale):
+    def forward(ctx, x, fam, kind, p, seed, sample_scale):
         _dev(x, sample_scale)
         x = x.contiguous()
-        y = torch.empty_like(x)
-        eps_ = x.numel() // x.shape[0] if sample_scale is not None else 0
-        _launch('tgt_gelu_dropout_scaled_fwd', _ptr(x), _ptr(y), x.numel(), _DT[x.dtype], float(p), seed, _ptr(sample_scale), eps_,
-                prof='tgt_gelu_dropout_fwd')
+        y = torch.empty(*x.shape[:-1], x.shape[-1] // 2, dtype=x.dtype, device=x.device) if fam.half else torch.empty_like(x)
+        eps_ = 0 if sample_scale is None else y.numel() // (x.shape[0] if fam.kinds is None else sample_scale.numel())
+        _launch(fam.entry + '_fwd', _ptr(x), _ptr(y), *fam.shape(x, kind), float(p), seed, _ptr(sample_scale), eps_,
+                prof=f'tgt_{fam.name}_dropout_fwd')
         ctx.save_for_backward(x, sample_scale)
-        ctx.p, ctx.seed, ctx.eps_ = float(p), seed, eps_
+        ctx.meta = (fam, kind, float(p), seed, eps_)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, sample_scale = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        _launch('tgt_gelu_dropout_scaled_bwd', _ptr(x), _ptr(dy), _ptr(dx), x.numel(), _DT[x.dtype], ctx.p, ctx.seed, _ptr(sample_scale),
-                ctx.eps_, prof='tgt_gelu_dropout_bwd')
-        return dx, None, None, None
+        fam, kind, p, seed, eps_ = ctx.meta
+        return _act_backward(fam, x, dy, kind, p, seed, sample_scale, eps_), None, None, None, None, None
+
+
+def _act_dropout(fam, x, kind, p, training, sample_scale):
+    if fam.kinds is not None:
+        kind = _act_kind(fam, kind)
+    p, seed = draw_dropout(p, training)
+    _dev(x, sample_scale)
+    _act_check(fam, x, sample_scale)
+    return _ActDropout.apply(x, fam, kind, p, seed, sample_scale)
 
 
 def gelu_dropout(x, p, training, sample_scale=None):
@@ -1498,64 +1579,7 @@ def gelu_dropout(x, p, training, sample_scale=None):
     The drop pattern comes from a per-call seed drawn from torch's CPU generator (no device sync).
     sample_scale (B,) float32: the result is multiplied by sample_scale[b] -- the DropPath factor of the residual
     branch, folded in here (see linear_residual_layer_norm(prescaled=True))."""
-    p, seed = draw_dropout(p, training)
-    if sample_scale is not None and (x.numel() // x.shape[0]) % 8:
-        raise RuntimeError('gelu_dropout: sample_scale needs a multiple of 8 elements per sample')
-    return _GeluDropout.apply(x, p, seed, sample_scale)
-
-
-GLU_KINDS = _lib.GLU_KINDS        # 'geglu' / 'glu' / 'swiglu' -> TGT_GLU_*
-
-
-def _glu_kind(kind):
-    if isinstance(kind, str):
-        if kind not in GLU_KINDS:
-            raise RuntimeError(f'glu_dropout: unknown gated activation {kind!r} (one of {sorted(GLU_KINDS)})')
-        return GLU_KINDS[kind]
-    return int(kind)
-
-
-def _glu_backward(pre, d_act, kind, p, seed, sample_scale, eps_):
-    """[d_g | d_e] of y = dropout(e * act(g), p) * sample_scale for pre = [g | e]: one streaming pass, the drop pattern recomputed"""
-    cols = pre.shape[-1] // 2
-    d_act = d_act.contiguous()
-    if d_act.dtype != pre.dtype:
-        d_act = d_act.to(pre.dtype)
-    d_pre = torch.empty_like(pre)
-    _launch('tgt_glu_dropout_bwd', _ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel() // (2 * cols), cols, kind, _DT[pre.dtype], p, seed,
-            _ptr(sample_scale), eps_, prof='tgt_glu_dropout_bwd')
-    return d_pre
-
-
-class _GluDropout(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, kind, p, seed, sample_scale):
-        _dev(x, sample_scale)
-        x = x.contiguous()
-        cols = x.shape[-1] // 2
-        y = torch.empty(*x.shape[:-1], cols, dtype=x.dtype, device=x.device)
-        eps_ = y.numel() // sample_scale.numel() if sample_scale is not None else 0
-        _launch('tgt_glu_dropout_fwd', _ptr(x), _ptr(y), y.numel() // cols, cols, kind, _DT[x.dtype], float(p), seed, _ptr(sample_scale),
-                eps_, prof='tgt_glu_dropout_fwd')
-        ctx.save_for_backward(x, sample_scale)
-        ctx.meta = (kind, float(p), seed, eps_)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, sample_scale = ctx.saved_tensors
-        return _glu_backward(x, dy, *ctx.meta[:3], sample_scale, ctx.meta[3]), None, None, None, None
-
-
-def _glu_check(x_last, out_elems, dtype, sample_scale, what):
-    if dtype not in _DT:
-        raise RuntimeError(f'{what}: no kernel for dtype {dtype} (float32 / bfloat16 / float16)')
-    if x_last % 2:
-        raise RuntimeError(f'{what}: the last axis holds [gate | linear] halves, got {x_last} channels')
-    if sample_scale is not None:
-        cols = x_last // 2
-        if sample_scale.dtype != torch.float32 or out_elems % sample_scale.numel() or (out_elems // sample_scale.numel()) % cols:
-            raise RuntimeError(f'{what}: sample_scale must be float32 with a whole number of rows per sample')
+    return _act_dropout(_ACT_FAMILIES['gelu'], x, None, p, training, sample_scale)
 
 
 def glu_dropout(x, kind, p, training, sample_scale=None):
@@ -1563,60 +1587,7 @@ def glu_dropout(x, kind, p, training, sample_scale=None):
     (sigmoid) or 'swiglu' (g * sigmoid(g)) -- reference lib/tgt/layers/activations.py:4-17 and the nn.Dropout of
     lib/tgt/layers/layers.py:158.  Only x is kept for the backward; the drop pattern comes from a per-call seed (no mask tensor).
     sample_scale (B,) float32: the result is multiplied by sample_scale[b] (the branch's DropPath factor, see gelu_dropout)."""
-    kind = _glu_kind(kind)
-    p, seed = draw_dropout(p, training)
-    _dev(x, sample_scale)
-    _glu_check(x.shape[-1], x.numel() // 2, x.dtype, sample_scale, 'glu_dropout')
-    return _GluDropout.apply(x, kind, p, seed, sample_scale)
-
-
-ACT_KINDS = _lib.ACT_KINDS        # 'relu' / 'silu' / 'elu' -> TGT_ACT_*
-
-
-def _act_kind(kind):
-    if isinstance(kind, str):
-        if kind not in ACT_KINDS:
-            raise RuntimeError(f'act_dropout: unknown activation {kind!r} (one of {sorted(ACT_KINDS)})')
-        return ACT_KINDS[kind]
-    return int(kind)
-
-
-def _act_backward(pre, d_act, kind, p, seed, sample_scale, eps_):
-    """d_pre of y = dropout(act(pre), p) * sample_scale: one streaming pass, the drop pattern recomputed"""
-    d_act = d_act.contiguous()
-    if d_act.dtype != pre.dtype:
-        d_act = d_act.to(pre.dtype)
-    d_pre = torch.empty_like(pre)
-    _launch('tgt_act_dropout_bwd', _ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel(), kind, _DT[pre.dtype], p, seed, _ptr(sample_scale),
-            eps_, prof='tgt_act_dropout_bwd')
-    return d_pre
-
-
-class _ActDropout(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, kind, p, seed, sample_scale):
-        _dev(x, sample_scale)
-        x = x.contiguous()
-        y = torch.empty_like(x)
-        eps_ = x.numel() // sample_scale.numel() if sample_scale is not None else 0
-        _launch('tgt_act_dropout_fwd', _ptr(x), _ptr(y), x.numel(), kind, _DT[x.dtype], float(p), seed, _ptr(sample_scale), eps_,
-                prof='tgt_act_dropout_fwd')
-        ctx.save_for_backward(x, sample_scale)
-        ctx.meta = (kind, float(p), seed, eps_)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, sample_scale = ctx.saved_tensors
-        return _act_backward(x, dy, *ctx.meta[:3], sample_scale, ctx.meta[3]), None, None, None, None
-
-
-def _act_check(numel, dtype, sample_scale, what):
-    if dtype not in _DT:
-        raise RuntimeError(f'{what}: no kernel for dtype {dtype} (float32 / bfloat16 / float16)')
-    if sample_scale is not None:
-        if sample_scale.dtype != torch.float32 or numel % sample_scale.numel() or (numel // sample_scale.numel()) % 8:
-            raise RuntimeError(f'{what}: sample_scale must be float32 with a multiple of 8 elements per sample')
+    return _act_dropout(_ACT_FAMILIES['glu'], x, kind, p, training, sample_scale)
 
 
 def act_dropout(x, kind, p, training, sample_scale=None):
@@ -1624,11 +1595,7 @@ def act_dropout(x, kind, p, training, sample_scale=None):
     lib/tgt/layers/activations.py:21-25 looks up in torch.nn.functional, followed by the nn.Dropout of lib/tgt/layers/layers.py:158.
     Only x is kept for the backward; the drop pattern comes from a per-call seed (no mask tensor).
     sample_scale (B,) float32: the result is multiplied by sample_scale[b] (the branch's DropPath factor, see gelu_dropout)."""
-    kind = _act_kind(kind)
-    p, seed = draw_dropout(p, training)
-    _dev(x, sample_scale)
-    _act_check(x.numel(), x.dtype, sample_scale, 'act_dropout')
-    return _ActDropout.apply(x, kind, p, seed, sample_scale)
+    return _act_dropout(_ACT_FAMILIES['act'], x, kind, p, training, sample_scale)
 
 
 class _MultiHotEmbed(torch.autograd.Function):
@@ -2456,69 +2423,81 @@ _FFN_GELU_EPI = K.ffn_gelu_epi     # A/B knob: lin_W1 + GELU + dropout as one la
 _FFN_GELU_BWD_EPI = K.ffn_gelu_bwd_epi
 
 
-def _linear_act_forward(ctx, x, weight, bias, cd, epilogue, act_cols, p, seed, sample_scale, lazy=False, flags=0):
-    """(act, pre) of the ONE launch behind _LinearGeluDropout / _LinearGluDropout: pre = x W^T + b and act = dropout(activation(pre),
-    p) * sample_scale[b] of act_cols channels; ctx gets (x2, w, pre, sample_scale), ctx.lin, and p / seed / elements per sample"""
-    _dev(x, weight, sample_scale)
-    x2, w, b = _linear_operands(x, weight, bias, cd)
-    N = weight.shape[0]
-    ctx.lin = _LinearSaved.of(x, weight, bias, lazy)
-    pre = torch.empty(*ctx.lin.xs[:-1], N, dtype=cd, device=x.device)
-    act = torch.empty(*ctx.lin.xs[:-1], act_cols, dtype=cd, device=x.device)
-    rps = (x2.shape[0] // sample_scale.numel()) if sample_scale is not None else 0
-    edge_linear_raw(x2, w, b, epilogue, out=act.view(-1, act_cols), out2=pre.view(-1, N), dropout=(p, seed),
-                    row_scale=sample_scale, rows_per_sample=rps, flags=flags, live=ctx.lin.live)
-    ctx.save_for_backward(x2, w, pre, sample_scale)
-    ctx.p, ctx.seed, ctx.eps_ = float(p), seed, rps * act_cols
-    return act, pre
+class _ActRecord(collections.namedtuple('_ActRecord', 'pre p seed sample_scale kind')):
+    """What rides on the activation out of linear_gelu_dropout / linear_act_dropout as `_tgt_gelu` (as _tgt_colsum does): what a
+    consumer needs to take over the activation's backward (linear_residual_layer_norm).  kind: TGT_ACT_* of relu / silu / elu, None
+    for gelu."""
+    __slots__ = ()
 
 
-class _LinearGeluDropout(torch.autograd.Function):
-    """act = dropout(gelu(x W^T + b), p) * sample_scale[b] as ONE launch (tgt_edge_linear, TGT_EPI_GELU on the row-phase
-    kernel): the pre-activation is written once for the backward and never re-read by a separate activation pass
-    (reference FFN, lib/tgt/layers/layers.py:155-158).  Same drop pattern and arithmetic as tgt_gelu_dropout_scaled_fwd on
-    the stored pre-activation; the backward is that kernel's backward followed by the Linear's."""
+class _LinearActDropout(torch.autograd.Function):
+    """act = dropout(activation(x W^T + b), p) * sample_scale[b] of family fam as ONE launch (tgt_edge_linear with the family's
+    epilogue -- TGT_EPI_GELU / TGT_EPI_ACT on the row-phase kernel, TGT_EPI_GLU on the 256 -> 512 weight-resident kernel with the
+    activation in its store phase; reference FFN, lib/tgt/layers/layers.py:155-158): the pre-activation is written once for the
+    backward and never re-read by a separate activation pass.  Same drop pattern and arithmetic as the family's streaming forward on
+    the stored pre-activation; the backward is that kernel's backward followed by the Linear's (bias gradient: the column sums of
+    d_pre)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, cd, p, seed, sample_scale, lazy=False):
+    def forward(ctx, x, weight, bias, cd, fam, kind, p, seed, sample_scale, lazy=False):
         ctx.set_materialize_grads(False)
         # TWO outputs: the activation, and the pre-activation as a differentiable value of its own -- a consumer that owns the
-        # activation's derivative (linear_residual_layer_norm: GELU backward as the epilogue of its data-gradient GEMM) reads
-        # the activation detached and sends its gradient to `pre` directly
-        return _linear_act_forward(ctx, x, weight, bias, cd, _lib.EPI_GELU, weight.shape[0], p, seed, sample_scale, lazy)
+        # activation's derivative (linear_residual_layer_norm: GELU_BWD / ACT_BWD as the epilogue of its data-gradient GEMM) reads
+        # the activation detached and sends its gradient to `pre` directly.  (A GLU has no such consumer: its caller drops `pre`.)
+        _dev(x, weight, sample_scale)
+        x2, w, b = _linear_operands(x, weight, bias, cd)
+        N = weight.shape[0]
+        act_cols = N // 2 if fam.half else N
+        ctx.lin = _LinearSaved.of(x, weight, bias, lazy)
+        pre = torch.empty(*ctx.lin.xs[:-1], N, dtype=cd, device=x.device)
+        act = torch.empty(*ctx.lin.xs[:-1], act_cols, dtype=cd, device=x.device)
+        rps = (x2.shape[0] // sample_scale.numel()) if sample_scale is not None else 0
+        edge_linear_raw(x2, w, b, fam.epilogue, out=act.view(-1, act_cols), out2=pre.view(-1, N), dropout=(p, seed),
+                        row_scale=sample_scale, rows_per_sample=rps, flags=(kind or 0) << fam.kind_shift, live=ctx.lin.live)
+        ctx.save_for_backward(x2, w, pre, sample_scale)
+        ctx.meta = (fam, kind, float(p), seed, rps * act_cols)
+        return act, pre
 
     @staticmethod
     def backward(ctx, d_act, d_pre_in):
         x2, w, pre, sample_scale = ctx.saved_tensors
-        p, seed, eps_ = ctx.p, ctx.seed, ctx.eps_
-        d_pre = None
-        need_db = ctx.lin.bdt is not None and ctx.needs_input_grad[_LINEAR_GELU_ARGS.index('bias')]
-        cs = handed = None
+        fam, kind, p, seed, eps_ = ctx.meta
+        d_pre = cs = handed = None
         if d_act is not None:
-            d_act = d_act.contiguous()
-            d_pre = torch.empty_like(pre)
             N = pre.shape[-1]
             vec = 16 // pre.element_size()
-            if _GELU_BWD_COLSUM and need_db and d_pre_in is None and N % vec == 0 and (256 * vec) % N == 0:
-                # the bias gradient of lin_W1 (column sums of d_pre) rides on the activation's backward pass: no separate
-                # reduction pass over the 134 MB gradient
+            if _GELU_BWD_COLSUM and fam.kinds is None and d_pre_in is None and N % vec == 0 and (256 * vec) % N == 0 and \
+                    ctx.lin.bdt is not None and ctx.needs_input_grad[_LINEAR_ACT_ARGS.index('bias')]:
+                # (gelu only) the bias gradient of lin_W1 (column sums of d_pre) rides on the activation's backward pass: no
+                # separate reduction pass over the 134 MB gradient
+                d_act = d_act.contiguous()
+                d_pre = torch.empty_like(pre)
                 cs = torch.empty(N, dtype=torch.float32, device=pre.device)
                 partial = torch.empty(_lib.lib().tgt_gelu_colsum_parts() * N, dtype=torch.float32, device=pre.device)
                 _launch('tgt_gelu_dropout_bwd_colsum', _ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel(), _DT[pre.dtype], p, seed,
                         _ptr(sample_scale), eps_, N, _ptr(partial), _ptr(cs), prof='tgt_gelu_dropout_bwd')
             else:
-                _launch('tgt_gelu_dropout_scaled_bwd', _ptr(pre), _ptr(d_act), _ptr(d_pre), pre.numel(), _DT[pre.dtype], p, seed,
-                        _ptr(sample_scale), eps_, prof='tgt_gelu_dropout_bwd')
+                d_pre = _act_backward(fam, pre, d_act, kind, p, seed, sample_scale, eps_)
         if d_pre_in is not None:
             if d_pre is None:
-                handed = d_pre_in                                      # (the GELU_BWD epilogue that wrote it summed its columns)
+                handed = d_pre_in                              # (the GELU_BWD / ACT_BWD epilogue that wrote it summed its columns)
             d_pre = d_pre_in.contiguous() if d_pre is None else d_pre + d_pre_in
         if d_pre is None:
-            return _grads(_LINEAR_GELU_ARGS)
-        return _grads(_LINEAR_GELU_ARGS, *_linear_backward_db(ctx, x2, w, d_pre.view(-1, d_pre.shape[-1]), cs, handed))
+            return _grads(_LINEAR_ACT_ARGS)
+        return _grads(_LINEAR_ACT_ARGS, *_linear_backward_db(ctx, x2, w, d_pre.view(-1, d_pre.shape[-1]), cs, handed))
 
 
-_LINEAR_GELU_ARGS = _forward_args(_LinearGeluDropout, _XWB)
+_LINEAR_ACT_ARGS = _forward_args(_LinearActDropout, _XWB)
+
+
+def _linear_act_dropout(fam, x, weight, bias, kind, p, training, sample_scale, lazy=True):
+    """(act, its _ActRecord) of _LinearActDropout behind the three public entries; lazy False: no lazy data gradient"""
+    if fam.kinds is not None:
+        kind = _act_kind(fam, kind)
+    cd = _compute_dtype(x, on_cpu=True)
+    p, seed = draw_dropout(p, training)
+    act, pre = _LinearActDropout.apply(x, weight, bias, cd, fam, kind, p, seed, sample_scale, lazy and _lazy_ok(x, weight, cd))
+    return act, _ActRecord(pre, p, seed, sample_scale, kind)
 
 
 def _linear_act_ok(x, weight, sample_scale, N, ks, epilogue):
@@ -2541,34 +2520,9 @@ def linear_gelu_dropout_ok(x, weight, sample_scale=None):
 
 def linear_gelu_dropout(x, weight, bias, p, training, sample_scale=None):
     """dropout(gelu(linear(x, weight, bias)), p) [* sample_scale per graph] in one launch; see linear_gelu_dropout_ok"""
-    cd = _compute_dtype(x, on_cpu=True)
-    p, seed = draw_dropout(p, training)
-    act, pre = _LinearGeluDropout.apply(x, weight, bias, cd, p, seed, sample_scale, _lazy_ok(x, weight, cd))
-    # rides on the tensor object (as _tgt_colsum does): what a consumer needs to take over the activation's backward
-    act._tgt_gelu = (pre, p, seed, sample_scale)
+    act, record = _linear_act_dropout(_ACT_FAMILIES['gelu'], x, weight, bias, None, p, training, sample_scale)
+    act._tgt_gelu = record
     return act
-
-
-class _LinearGluDropout(torch.autograd.Function):
-    """act = dropout(e * act(g), p) * sample_scale[b] with [g | e] = x W^T + b as ONE launch (tgt_edge_linear, TGT_EPI_GLU: the
-    256 -> 512 weight-resident kernel with the activation in its store phase; reference FFN, lib/tgt/layers/layers.py:155-158 with
-    a GLU activation).  The pre-activation is written once for the backward, which is tgt_glu_dropout_bwd on it followed by the
-    Linear's (bias gradient: the column sums of d_pre)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, cd, kind, p, seed, sample_scale):
-        ctx.kind = kind
-        return _linear_act_forward(ctx, x, weight, bias, cd, _lib.EPI_GLU, weight.shape[0] // 2, p, seed, sample_scale,
-                                   flags=kind << _lib.EDGE_GLU_KIND_SHIFT)[0]
-
-    @staticmethod
-    def backward(ctx, d_act):
-        x2, w, pre, sample_scale = ctx.saved_tensors
-        d_pre = _glu_backward(pre, d_act, ctx.kind, ctx.p, ctx.seed, sample_scale, ctx.eps_)
-        return _grads(_LINEAR_GLU_ARGS, *_linear_backward_db(ctx, x2, w, d_pre.view(-1, d_pre.shape[-1])))
-
-
-_LINEAR_GLU_ARGS = _forward_args(_LinearGluDropout, _XWB)
 
 
 def linear_glu_dropout_ok(x, weight, sample_scale=None):
@@ -2579,46 +2533,12 @@ def linear_glu_dropout_ok(x, weight, sample_scale=None):
 def linear_glu_dropout(x, weight, bias, kind, p, training, sample_scale=None):
     """dropout(e * act(g), p) [* sample_scale per graph] with [g | e] = linear(x, weight, bias) in one launch; kind as in
     glu_dropout; see linear_glu_dropout_ok"""
-    kind = _glu_kind(kind)
-    cd = _compute_dtype(x, on_cpu=True)
-    p, seed = draw_dropout(p, training)
-    return _LinearGluDropout.apply(x, weight, bias, cd, kind, p, seed, sample_scale)
+    return _linear_act_dropout(_ACT_FAMILIES['glu'], x, weight, bias, kind, p, training, sample_scale, lazy=False)[0]
 
 
 # A/B knob: lin_W1 + relu / silu / elu + dropout as one launch on the edge rows and the activation's backward as the epilogue of
 # lin_W2's data-gradient GEMM (TGT_EPI_ACT / TGT_EPI_ACT_BWD), against library GEMM + one streaming pass each way
 _FFN_ACT_EPI = K.ffn_act_epi
-
-
-class _LinearActDropout(torch.autograd.Function):
-    """act = dropout(activation(x W^T + b), p) * sample_scale[b] for relu / silu / elu as ONE launch (tgt_edge_linear, TGT_EPI_ACT:
-    reference FFN, lib/tgt/layers/layers.py:155-158).  As _LinearGeluDropout: two outputs, the activation and the pre-activation
-    as a differentiable value of its own, so that linear_residual_layer_norm can take over the activation's backward
-    (TGT_EPI_ACT_BWD); otherwise the backward is tgt_act_dropout_bwd on the stored pre-activation followed by the Linear's."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, cd, kind, p, seed, sample_scale, lazy=False):
-        ctx.set_materialize_grads(False)
-        ctx.kind = kind
-        return _linear_act_forward(ctx, x, weight, bias, cd, _lib.EPI_ACT, weight.shape[0], p, seed, sample_scale, lazy,
-                                   flags=kind << _lib.EDGE_ACT_KIND_SHIFT)
-
-    @staticmethod
-    def backward(ctx, d_act, d_pre_in):
-        x2, w, pre, sample_scale = ctx.saved_tensors
-        d_pre = handed = None
-        if d_act is not None:
-            d_pre = _act_backward(pre, d_act, ctx.kind, ctx.p, ctx.seed, sample_scale, ctx.eps_)
-        if d_pre_in is not None:
-            if d_pre is None:
-                handed = d_pre_in                                      # (the ACT_BWD epilogue that wrote it summed its columns)
-            d_pre = d_pre_in.contiguous() if d_pre is None else d_pre + d_pre_in
-        if d_pre is None:
-            return _grads(_LINEAR_ACT_ARGS)
-        return _grads(_LINEAR_ACT_ARGS, *_linear_backward_db(ctx, x2, w, d_pre.view(-1, d_pre.shape[-1]), None, handed))
-
-
-_LINEAR_ACT_ARGS = _forward_args(_LinearActDropout, _XWB)
 
 
 def linear_act_dropout_ok(x, weight, sample_scale=None):
@@ -2629,12 +2549,8 @@ def linear_act_dropout_ok(x, weight, sample_scale=None):
 def linear_act_dropout(x, weight, bias, kind, p, training, sample_scale=None):
     """dropout(act(linear(x, weight, bias)), p) [* sample_scale per graph] in one launch; kind as in act_dropout; see
     linear_act_dropout_ok"""
-    kind = _act_kind(kind)
-    cd = _compute_dtype(x, on_cpu=True)
-    p, seed = draw_dropout(p, training)
-    act, pre = _LinearActDropout.apply(x, weight, bias, cd, kind, p, seed, sample_scale, _lazy_ok(x, weight, cd))
-    # the record of linear_gelu_dropout with the kind behind it: what a consumer needs to take over the activation's backward
-    act._tgt_gelu = (pre, p, seed, sample_scale, kind)
+    act, record = _linear_act_dropout(_ACT_FAMILIES['act'], x, weight, bias, kind, p, training, sample_scale)
+    act._tgt_gelu = record
     return act
 
 
@@ -2694,9 +2610,9 @@ class _LinearResidualLN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, res, scale, ln_w, ln_b, eps, cd, out_dtype, prescaled=False, pre=None, gelu=None, col_perm=None):
-        # pre / gelu = (p, seed, sample_scale[, kind]): x is dropout(gelu(pre)) * sample_scale, handed in DETACHED; this node then owns
+        # pre / gelu (the _ActRecord of x): x is dropout(gelu(pre)) * sample_scale, handed in DETACHED; this node then owns
         # the activation's derivative and returns the gradient of `pre` (GELU backward as the epilogue of the data-gradient GEMM).
-        # kind (TGT_ACT_*): the activation is relu / silu / elu instead (linear_act_dropout; TGT_EPI_ACT_BWD)
+        # gelu.kind (TGT_ACT_*): the activation is relu / silu / elu instead (linear_act_dropout; TGT_EPI_ACT_BWD)
         _dev(x, weight, res, ln_w, ln_b)
         ctx.lin = _LinearSaved.of(x, weight, bias)
         xs = ctx.lin.xs
@@ -2717,13 +2633,9 @@ class _LinearResidualLN(torch.autograd.Function):
         edge_linear_raw(x2, w, b, _lib.EPI_RESID, out=s.view(rows, N), res=res2, row_scale=scale, rows_per_sample=rps,
                         ln=(g, be, eps), stats=(mean, rstd), y=y.view(rows, N),
                         flags=_lib.EDGE_BIAS_SCALED if (prescaled and scale is not None) else 0, live=ctx.lin.live)
-        ctx.gelu = ctx.act_kind = None
-        if pre is not None:
-            ctx.gelu = (float(gelu[0]), gelu[1], gelu[2] is not None)
-            ctx.act_kind = gelu[3] if len(gelu) > 3 else None
-            ctx.save_for_backward(x2, w, s, g, mean, rstd, scale, pre, gelu[2])
-        else:
-            ctx.save_for_backward(x2, w, s, g, mean, rstd, scale)
+        # (the record's scalars; its tensors are saved: `pre` and the factor -- or None -- behind the seven of every call)
+        ctx.gelu = None if pre is None else gelu._replace(pre=None, p=float(gelu.p), sample_scale=None)
+        ctx.save_for_backward(x2, w, s, g, mean, rstd, scale, *(() if pre is None else (pre, gelu.sample_scale)))
         ctx.lndt, ctx.rdt, ctx.rps = ln_w.dtype, res.dtype, rps
         ctx.prescaled = bool(prescaled and scale is not None)
         return s, y
@@ -2752,13 +2664,13 @@ class _LinearResidualLN(torch.autograd.Function):
         if ctx.gelu is not None:
             # d_pre = ((d_z W) * sample_scale) * gelu'(pre) * keep / (1 - p): the data gradient and the activation's backward in
             # one launch (TGT_EPI_GELU_BWD); x was handed in detached, its slot gets no gradient
-            pre, g_scale = ctx.saved_tensors[7], (ctx.saved_tensors[8] if ctx.gelu[2] else None)
+            pre, g_scale = ctx.saved_tensors[7:9]
             if need[_LINEAR_RESIDUAL_LN_ARGS.index('pre')]:
                 d_pre = torch.empty_like(pre)
                 # (256 outputs = the row-phase kernel: it also returns the column sums of d_pre, lin_W1's bias gradient)
                 # the weight gradient of THIS Linear rides on the same launch (TGT_EDGE_WGRAD): dW = d_z^T x with x = the activation
                 # recomputed from `pre` in the row phase -- neither d_z nor x is read again by a weight-gradient GEMM
-                kind = ctx.act_kind                     # (relu / silu / elu: the same launch with TGT_EPI_ACT_BWD; no fused weight gradient)
+                kind = ctx.gelu.kind                    # (relu / silu / elu: the same launch with TGT_EPI_ACT_BWD; no fused weight gradient)
                 fuse_dw = (_EDGE_WGRAD and need_dw and ctx.col_inv is None and N == 256 and pre.shape[-1] == 256 and
                            x2.shape[1] == 256 and wdt == torch.float32 and kind is None)
                 parts = _lib.lib().tgt_edge_linear_parts(rows, 256)
@@ -2769,7 +2681,7 @@ class _LinearResidualLN(torch.autograd.Function):
                 dw_part = torch.empty(parts, 256, 256, dtype=torch.float32, device=pre.device) if fuse_dw else None
                 edge_linear_raw(d_z.reshape(rows, N), weight_t(w), None, _lib.EPI_GELU_BWD if kind is None else _lib.EPI_ACT_BWD,
                                 out=d_pre.view(rows, -1), res=pre.view(rows, -1), out_scale=g_scale, rows_per_sample=rps,
-                                dropout=(ctx.gelu[0], ctx.gelu[1]), colsum_partial=part, dw_partial=dw_part, live=live,
+                                dropout=(ctx.gelu.p, ctx.gelu.seed), colsum_partial=part, dw_partial=dw_part, live=live,
                                 flags=0 if kind is None else kind << _lib.EDGE_ACT_KIND_SHIFT)
                 if part is not None:
                     with _on_stream(_terminal_fork(rows, part)):
@@ -2825,13 +2737,13 @@ def linear_residual_layer_norm(x, weight, bias, res, scale, ln_weight, ln_bias, 
     cd = _compute_dtype(x)
     # x = the FFN's activation out of linear_gelu_dropout: take over its backward when the data gradient runs on the row-phase kernel
     gelu = getattr(x, '_tgt_gelu', None)
-    if gelu is not None and not (_FFN_ACT_EPI if len(gelu) > 4 else _FFN_GELU_BWD_EPI):      # (the record of linear_act_dropout ends with a kind)
+    if gelu is not None and not (_FFN_GELU_BWD_EPI if gelu.kind is None else _FFN_ACT_EPI):
         gelu = None
-    if gelu is not None and not (weight.shape[0] == 256 and weight.shape[1] == 256 and gelu[0].dtype == cd and
+    if gelu is not None and not (weight.shape[0] == 256 and weight.shape[1] == 256 and gelu.pre.dtype == cd and
                                  _residual_fusable(x, weight, res, cd) and
-                                 edge_linear_supported(256, 256, cd, _lib.EPI_ACT_BWD if len(gelu) > 4 else _lib.EPI_GELU_BWD)):
+                                 edge_linear_supported(256, 256, cd, _lib.EPI_GELU_BWD if gelu.kind is None else _lib.EPI_ACT_BWD)):
         gelu = None
-    extra = () if gelu is None else (gelu[0], gelu[1:])
+    extra = () if gelu is None else (gelu.pre, gelu)
     if gelu is not None:
         x = x.detach()
     if col_perm is not None:
