@@ -23,8 +23,8 @@
  *    (c = d*H + h).  The Python mirror permutes the projection weights, not
  *    the activations, to get head-major triplet operands.
  *  - ragged batches: what a padded node or a padded edge row would compute may be left out on request -- per-graph node
- *    counts beside the argument block (tgt_triplet_attention_*_counts), a live tile list beside it (tgt_edge_linear_live);
- *    both are permissions to skip, never obligations, and a NULL pointer is the plain entry point.
+ *    counts beside the argument block (tgt_triplet_attention_*_counts), a live tile list beside it (tgt_edge_linear_live,
+ *    tgt_edge_gated_out_fwd_live); both are permissions to skip, never obligations, and a NULL pointer is the plain entry point.
  */
 #ifndef TGT_HIP_H
 #define TGT_HIP_H
@@ -299,6 +299,27 @@ int tgt_triangular_update_tiled_fwd(const void* e4, int64_t ld_e, const void* v4
 int tgt_triangular_update_tiled_bwd(const void* e4, int64_t ld_e, const void* v4, int64_t ld_v, const float* mask,
                                     const void* d_out, void* d_e4, int64_t ld_de, void* d_v4, int64_t ld_dv,
                                     int32_t B, int32_t N, int32_t H, int32_t dtype, void* stream);
+/* Ragged batches: the tiled core with per-graph node counts.  node_counts: (B) int32 DEVICE memory; n_b = clamp(node_counts[b],
+ * 0, N), clamped in the kernel; nothing is read on the host (capturable).  node_counts == NULL: the plain entry point (which
+ * forwards here with NULL).  Checks: those of the plain entry points in their order, then a node_counts pointer that is not 4-byte
+ * aligned (TGT_ERR_INVALID).
+ * The caller vouches that the mask closes (finfo.min or -inf) every pair (i, j) of graph b with i >= n_b or j >= n_b -- ROWS as
+ * well as columns, as for tgt_node_attention_fwd_counts.  A count is a permission to skip, never an obligation.
+ * Per workgroup (graph, head group, direction), n = n_b: only the pairs of the real block [0, n) x [0, n) are staged, the
+ * contraction runs over ceil(n / 16) chunks, result tiles with a first row or column at or past n are not multiplied.  Nothing is
+ * read at a pair with a node >= n: not e4 / v4, not mask, not d_out (the backward takes d_out as zero there).  Every position of
+ * [0, N) x [0, N) is still written: out, and columns [0, 4H) of d_e4 / d_v4, are zeros (+0) at pairs with a node >= n; n = 0:
+ * all zeros.
+ * Exact under the contract: all four operands are gated by the mask of their own pair and a closed gate is exactly 0, so a pair
+ * with a padded node adds exact zeros to every sum and the plain call's own result there is zero (of either sign in the backward).
+ * The real block is value-equal (==) to the plain call's, run to run bit-reproducible: fixed summation order, no atomics. */
+int tgt_triangular_update_tiled_fwd_counts(const void* e4, int64_t ld_e, const void* v4, int64_t ld_v, const float* mask,
+                                           void* out, int32_t B, int32_t N, int32_t H, int32_t dtype,
+                                           const int32_t* node_counts, void* stream);
+int tgt_triangular_update_tiled_bwd_counts(const void* e4, int64_t ld_e, const void* v4, int64_t ld_v, const float* mask,
+                                           const void* d_out, void* d_e4, int64_t ld_de, void* d_v4, int64_t ld_dv,
+                                           int32_t B, int32_t N, int32_t H, int32_t dtype, const int32_t* node_counts,
+                                           void* stream);
 
 /* ------------------------------------------------------------------------
  * Node attention with edge bias + gate (EGT_Attention) and the logits-only
@@ -599,6 +620,21 @@ int tgt_edge_gated_out_bwd(const tgt_edge_gated_args* a, void* stream);
 int tgt_edge_live_tiles(const int32_t* node_counts, int32_t B, int32_t N, int32_t* tiles, void* stream);
 int tgt_edge_linear_live_supported(const tgt_edge_linear_args* a);
 int tgt_edge_linear_live(const tgt_edge_linear_args* a, const int32_t* tiles, void* stream);
+/* The gated output stage of TriangularUpdate on the live tiles only: tgt_edge_gated_out_fwd / _bwd with the list of
+ * tgt_edge_live_tiles (1 + ceil(M / 32) entries).  tiles == NULL: the plain call.  The argument block, its checks and their order
+ * are unchanged; then a list that is not 4-byte aligned or more row tiles than an int32 list can name (TGT_ERR_INVALID).
+ * Same grid and same dealing as tgt_edge_linear_live: tgt_edge_gated_out_parts, `parts` and the grid-cap hook keep their meaning;
+ * workgroup w walks tiles[1 + w + s * grid] while that index is below tiles[0], the dead tiles the same way from the tail;
+ * entries are clamped where they are read.
+ * Forward: dead tiles get ZEROS in s, y, mean, rstd and no operand of a dead tile is read; live tiles are bit-identical to the
+ *   plain launch.
+ * Backward: dead tiles get zeros in d_a; dt, a and s of a dead tile are not read and it adds nothing to dw_partial / db_partial.
+ *   Every plane and row of the partials is still written, those of a workgroup without a live tile included (zeros).  d_a of live
+ *   tiles is bit-identical to the plain launch; the list regroups rows over workgroups, so the summed weight and bias gradients
+ *   equal the plain launch's up to fp32 summation order, bit-reproducible run to run.
+ * The caller vouches that the dead rows do not matter, as for tgt_edge_linear_live. */
+int tgt_edge_gated_out_fwd_live(const tgt_edge_gated_args* a, const int32_t* tiles, void* stream);
+int tgt_edge_gated_out_bwd_live(const tgt_edge_gated_args* a, const int32_t* tiles, void* stream);
 
 /* ------------------------------------------------------------------------
  * LayerNorm over the last axis (the five per-layer norms of the TGT layer:

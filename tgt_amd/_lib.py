@@ -175,6 +175,8 @@ SYMBOLS = {
     'tgt_triangular_update_tiled_supported': (C.c_int, [_i32, _i32, _i32]),
     'tgt_triangular_update_tiled_fwd': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     'tgt_triangular_update_tiled_bwd': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    'tgt_triangular_update_tiled_fwd_counts': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'tgt_triangular_update_tiled_bwd_counts': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     'tgt_gelu_dropout_fwd': (C.c_int, [_vp, _vp, _i64, _i32, _f32, C.c_uint64, _vp]),
     'tgt_gelu_dropout_bwd': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, C.c_uint64, _vp]),
     'tgt_gelu_dropout_scaled_fwd': (C.c_int, [_vp, _vp, _i64, _i32, _f32, C.c_uint64, _vp, _i64, _vp]),
@@ -212,6 +214,8 @@ SYMBOLS = {
     'tgt_edge_live_tiles': (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     'tgt_edge_linear_live_supported': (C.c_int, [C.POINTER(EdgeLinearArgs)]),
     'tgt_edge_linear_live': (C.c_int, [C.POINTER(EdgeLinearArgs), _vp, _vp]),
+    'tgt_edge_gated_out_fwd_live': (C.c_int, [C.POINTER(EdgeGatedArgs), _vp, _vp]),
+    'tgt_edge_gated_out_bwd_live': (C.c_int, [C.POINTER(EdgeGatedArgs), _vp, _vp]),
     'tgt_adam_step': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _vp, _vp, _i32, _vp]),
     'tgt_grad_stats_parts': (C.c_int, []),
     'tgt_grad_scaler_step': (C.c_int, [_vp, _i64, _vp, _vp, _i32, _f32, _f32, _i32, _f32, _f32, _i32, _vp]),

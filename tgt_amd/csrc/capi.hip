@@ -48,10 +48,10 @@ int triangular_update_run(const void* e4, const void* v4, const float* mask, voi
 int triangular_update_tiled_supported(int N, int H, int dtype);
 int triangular_update_tiled_run(const void* e4, int64_t ld_e, const void* v4, int64_t ld_v, const float* mask, void* out,
                                 const void* d_out, void* d_e4, int64_t ld_de, void* d_v4, int64_t ld_dv, int B, int N, int H,
-                                int dtype, bool bwd, hipStream_t st);
+                                int dtype, bool bwd, const int32_t* node_counts, hipStream_t st);
 int edge_gated_out_supported(const tgt_edge_gated_args* a);
 int edge_gated_out_parts(int64_t M);
-int edge_gated_out_run(const tgt_edge_gated_args* a, bool bwd, hipStream_t st);
+int edge_gated_out_run(const tgt_edge_gated_args* a, bool bwd, const int32_t* tiles, hipStream_t st);
 int colsum_run(const void* x, int x_dtype, int64_t rows, int C, float* out, float* partial, hipStream_t st);
 int sum_rows_run(const float* x, int rows, int C, float* out, hipStream_t st);
 int gelu_dropout_bwd_colsum_run(const void* x, const void* dy, void* out, int64_t n, int dtype, float p, uint64_t seed,
@@ -167,14 +167,23 @@ int tgt_triangular_update_bwd(const void* e4, const void* v4, const float* mask,
 int tgt_triangular_update_tiled_supported(int32_t N, int32_t H, int32_t dtype) { return triangular_update_tiled_supported(N, H, dtype); }
 int tgt_triangular_update_tiled_fwd(const void* e4, int64_t ld_e, const void* v4, int64_t ld_v, const float* mask, void* out,
                                     int32_t B, int32_t N, int32_t H, int32_t dtype, void* stream) {
+    return tgt_triangular_update_tiled_fwd_counts(e4, ld_e, v4, ld_v, mask, out, B, N, H, dtype, nullptr, stream);
+}
+int tgt_triangular_update_tiled_fwd_counts(const void* e4, int64_t ld_e, const void* v4, int64_t ld_v, const float* mask, void* out,
+                                           int32_t B, int32_t N, int32_t H, int32_t dtype, const int32_t* node_counts, void* stream) {
     return triangular_update_tiled_run(e4, ld_e, v4, ld_v, mask, out, nullptr, nullptr, 0, nullptr, 0, B, N, H, dtype, false,
-                                       reinterpret_cast<hipStream_t>(stream));
+                                       node_counts, reinterpret_cast<hipStream_t>(stream));
 }
 int tgt_triangular_update_tiled_bwd(const void* e4, int64_t ld_e, const void* v4, int64_t ld_v, const float* mask,
                                     const void* d_out, void* d_e4, int64_t ld_de, void* d_v4, int64_t ld_dv, int32_t B, int32_t N,
                                     int32_t H, int32_t dtype, void* stream) {
+    return tgt_triangular_update_tiled_bwd_counts(e4, ld_e, v4, ld_v, mask, d_out, d_e4, ld_de, d_v4, ld_dv, B, N, H, dtype, nullptr, stream);
+}
+int tgt_triangular_update_tiled_bwd_counts(const void* e4, int64_t ld_e, const void* v4, int64_t ld_v, const float* mask,
+                                           const void* d_out, void* d_e4, int64_t ld_de, void* d_v4, int64_t ld_dv, int32_t B, int32_t N,
+                                           int32_t H, int32_t dtype, const int32_t* node_counts, void* stream) {
     return triangular_update_tiled_run(e4, ld_e, v4, ld_v, mask, nullptr, d_out, d_e4, ld_de, d_v4, ld_dv, B, N, H, dtype, true,
-                                       reinterpret_cast<hipStream_t>(stream));
+                                       node_counts, reinterpret_cast<hipStream_t>(stream));
 }
 int tgt_gelu_dropout_fwd(const void* x, void* y, int64_t n, int32_t dtype, float p, uint64_t seed, void* stream) {
     return gelu_dropout_run(x, nullptr, y, n, dtype, p, seed, false, nullptr, 0, reinterpret_cast<hipStream_t>(stream));
@@ -369,11 +378,13 @@ int tgt_edge_live_tiles(const int32_t* node_counts, int32_t B, int32_t N, int32_
 void tgt_edge_linear_set_grid_cap(int32_t cap) { edge_linear_set_grid_cap(cap); }
 int tgt_edge_gated_out_supported(const tgt_edge_gated_args* a) { return edge_gated_out_supported(a); }
 int tgt_edge_gated_out_parts(int64_t M) { return edge_gated_out_parts(M); }
-int tgt_edge_gated_out_fwd(const tgt_edge_gated_args* a, void* stream) {
-    return edge_gated_out_run(a, false, reinterpret_cast<hipStream_t>(stream));
+int tgt_edge_gated_out_fwd(const tgt_edge_gated_args* a, void* stream) { return tgt_edge_gated_out_fwd_live(a, nullptr, stream); }
+int tgt_edge_gated_out_bwd(const tgt_edge_gated_args* a, void* stream) { return tgt_edge_gated_out_bwd_live(a, nullptr, stream); }
+int tgt_edge_gated_out_fwd_live(const tgt_edge_gated_args* a, const int32_t* tiles, void* stream) {
+    return edge_gated_out_run(a, false, tiles, reinterpret_cast<hipStream_t>(stream));
 }
-int tgt_edge_gated_out_bwd(const tgt_edge_gated_args* a, void* stream) {
-    return edge_gated_out_run(a, true, reinterpret_cast<hipStream_t>(stream));
+int tgt_edge_gated_out_bwd_live(const tgt_edge_gated_args* a, const int32_t* tiles, void* stream) {
+    return edge_gated_out_run(a, true, tiles, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -16,6 +16,14 @@
 //             accumulator holds it, the resident W fragments permuted alike); the four waves' partial sums meet in LDS, fixed order.
 //             dw:  dz^T and a^T go through LDS (the contraction index is the row), accumulators persist over the tiles.
 // Rows at or past M: a and dt read as zeros, so dz is zero there and nothing of them enters d_a / dw / db; no store leaves M rows.
+//
+// Ragged batches (tgt_hip.h, tgt_edge_gated_out_fwd_live / _bwd_live): the live tile list of edge_common.hpp as a trailing parameter
+// pack `TL... tl` of both kernels, empty without a list -- that instantiation has the argument list and the instruction stream it
+// always had.  With a list workgroup w walks list[1 + w + s * gridDim] below list[0] (the dealing of tgt_edge_linear_live, same
+// grid) and first gives its share of the DEAD tiles zeros in every output (s, y, mean, rstd; d_a) without reading an operand of
+// them.  The trip count of the tile loop is uniform per workgroup, so its barriers are too; a workgroup without a live tile still
+// writes its (zero) dw_partial plane and db_partial row.  Entries are clamped where they are read (edge_live_tile): a tile index
+// past the last row loads zeros and stores nothing.
 #include "edge_common.hpp"
 
 namespace tgt {
@@ -73,23 +81,86 @@ __device__ __forceinline__ void go_load_a(const T* a, int64_t lda, int64_t m, in
     for (int kc = 0; kc < KC; ++kc) af[kc] = m < M ? load_frag<T>(a + m * lda + kc * 16 + 8 * hi) : zero_frag<T>();
 }
 
+// zeros into columns [0, cols) of rows [32 tile, 32 tile + 32) of an (M, ld) tensor, by the 256 threads of a workgroup: 16 bytes each
+template <typename T>
+__device__ __forceinline__ void go_zero_rows(T* base, int64_t ld, int cols, int64_t tile, int64_t M, int tid) {
+    const int per_row = cols / 8;
+    for (int i = tid; i < 32 * per_row; i += 256) {
+        const int64_t mr = tile * 32 + i / per_row;
+        if (mr < M) *reinterpret_cast<uint4*>(base + mr * ld + (i % per_row) * 8) = make_uint4(0, 0, 0, 0);
+    }
+}
+
+// The LIVE walk reads the list through the constant address space.  These kernels store through plain pointers, so hipcc cannot
+// prove a plain `list[i]` untouched by them and reads it with a VECTOR load and a full `s_waitcnt vmcnt(0)` at the top of every
+// tile -- which also drains the stores of the tile before (read off the ISA; +6 us on the 175 us backward with a list that names
+// every tile).  The kernels never write the list, so it IS constant for them: a uniform index is then one scalar load, issued a
+// tile ahead.  Same clamping as edge_live_count / edge_live_tile (edge_common.hpp), which the dead walk uses as they are.
+typedef const __attribute__((address_space(4))) int32_t* go_list_t;
+__device__ __forceinline__ go_list_t go_const_list(const int32_t* p) { return (go_list_t)reinterpret_cast<uintptr_t>(p); }
+__device__ __forceinline__ int go_live_count(go_list_t list, int64_t row_tiles) {
+    const int n = list[0];
+    return n < 0 ? 0 : (n > row_tiles ? (int)row_tiles : n);
+}
+// entry `idx` as it stands in the list (0 at or past `end`: never used); it becomes a tile -- go_clamp_tile -- only where it is
+// USED, a tile later, so the wait for the load sits there and not behind the load
+__device__ __forceinline__ int go_live_raw(go_list_t list, int64_t idx, int64_t end) { return idx < end ? list[1 + idx] : 0; }
+__device__ __forceinline__ int64_t go_clamp_tile(int t, int64_t row_tiles) {
+    return t < 0 ? row_tiles : (t > row_tiles ? row_tiles : (int64_t)t);
+}
+// The list's count and this workgroup's first entry, read at the TOP of a kernel: two independent scalar loads whose latency the
+// weight loads hide.  The entry is read whether or not it is live: index blockIdx.x is below the row tiles (the grid never exceeds
+// them), so inside the list.
+struct GoLiveHead {
+    int n_live;
+    int first_raw;
+};
+__device__ __forceinline__ GoLiveHead go_live_head(go_list_t list, int64_t row_tiles) {
+    const int64_t w = (int64_t)blockIdx.x < row_tiles ? (int64_t)blockIdx.x : row_tiles - 1;
+    const int raw = list[1 + w];
+    return {go_live_count(list, row_tiles), raw};
+}
+
 __device__ __forceinline__ float go_wave_sum4(const float* red, int r) {          // the four waves' partials of row r, fixed order
     return ((red[r] + red[32 + r]) + red[64 + r]) + red[96 + r];
 }
 
-template <typename T, int K>
-__global__ void __launch_bounds__(256) edge_gated_fwd_kernel(const tgt_edge_gated_args a) {
+template <typename T, int K, typename... TL>
+__global__ void __launch_bounds__(256) edge_gated_fwd_kernel(const tgt_edge_gated_args a, TL... tl) {
     constexpr int KC = K / 16;
+    constexpr bool LV = sizeof...(TL) > 0;
     __shared__ float red[2][4 * 32];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5;
     const T* bias = reinterpret_cast<const T*>(a.bias);
     const T* res = reinterpret_cast<const T*>(a.res);
     T* s_out = reinterpret_cast<T*>(a.s);
     T* y_out = reinterpret_cast<T*>(a.y);
+    const int64_t M = a.M, tiles = (M + 31) / 32;
+    const int32_t* live = edge_live_ptr(tl...);
+    int64_t n_walk = tiles;                                // entries this launch deals: all tiles, or the live ones of the list
+    int raw_next = 0;
+    if constexpr (LV) {
+        const GoLiveHead head = go_live_head(go_const_list(live), tiles);
+        n_walk = head.n_live;
+        raw_next = head.first_raw;
+    }
     GoWeights<T, K> W;
     W.load(reinterpret_cast<const T*>(a.w), a.ldw, wave, r, hi);
-    const int64_t M = a.M, tiles = (M + 31) / 32;
-    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    if constexpr (LV) {
+        edge_dead_tiles(live, (int)n_walk, tiles, [&](int64_t t) {      // zeros, no operand read
+            go_zero_rows<T>(s_out, GO_C, GO_C, t, M, threadIdx.x);
+            go_zero_rows<T>(y_out, GO_C, GO_C, t, M, threadIdx.x);
+            const int64_t mr = t * 32 + threadIdx.x;
+            if (threadIdx.x < 32 && mr < M) { a.mean[mr] = 0.f; a.rstd[mr] = 0.f; }
+        });
+    }
+    // (with a list: the NEXT entry is read while this tile computes -- a scalar load whose latency the tile hides)
+    for (int64_t it = blockIdx.x; it < n_walk; it += gridDim.x) {
+        int64_t tile = it;
+        if constexpr (LV) {
+            tile = go_clamp_tile(raw_next, tiles);
+            raw_next = go_live_raw(go_const_list(live), it + gridDim.x, n_walk);
+        }
         const int64_t m = tile * 32 + r;
         frag_t<T> af[KC];
         go_load_a<T, KC>(reinterpret_cast<const T*>(a.a), a.lda, m, M, hi, af);
@@ -138,9 +209,10 @@ __global__ void __launch_bounds__(256) edge_gated_fwd_kernel(const tgt_edge_gate
     }
 }
 
-template <typename T, int K>
-__global__ void __launch_bounds__(256) edge_gated_bwd_kernel(const tgt_edge_gated_args a) {
+template <typename T, int K, typename... TL>
+__global__ void __launch_bounds__(256) edge_gated_bwd_kernel(const tgt_edge_gated_args a, TL... tl) {
     constexpr int KC = K / 16, KB = K > 32 ? K / 32 : 1;
+    constexpr bool LV = sizeof...(TL) > 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char go_smem[];
     T* dzT = reinterpret_cast<T*>(go_smem);                       // [2C][GO_TP]: dz transposed, row = weight row
     T* aT = dzT + 2 * GO_C * GO_TP;                               // [64][GO_TP]: the a tile transposed (rows at or past K stay zero)
@@ -150,6 +222,15 @@ __global__ void __launch_bounds__(256) edge_gated_bwd_kernel(const tgt_edge_gate
     const T* bias = reinterpret_cast<const T*>(a.bias);
     const T* dt = reinterpret_cast<const T*>(a.dt);
     T* d_a = reinterpret_cast<T*>(a.d_a);
+    const int64_t M = a.M, tiles = (M + 31) / 32;
+    const int32_t* live = edge_live_ptr(tl...);
+    int64_t n_walk = tiles;
+    int raw_next = 0;
+    if constexpr (LV) {
+        const GoLiveHead head = go_live_head(go_const_list(live), tiles);
+        n_walk = head.n_live;
+        raw_next = head.first_raw;
+    }
     for (int i = tid; i < 64 * GO_TP; i += 256) aT[i] = from_f32<T>(0.f);
     GoWeights<T, K> W;
     W.load(wp, a.ldw, wave, r, hi);
@@ -180,8 +261,14 @@ __global__ void __launch_bounds__(256) edge_gated_bwd_kernel(const tgt_edge_gate
             for (int q = 0; q < 16; ++q) dw[j][kb][q] = 0.f;
     float db[2] = {0.f, 0.f};
     __syncthreads();
-    const int64_t M = a.M, tiles = (M + 31) / 32;
-    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    if constexpr (LV) edge_dead_tiles(live, (int)n_walk, tiles, [&](int64_t t) { go_zero_rows<T>(d_a, a.ld_da, K, t, M, tid); });      // dt / a / s not read
+    // (with a list: the NEXT entry is read while this tile computes -- a scalar load whose latency the tile hides)
+    for (int64_t it = blockIdx.x; it < n_walk; it += gridDim.x) {
+        int64_t tile = it;
+        if constexpr (LV) {
+            tile = go_clamp_tile(raw_next, tiles);
+            raw_next = go_live_raw(go_const_list(live), it + gridDim.x, n_walk);
+        }
         const int64_t m = tile * 32 + r;
         frag_t<T> af[KC];
         go_load_a<T, KC>(reinterpret_cast<const T*>(a.a), a.lda, m, M, hi, af);
@@ -273,22 +360,23 @@ __global__ void __launch_bounds__(256) edge_gated_bwd_kernel(const tgt_edge_gate
     a.db_partial[(int64_t)blockIdx.x * 2 * GO_C + 256 + tid] = db[1];
 }
 
-template <typename T, int K>
-int go_launch(const tgt_edge_gated_args& a, bool bwd, int grid, hipStream_t st) {
+// (TL: empty, or the live tile list -- the kernels' trailing parameter pack)
+template <typename T, int K, typename... TL>
+int go_launch(const tgt_edge_gated_args& a, bool bwd, int grid, hipStream_t st, TL... tl) {
     if (!bwd) {
-        hipLaunchKernelGGL((edge_gated_fwd_kernel<T, K>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((edge_gated_fwd_kernel<T, K, TL...>), dim3(grid), dim3(256), 0, st, a, tl...);
         return check_launch("edge_gated_fwd_kernel");
     }
     const int lds = (2 * GO_C + 64) * GO_TP * (int)sizeof(T) + 4 * 32 * 64 * (int)sizeof(float);
-    return launch_lds<edge_gated_bwd_kernel<T, K>>("edge_gated_bwd_kernel", dim3(grid), dim3(256), lds, st, a);
+    return launch_lds<edge_gated_bwd_kernel<T, K, TL...>>("edge_gated_bwd_kernel", dim3(grid), dim3(256), lds, st, a, tl...);
 }
 
-template <typename T>
-int go_dispatch(const tgt_edge_gated_args& a, bool bwd, int grid, hipStream_t st) {
+template <typename T, typename... TL>
+int go_dispatch(const tgt_edge_gated_args& a, bool bwd, int grid, hipStream_t st, TL... tl) {
     switch (a.K) {
-        case 16: return go_launch<T, 16>(a, bwd, grid, st);
-        case 32: return go_launch<T, 32>(a, bwd, grid, st);
-        default: return go_launch<T, 64>(a, bwd, grid, st);
+        case 16: return go_launch<T, 16>(a, bwd, grid, st, tl...);
+        case 32: return go_launch<T, 32>(a, bwd, grid, st, tl...);
+        default: return go_launch<T, 64>(a, bwd, grid, st, tl...);
     }
 }
 
@@ -302,7 +390,8 @@ int edge_gated_out_supported(const tgt_edge_gated_args* a) {
 
 int edge_gated_out_parts(int64_t M) { return M > 0 ? edge_linear_parts(M, GO_C) : 0; }
 
-int edge_gated_out_run(const tgt_edge_gated_args* a, bool bwd, hipStream_t st) {
+// tiles: NULL, or the live tile list (1 + ceil(M / 32) entries) of tgt_edge_live_tiles
+int edge_gated_out_run(const tgt_edge_gated_args* a, bool bwd, const int32_t* tiles, hipStream_t st) {
     const char* what = bwd ? "edge gated output bwd" : "edge gated output fwd";
     if (!a) return set_error(TGT_ERR_INVALID, "%s: null args", what);
     if (a->M < 0 || a->K <= 0 || a->C <= 0) return set_error(TGT_ERR_INVALID, "%s: bad size", what);
@@ -313,7 +402,7 @@ int edge_gated_out_run(const tgt_edge_gated_args* a, bool bwd, hipStream_t st) {
     if (a->lda < a->K || a->lda % 8 || a->ldw < a->K || a->ldw % 8)
         return set_error(TGT_ERR_INVALID, "%s: lda %lld / ldw %lld (at least K, a multiple of 8)", what, (long long)a->lda, (long long)a->ldw);
     if (go_misaligned(a->a) || go_misaligned(a->w) || go_misaligned(a->bias)) return set_error(TGT_ERR_INVALID, "%s: operand not 16-byte aligned", what);
-    const int64_t tiles = (a->M + 31) / 32;
+    const int64_t row_tiles = (a->M + 31) / 32;
     int grid;
     if (!bwd) {
         if (!a->res || !a->s || !a->y || !a->gamma || !a->beta || !a->mean || !a->rstd) return set_error(TGT_ERR_INVALID, "%s: null tensor", what);
@@ -325,8 +414,13 @@ int edge_gated_out_run(const tgt_edge_gated_args* a, bool bwd, hipStream_t st) {
         if (!a->dt || !a->d_a || !a->dw_partial || !a->db_partial) return set_error(TGT_ERR_INVALID, "%s: null tensor", what);
         if (a->ld_da < a->K || a->ld_da % 8) return set_error(TGT_ERR_INVALID, "%s: ld_da %lld (at least K, a multiple of 8)", what, (long long)a->ld_da);
         if (go_misaligned(a->dt) || go_misaligned(a->d_a)) return set_error(TGT_ERR_INVALID, "%s: tensor not 16-byte aligned", what);
-        if (a->parts < 1 || a->parts > tiles) return set_error(TGT_ERR_INVALID, "%s: %d partial planes for %lld row tiles", what, a->parts, (long long)tiles);
+        if (a->parts < 1 || a->parts > row_tiles) return set_error(TGT_ERR_INVALID, "%s: %d partial planes for %lld row tiles", what, a->parts, (long long)row_tiles);
         grid = a->parts;
+    }
+    if (tiles) {
+        if (reinterpret_cast<uintptr_t>(tiles) & 3) return set_error(TGT_ERR_INVALID, "%s: live tile list not 4-byte aligned", what);
+        if (row_tiles > 0x7ffffffeLL) return set_error(TGT_ERR_INVALID, "%s: too many rows for a live tile list", what);
+        return a->dtype == TGT_BF16 ? go_dispatch<bf16_t>(*a, bwd, grid, st, tiles) : go_dispatch<f16_t>(*a, bwd, grid, st, tiles);
     }
     return a->dtype == TGT_BF16 ? go_dispatch<bf16_t>(*a, bwd, grid, st) : go_dispatch<f16_t>(*a, bwd, grid, st);
 }

@@ -26,8 +26,8 @@ _SPEC = {
     'tri_skip': ('TGT_TRI_SKIP', 1, 'int', 'triplet kernels skip DropPath-dropped graphs: 0 off, 1 forward, 2 backward too'),
     'tri_ragged': ('TGT_TRI_RAGGED', False, 'flag', 'triplet attention skips the padded nodes of every graph (N <= 64): per-graph node counts from the mask, once per forward; padded positions of the edge stream then hold other finite values'),
     'tri_ragged_kb': ('TGT_TRI_RAGGED_KB', False, 'flag', 'the key-blocked triplet attention kernels (65..128 nodes) use the node counts they are given (TGT_TRI_COUNTS_KB): padded units, query tiles and key blocks are skipped; needs tri_ragged in the model'),
-    'edge_ragged': ('TGT_EDGE_RAGGED', False, 'flag', 'the persistent edge row kernels skip the 32-row tiles that hold padded rows only (tgt_edge_linear_live): one live tile list per forward from the node counts; needs tri_ragged, and a model whose triplet modules all take node counts (the attention family)'),
-    'node_ragged': ('TGT_NODE_RAGGED', False, 'flag', 'node attention skips the padded nodes of every graph (tgt_node_attention_*_counts: the key-blocked forward, the backwards up to 64 nodes); the count then bounds rows as well as columns of the mask (two more small launches per forward); needs tri_ragged, and a model whose triplet modules all take node counts (the attention family)'),
+    'edge_ragged': ('TGT_EDGE_RAGGED', False, 'flag', 'the persistent edge row kernels skip the 32-row tiles that hold padded rows only (tgt_edge_linear_live): one live tile list per forward from the node counts; needs tri_ragged, and a model whose triplet modules all take node counts (the attention family and TriangularUpdate)'),
+    'node_ragged': ('TGT_NODE_RAGGED', False, 'flag', 'node attention skips the padded nodes of every graph (tgt_node_attention_*_counts: the key-blocked forward, the backwards up to 64 nodes); the count then bounds rows as well as columns of the mask (two more small launches per forward); needs tri_ragged, and a model whose triplet modules all take node counts (the attention family and TriangularUpdate)'),
     'triupd_tiled': ('TGT_TRIUPD_TILED', True, 'flag', 'TriangularUpdate core on staged matrix-core tiles (tgt_triangular_update_tiled_*: 16-bit, N <= 64, H a multiple of 4) instead of the lane-per-head kernel; every operand is gated once, in the element type (profiles/triupd_ab.txt)'),
     'triupd_gated': ('TGT_TRIUPD_GATED', True, 'flag', "TriangularUpdate's lin_O + gate + DropPath + residual + the edge FFN's LayerNorm as one launch each way (tgt_edge_gated_out_*: 16-bit, C = 256, 2H in {16, 32, 64}) instead of library GEMM + eager gate + add/LayerNorm pass (profiles/triupd_ab.txt)"),
     'defer_sums': ('TGT_DEFER_SUMS', False, 'flag', 'closing sums of the backward collected into one launch (measured slower)'),

@@ -1112,19 +1112,26 @@ def _triupd_tiled_ok(N, H, dtype):
 class _TriangularUpdatePacked(torch.autograd.Function):
     """ops.triangular_update on the two halves of ONE projection output ev = [lin_E | lin_V] (B,N,N,8H); the backward writes one
     (B,N,N,8H) gradient.  Tiled kernels where they take the shape (row stride 8H: nothing is copied), else the lane-per-head
-    kernel on contiguous copies of the halves."""
+    kernel on contiguous copies of the halves.  node_counts (ragged batches): the tiled kernels skip the pairs with a node at or
+    past the count, the backward with the counts its forward had; the lane-per-head route drops them."""
 
     @staticmethod
-    def forward(ctx, ev, mask3, H):
-        _dev(ev, mask3)
+    def forward(ctx, ev, mask3, H, node_counts=None):
+        _dev(ev, mask3, node_counts)
         ev = ev.contiguous()
         B, N = ev.shape[0], ev.shape[1]
+        _check_per_graph(node_counts, B, torch.int32, 'triangular update: node_counts')
         out = torch.empty(B, N, N, 2 * H, dtype=ev.dtype, device=ev.device)
         ctx.tiled = _triupd_tiled_ok(N, H, ev.dtype)
+        ctx.node_counts = node_counts if ctx.tiled else None
         if ctx.tiled:
             v_ptr = C.c_void_p(ev.data_ptr() + 4 * H * ev.element_size())
-            _launch('tgt_triangular_update_tiled_fwd', _ptr(ev), 8 * H, v_ptr, 8 * H, _ptr(mask3), _ptr(out), B, N, H, _DT[ev.dtype],
-                    prof='tgt_triangular_update_tiled_fwd')
+            if node_counts is None:
+                _launch('tgt_triangular_update_tiled_fwd', _ptr(ev), 8 * H, v_ptr, 8 * H, _ptr(mask3), _ptr(out), B, N, H, _DT[ev.dtype],
+                        prof='tgt_triangular_update_tiled_fwd')
+            else:          # (ragged: tgt_hip.h, tgt_triangular_update_tiled_fwd_counts -- the backward below gets the same counts)
+                _launch('tgt_triangular_update_tiled_fwd_counts', _ptr(ev), 8 * H, v_ptr, 8 * H, _ptr(mask3), _ptr(out), B, N, H,
+                        _DT[ev.dtype], _ptr(node_counts), prof='tgt_triangular_update_tiled_fwd')
         else:
             e4, v4 = ev[..., :4 * H].contiguous(), ev[..., 4 * H:].contiguous()
             _launch('tgt_triangular_update_fwd', _ptr(e4), _ptr(v4), _ptr(mask3), _ptr(out), B, N, H, _DT[ev.dtype])
@@ -1141,23 +1148,30 @@ class _TriangularUpdatePacked(torch.autograd.Function):
         if ctx.tiled:
             d_ev = torch.empty_like(ev)
             off = 4 * H * ev.element_size()
-            _launch('tgt_triangular_update_tiled_bwd', _ptr(ev), 8 * H, C.c_void_p(ev.data_ptr() + off), 8 * H, _ptr(mask3), _ptr(d_out),
-                    _ptr(d_ev), 8 * H, C.c_void_p(d_ev.data_ptr() + off), 8 * H, B, N, H, _DT[ev.dtype],
-                    prof='tgt_triangular_update_tiled_bwd')
-            return d_ev, None, None
+            operands = (_ptr(ev), 8 * H, C.c_void_p(ev.data_ptr() + off), 8 * H, _ptr(mask3), _ptr(d_out),
+                        _ptr(d_ev), 8 * H, C.c_void_p(d_ev.data_ptr() + off), 8 * H, B, N, H, _DT[ev.dtype])
+            if ctx.node_counts is None:
+                _launch('tgt_triangular_update_tiled_bwd', *operands, prof='tgt_triangular_update_tiled_bwd')
+            else:
+                _launch('tgt_triangular_update_tiled_bwd_counts', *operands, _ptr(ctx.node_counts), prof='tgt_triangular_update_tiled_bwd')
+            return d_ev, None, None, None
         e4, v4 = ev[..., :4 * H].contiguous(), ev[..., 4 * H:].contiguous()
         d_e4, d_v4 = torch.empty_like(e4), torch.empty_like(v4)
         _launch('tgt_triangular_update_bwd', _ptr(e4), _ptr(v4), _ptr(mask3), _ptr(d_out), _ptr(d_e4), _ptr(d_v4), B, N, H, _DT[ev.dtype])
-        return torch.cat((d_e4, d_v4), dim=-1), None, None
+        return torch.cat((d_e4, d_v4), dim=-1), None, None, None
 
 
-def triangular_update_packed(ev, mask3, num_heads):
+def triangular_update_packed(ev, mask3, num_heads, node_counts=None):
     """ev: (B,N,N,8H) = [lin_E | lin_V] outputs of one fused projection -> (B,N,N,2H): ops.triangular_update without the two
     separate operands.  TGT_TRIUPD_TILED and a shape the tiled kernels take (16-bit, N <= 64, H a multiple of 4): the core on
-    matrix-core tiles; otherwise the existing kernel on the two halves."""
+    matrix-core tiles; otherwise the existing kernel on the two halves.
+    node_counts (B,) int32 on the device: ragged batches -- the tiled kernels neither load nor multiply the pairs with a node
+    >= node_counts[b]; the result and the gradient there are zeros.  The mask must close every such pair, ROWS as well as columns
+    (tgt_hip.h, tgt_triangular_update_tiled_fwd_counts); then the call equals the one without counts.  The lane-per-head route
+    ignores the counts."""
     if ev.shape[-1] != 8 * num_heads:
         raise ValueError(f'triangular_update_packed: ev has {ev.shape[-1]} columns, expected 8 * num_heads = {8 * num_heads}')
-    return _TriangularUpdatePacked.apply(ev, mask3, num_heads)
+    return _TriangularUpdatePacked.apply(ev, mask3, num_heads, node_counts)
 
 
 # ---------------------------------------------------------------------------
@@ -2796,10 +2810,15 @@ class _GatedLinearResidualLN(torch.autograd.Function):
         a.res, a.s, a.y, a.gamma, a.beta, a.eps = res.data_ptr(), s.data_ptr(), y.data_ptr(), g.data_ptr(), be.data_ptr(), float(eps)
         a.mean, a.rstd = mean.data_ptr(), rstd.data_ptr()
         a.row_scale, a.rows_per_sample = (None if scale is None else scale.data_ptr()), rps
-        _launch('tgt_edge_gated_out_fwd', C.byref(a), prof='tgt_edge_gated_out_fwd')
+        # (ragged: the live tile list of the forward in progress, when it describes exactly these rows -- kept for the backward)
+        live = _edge_live
+        ctx.live = live = live if (live is not None and live.rows == rows and live.tiles.device == x2.device) else None
+        if live is None:
+            _launch('tgt_edge_gated_out_fwd', C.byref(a), prof='tgt_edge_gated_out_fwd')
+        else:
+            _launch('tgt_edge_gated_out_fwd_live', C.byref(a), _ptr(live.tiles), prof='tgt_edge_gated_out_fwd')
         ctx.save_for_backward(x2, w, b, s, g, mean, rstd, scale)
         ctx.lndt, ctx.rdt, ctx.rps = ln_w.dtype, res.dtype, rps
-        ctx.live = _edge_live
         return s, y
 
     @staticmethod
@@ -2825,7 +2844,10 @@ class _GatedLinearResidualLN(torch.autograd.Function):
         a = _gated_args(x2, w, b, C_)
         a.parts, a.dt, a.d_a, a.ld_da = parts, d_t.data_ptr(), d_a.data_ptr(), K_
         a.dw_partial, a.db_partial = dw_part.data_ptr(), db_part.data_ptr()
-        _launch('tgt_edge_gated_out_bwd', C.byref(a), prof='tgt_edge_gated_out_bwd')
+        if ctx.live is None:
+            _launch('tgt_edge_gated_out_bwd', C.byref(a), prof='tgt_edge_gated_out_bwd')
+        else:              # the list object of the forward: the backward skips what its forward skipped
+            _launch('tgt_edge_gated_out_bwd_live', C.byref(a), _ptr(ctx.live.tiles), prof='tgt_edge_gated_out_bwd')
         need = ctx.needs_input_grad
         dw = db = None
         with _on_stream(_terminal_fork(rows, dw_part, db_part)):

@@ -216,18 +216,31 @@ class TriangularUpdate(_TripletBase):
     def forward(self, e, mask):
         return self.forward_normed(self.tri_ln_e(e), mask)
 
-    def forward_normed(self, x, mask):
+    takes_node_counts = True          # forward_normed / attend(..., node_counts=): padded nodes of a ragged batch are not computed
+
+    # ... and its counts must bound the ROWS of the mask as well as the columns: all four operands are gated by the mask of their
+    # own pair, [a,k] and [k,a] alike (TGT_Encoder then takes the larger of the counts of the mask and of its transpose)
+    node_counts_bound_rows = True
+
+    def forward_normed(self, x, mask, node_counts=None):
+        """the block after tri_ln_e.  node_counts (B,) int32: as attend(); without them, ops.triangular_update on the two
+        separate projections, as ever"""
+        if node_counts is not None:
+            gate, lin = self.lin_O(self.attend(x, mask, node_counts)).chunk(2, dim=-1)
+            return torch.sigmoid(gate) * lin
         B, N = x.shape[0], x.shape[1]
         va = ops.triangular_update(self.lin_E(x), self.lin_V(x), ops.as_mask3(mask, B, N), self.num_heads)
         gate, lin = self.lin_O(va).chunk(2, dim=-1)
         return torch.sigmoid(gate) * lin
 
-    def attend(self, x, mask):
+    def attend(self, x, mask, node_counts=None):
         """the block after tri_ln_e without lin_O and the gate: lin_E and lin_V as ONE projection, then the core on its two
-        halves (ops.triangular_update_packed) -> (B,N,N,2H) = [O_in | O_out] (TGT_Layer fuses what follows: out_proj_residual_ln)"""
+        halves (ops.triangular_update_packed) -> (B,N,N,2H) = [O_in | O_out] (TGT_Layer fuses what follows: out_proj_residual_ln).
+        node_counts (B,) int32: ragged batches -- the tiled core skips every pair with a node >= node_counts[b]; the mask must
+        close those pairs, rows as well as columns, and then the result is the one without counts (zeros there either way)"""
         B, N = x.shape[0], x.shape[1]
         ev = ops.fused_linear(x, self._table, (self.lin_E.weight, self.lin_E.bias, self.lin_V.weight, self.lin_V.bias))
-        return ops.triangular_update_packed(ev, ops.as_mask3(mask, B, N), self.num_heads)
+        return ops.triangular_update_packed(ev, ops.as_mask3(mask, B, N), self.num_heads, node_counts=node_counts)
 
     def out_proj_residual_ln(self, va, res, scale, ln):
         """(s, LayerNorm(s)), s = res + scale * (sigmoid(g) * l), [g | l] = lin_O(va): lin_O here is 2H -> 2C in the reference's own

@@ -73,7 +73,8 @@ class TGT_Encoder(nn.Module):
 
     def _edge_ragged_ok(self):
         """may the edge row kernels leave the padded rows out?  Only when no layer lets a padded row reach a real one: a triplet
-        module must take the node counts (the attention family: every key of a padded node is masked).  The aggregate family's
+        module must take the node counts (the attention family: every key of a padded node is masked; TriangularUpdate: every
+        operand of a pair with a padded node is gated to an exact zero).  The aggregate family's
         gated outward direction is unmasked (quirk Q2), so its padded rows DO reach real outputs: such a model computes everything."""
         return self._padding_is_unread('edge_ragged', 'TGT_EDGE_RAGGED has no effect on this model: a triplet module that does not take '
                                        'node counts (the aggregate family) reads padded rows; every edge row is computed')
@@ -85,6 +86,10 @@ class TGT_Encoder(nn.Module):
         if not ok:
             ops._slow_path_notice(key, notice)
         return ok
+
+    def _counts_bound_rows(self):
+        """does some triplet module need counts that bound the rows of the mask as well as its columns?"""
+        return any(getattr(layer.tria, 'node_counts_bound_rows', False) for layer in self.TGT_layers if hasattr(layer, 'tria'))
 
     def _node_ragged_ok(self):
         """may node attention leave the padded nodes out?  Its H_hat is then zero at padded pairs instead of a finite value, which
@@ -104,7 +109,8 @@ class TGT_Encoder(nn.Module):
         if own_counts:
             mask3 = ops.as_mask3(graph.mask, graph.e.shape[0], graph.e.shape[1])
             graph['node_counts'] = ops.mask_node_counts(mask3)
-            if node_ragged:
+            # (a triplet module whose operands are gated by the mask of their own pair -- TriangularUpdate -- needs the row half too)
+            if node_ragged or self._counts_bound_rows():
                 graph['node_counts'] = torch.maximum(graph['node_counts'], ops.mask_node_counts(mask3.transpose(1, 2).contiguous()))
         if node_ragged and graph.get('node_counts') is not None:
             graph['node_ragged'] = True
